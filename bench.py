@@ -1,9 +1,14 @@
 """bench.py — headline benchmark of the HyperVLA action-prediction path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch 256] [--enc-dtype f16|bf16]
+    python bench.py --gpus N --steps K --warmup W [--batch 256] [--enc-dtype f16|bf16] [--full] [--dump-outputs DIR]
     (N > 1 works as typed: without WORLD_SIZE in the environment the script starts its own ranks with
      `python -m torch.distributed.run --nproc-per-node N ...` as a CHILD process before anything touches the GPU;
      under a launcher that already set RANK / WORLD_SIZE it is one of the ranks.)
+
+A plain run sets up, warms up, times K steps and prints the result line.  --full adds the figures that take passes of
+their own: the box probe, the roofline of the dominant kernel (HIP events around its launches inside the timed region),
+the p50 step latency, the per-kernel breakdown, the policy-only variant and the CPU baseline (for --finetune: the GEMM
+roofline).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; inputs are seeded).
 
 One "step" = one `sample_actions` over one batch of synthetic OXE-shaped observations: uint8 224x224
 images -> DINOv2-base (in the loop, as the reference runs it, base_vit.py:109-133) -> generated vit_t
@@ -160,6 +165,13 @@ def cpu_baseline(g, params, seconds=12.0, batch=8):
                       f"{dt:.1f} s)"}
 
 
+def dump_outputs(d, arrays, rank, world):
+    """--dump-outputs: one float32 .npy per array a caller of the timed path receives (rank-suffixed when N > 1)."""
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(d, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), x.detach().float().cpu().numpy())
+
+
 def finetune_bench(a, model, rank, world, use_dist):
     """Config 5: one optimiser step per iteration on a per-GPU batch; `value` = samples/s over all ranks."""
     from hypervla import synthetic as syn
@@ -184,28 +196,31 @@ def finetune_bench(a, model, rank, world, use_dist):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
-    # the step's dominant kernel family, timed live on two more steps (HIP events on the launch stream around every batched GEMM
-    # launch: hvla_train_profile): csrc/train.hip bgemm3_kernel, the split-bf16 GEMM of every forward / dX / dW product
-    model._ctx.train_profile(True)
-    for _ in range(2):
-        ft.step(ins, st, images, batch)
-    torch.cuda.synchronize(dev)
-    gemm_ms, gemm_flops, gemm_n = model._ctx.train_profile_read()
-    model._ctx.train_profile(False)
-    f32_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    roofline = {"bound": "mfma", "kernel": "bgemm3_kernel (csrc/train.hip): every dense product of the step, f32 operands split hi + lo "
-                                           "while staged, THREE v_mfma_f32_32x32x16_bf16 per product (a_hi b_hi + a_hi b_lo + a_lo b_hi)",
-                "achieved": round(f32_tflops, 2), "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(f32_tflops / PEAK_TFLOPS, 4),
-                "matrix_instruction_tflops": round(3.0 * f32_tflops, 2), "matrix_instruction_frac": round(3.0 * f32_tflops / PEAK_TFLOPS, 4),
-                "mfma_per_product": 3, "traffic": None,
-                "gemm_ms_per_step": round(gemm_ms / 2, 3), "gemm_launches_per_step": gemm_n // 2,
-                "gemm_flops_per_step_f32_equivalent": gemm_flops / 2,
-                "note": "achieved / frac = USEFUL work (f32-equivalent 2MNK) / summed duration of the GEMM launches against the bf16 peak; "
-                        "the matrix cores execute three instructions per product (matrix_instruction_*); "
-                        "the rest of the step is element-wise kernels and the optimiser"}
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"loss": last}, rank, world)
+    if a.full:
+        # the step's dominant kernel family, timed live on two more steps (HIP events on the launch stream around every batched GEMM
+        # launch: hvla_train_profile): csrc/train.hip bgemm3_kernel, the split-bf16 GEMM of every forward / dX / dW product
+        model._ctx.train_profile(True)
+        for _ in range(2):
+            ft.step(ins, st, images, batch)
+        torch.cuda.synchronize(dev)
+        gemm_ms, gemm_flops, gemm_n = model._ctx.train_profile_read()
+        model._ctx.train_profile(False)
+        f32_tflops = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        roofline = {"bound": "mfma", "kernel": "bgemm3_kernel (csrc/train.hip): every dense product of the step, f32 operands split hi + lo "
+                                               "while staged, THREE v_mfma_f32_32x32x16_bf16 per product (a_hi b_hi + a_hi b_lo + a_lo b_hi)",
+                    "achieved": round(f32_tflops, 2), "peak": PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(f32_tflops / PEAK_TFLOPS, 4),
+                    "matrix_instruction_tflops": round(3.0 * f32_tflops, 2), "matrix_instruction_frac": round(3.0 * f32_tflops / PEAK_TFLOPS, 4),
+                    "mfma_per_product": 3, "traffic": None,
+                    "gemm_ms_per_step": round(gemm_ms / 2, 3), "gemm_launches_per_step": gemm_n // 2,
+                    "gemm_flops_per_step_f32_equivalent": gemm_flops / 2,
+                    "note": "achieved / frac = USEFUL work (f32-equivalent 2MNK) / summed duration of the GEMM launches against the bf16 peak; "
+                            "the matrix cores execute three instructions per product (matrix_instruction_*); "
+                            "the rest of the step is element-wise kernels and the optimiser"}
     if rank == 0:
         print(json.dumps({
-            "roofline": roofline,
+            **({"roofline": roofline} if a.full else {}),
             "metric": "finetune_samples_per_sec", "value": round(whole_job_rate(B, world, a.steps, elapsed), 2),
             "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
@@ -290,7 +305,14 @@ def main():
                          "unless --train-encoder)")
     ap.add_argument("--train-encoder", action="store_true",
                     help="with --finetune: fine_tune_pretrained_image_encoder=True (README.md:55)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take passes of their own: box probe, roofline, p50 latency, per-kernel breakdown, "
+                         "policy-only variant, CPU baseline (a plain run times the steps and prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus))
@@ -351,12 +373,9 @@ def main():
             ctx.ensemble(w._h, actions.data_ptr(), ens[0].data_ptr(), ens[1].data_ptr(), ens[2].data_ptr(),
                          ens[3].data_ptr(), stream)
 
-    box = box_probe(ctx, dev) if rank == 0 else None
+    box = box_probe(ctx, dev) if (a.full and rank == 0) else None
     for _ in range(a.warmup):
         step()
-    ctx.launches()
-    step()
-    launches = ctx.launches()         # what the library enqueued for one eager step (hvla_launches)
     eager_step = step
     if a.graph:                        # capture one step (launches only, no allocation / sync inside hvla_step)
         torch.cuda.synchronize(dev)
@@ -372,39 +391,74 @@ def main():
         stream = model._stream()
         step = graph.replay
         step()
-    # ---- which kernel symbol is the dominant one?  An un-timed pass with events around every category (hvla_profile mode 2), then the
-    # categories of the symbol with the largest share are the ones whose launches carry events inside the timed region (mode 1).
-    parts = 2 if (a.streams == 2 and B >= 64) else 1       # episodes per launch = B / parts
-    symbols = big_gemm_symbols(B // parts, g, a.enc_dtype)
-    dom_cats = ["fc1_gemm"]
-    if symbols is not None:
-        ctx.profile(2)
-        for _ in range(2):
-            eager_step()
-        torch.cuda.synchronize(dev)
-        pre = ctx.profile_read()
-        share = {}
-        for cat, (name, _) in symbols.items():
-            share[name] = share.get(name, 0.0) + pre[cat][0]
-        dom_symbol = max(share, key=share.get)
-        dom_cats = [c for c, (name, _) in symbols.items() if name == dom_symbol]
-    ctx.profile_select(dom_cats)
-    ctx.profile(0 if a.graph else 1)   # HIP events around the dominant kernel's launches only, on the launch stream
+    if a.full:
+        # ---- which kernel symbol is the dominant one?  An un-timed pass with events around every category (hvla_profile mode 2), then
+        # the categories of the symbol with the largest share are the ones whose launches carry events inside the timed region (mode 1).
+        parts = 2 if (a.streams == 2 and B >= 64) else 1       # episodes per launch = B / parts
+        symbols = big_gemm_symbols(B // parts, g, a.enc_dtype)
+        dom_cats = ["fc1_gemm"]
+        if symbols is not None:
+            ctx.profile(2)
+            for _ in range(2):
+                eager_step()
+            torch.cuda.synchronize(dev)
+            pre = ctx.profile_read()
+            share = {}
+            for cat, (name, _) in symbols.items():
+                share[name] = share.get(name, 0.0) + pre[cat][0]
+            dom_symbol = max(share, key=share.get)
+            dom_cats = [c for c, (name, _) in symbols.items() if name == dom_symbol]
+        ctx.profile_select(dom_cats)
+        ctx.profile(0 if a.graph else 1)   # HIP events around the dominant kernel's launches only, on the launch stream
     sync_all()
+    ctx.launches()
     t0 = time.perf_counter()
     for _ in range(a.steps):
         step()
     sync_all()
     elapsed = time.perf_counter() - t0
-    if a.graph:                        # events cannot be recorded inside a replayed graph: time the dominant
-        ctx.profile(1)                 # kernel on eager launches of the same step right after the timed region
-        for _ in range(3):
-            eager_step()
-        torch.cuda.synchronize(dev)
-    dom = ctx.profile_read()
-    ctx.profile(0)
+    launches = ctx.launches() // a.steps       # what the library enqueued per eager step (hvla_launches; a replay enqueues none)
+    if a.dump_outputs:                 # what a caller of hvla_step (+ hvla_ensemble) receives, before any un-timed pass overwrites it
+        dump_outputs(a.dump_outputs, {"actions": actions, "gripper_logits": logits,
+                                      **({"ensembled_actions": ens[3]} if ens is not None else {})}, rank, world)
+    if a.full:
+        if a.graph:                    # events cannot be recorded inside a replayed graph: time the dominant
+            ctx.profile(1)             # kernel on eager launches of the same step right after the timed region
+            for _ in range(3):
+                eager_step()
+            torch.cuda.synchronize(dev)
+        dom = ctx.profile_read()
+        ctx.profile(0)
     elapsed = max_over_ranks(elapsed, dev)
     if rank != 0:
+        if use_dist:
+            dist.destroy_process_group()
+        return
+    ms_per_step = elapsed / a.steps * 1e3
+    fl = algorithmic_flops(g)
+    out = {
+        "metric": "actions_per_sec", "value": round(whole_job_rate(B, world, a.steps, elapsed), 2), "unit": "actions/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.enc_dtype, "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[2] (hipGraph-captured step incl. device-side ensemble): " if a.graph else
+                                "BASELINE configs[1]: ") + "hypernet weight-gen once (untimed) + full sample_actions step "
+                               f"(u8 224x224 -> DINOv2-{a.encoder} E={g.enc_dim} in the loop -> generated vit_t 4L/64d policy -> "
+                               "[4,7] action chunk); 1 action = 1 sample-step",
+                   "batch_per_gpu": B, "global_batch": world * B, "encoder": "DINOv2-base (reference parity, E=768)" if a.encoder == "base" else "DINOv2-small (E=384)",
+                   "parallelism": f"episode-dp{world} (no collectives)",
+                   "encoder_operands": a.enc_dtype + " (+ per-image first-order compensation of the weight rounding, "
+                                       "kernel_ms_per_step.small_row_gemms)",
+                   "policy_operands": "split-bf16 (bf16x3)",
+                   "launch": "hipGraph replay" if a.graph else f"eager ({launches} launches per step, counted by the library)",
+                   "streams": a.streams,
+                   "ensemble": "device-side un-normalise + temporal ensemble (history = horizon) inside the step"
+                               if ens is not None else "not in the step"},
+        "step_tflops": round((fl["encoder"] + fl["policy"]) * B / (ms_per_step * 1e-3) / 1e12, 2),
+        "step_frac_of_peak": round((fl["encoder"] + fl["policy"]) * B / (ms_per_step * 1e-3) / 1e12 / PEAK_TFLOPS, 4),
+        "generate_ms": round(generate_ms, 3),
+    }
+    if not a.full:
+        print(json.dumps(out))
         if use_dist:
             dist.destroy_process_group()
         return
@@ -446,7 +500,6 @@ def main():
     torch.cuda.synchronize(dev)
     pol_ms = e0.elapsed_time(e1) / 100
 
-    fl = algorithmic_flops(g)
     rows = (B // parts) * (g.patches + 1)
     main_rows = fc1_main_rows(B // parts, g)
     if symbols is None:                 # small batch: the fc1 launch (gemm64c_kernel / gemm64_kernel), as rounds 1-5 reported it
@@ -484,24 +537,7 @@ def main():
             hbm_tbps = round(traffic / (dom_ms * 1e-3) / 1e12, 3)
         if "SQ_VALU_MFMA_BUSY_CYCLES" in pm and pm.get("GRBM_GUI_ACTIVE", 0) > 0:
             mfma_busy = round(pm["SQ_VALU_MFMA_BUSY_CYCLES"] / (pm["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0), 4)
-    ms_per_step = elapsed / a.steps * 1e3
-    out = {
-        "metric": "actions_per_sec", "value": round(whole_job_rate(B, world, a.steps, elapsed), 2), "unit": "actions/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.enc_dtype, "data": "synthetic",
-        "config": {"workload": ("BASELINE configs[2] (hipGraph-captured step incl. device-side ensemble): " if a.graph else
-                                "BASELINE configs[1]: ") + "hypernet weight-gen once (untimed) + full sample_actions step "
-                               f"(u8 224x224 -> DINOv2-{a.encoder} E={g.enc_dim} in the loop -> generated vit_t 4L/64d policy -> "
-                               "[4,7] action chunk); 1 action = 1 sample-step",
-                   "batch_per_gpu": B, "global_batch": world * B, "encoder": "DINOv2-base (reference parity, E=768)" if a.encoder == "base" else "DINOv2-small (E=384)",
-                   "parallelism": f"episode-dp{world} (no collectives)",
-                   "encoder_operands": a.enc_dtype + " (+ per-image first-order compensation of the weight rounding, "
-                                       "kernel_ms_per_step.small_row_gemms)",
-                   "policy_operands": "split-bf16 (bf16x3)",
-                   "launch": "hipGraph replay" if a.graph else f"eager ({launches} launches per step, counted by the library)",
-                   "streams": a.streams,
-                   "ensemble": "device-side un-normalise + temporal ensemble (history = horizon) inside the step"
-                               if ens is not None else "not in the step"},
+    out.update({
         "box": box,
         "latency_samples": len(lat),
         "p50_step_latency_ms": round(float(np.median(lat)), 4),
@@ -517,13 +553,10 @@ def main():
                      "launch_ms": round(dom_ms, 4), "launches_timed": dom_n,
                      "flops_per_launch": flops_per_launch, "rows_per_launch": main_rows, "rows_total": rows,
                      "by_shape": by_shape},
-        "step_tflops": round((fl["encoder"] + fl["policy"]) * B / (ms_per_step * 1e-3) / 1e12, 2),
-        "step_frac_of_peak": round((fl["encoder"] + fl["policy"]) * B / (ms_per_step * 1e-3) / 1e12 / PEAK_TFLOPS, 4),
         "kernel_ms_per_step": breakdown,
         "policy_only": {"ms_per_step": round(pol_ms, 4), "actions_per_sec": round(B / (pol_ms * 1e-3), 1),
                         "input": "f32 patch tokens [B,256,768] resident in HBM"},
-        "generate_ms": round(generate_ms, 3),
-    }
+    })
     if world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(g, model.params)
     print(json.dumps(out))

@@ -1018,9 +1018,10 @@ def test_two_stream_step_with_a_narrow_mlp():
     np.testing.assert_array_equal(outs[1][1], outs[0][1])
 
 
-def test_bench_contract_with_two_ranks_on_one_gpu():
+def test_bench_contract_with_two_ranks_on_one_gpu(tmp_path):
     """bench.py's N > 1 control flow (barrier, max over ranks, rank 0 prints ONE line, whole-job value) on a one-GPU box:
-    two ranks share GPU 0 over gloo (test hook HVLA_BENCH_SHARE_GPU); the driver's real runs use RCCL, one rank per GPU."""
+    two ranks share GPU 0 over gloo (test hook HVLA_BENCH_SHARE_GPU); the driver's real runs use RCCL, one rank per GPU.
+    Every rank writes its last timed step under --dump-outputs; the roofline and latency figures come with --full only."""
     import json
     import os
     import subprocess
@@ -1028,20 +1029,30 @@ def test_bench_contract_with_two_ranks_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HVLA_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     import socket
-    for extra in ([], ["--finetune"]):
+    for k, extra in enumerate(([], ["--finetune"], ["--full"])):
         with socket.socket() as sk:                          # a fresh port per launch: the previous one may still be in TIME_WAIT
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
+        dump = tmp_path / str(k)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-               "--batch", "8", "--no-cpu-baseline"] + extra
+               "--batch", "8", "--no-cpu-baseline", "--dump-outputs", str(dump)] + extra
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, r.stdout
         d = json.loads(lines[0])
         assert d["n_gpus"] == 2 and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
-        assert d["config"]["global_batch"] == 16 if not extra else True
+        assert d["config"]["global_batch"] == 16 if extra != ["--finetune"] else True
+        assert d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["unit"] and d["dtype"]
+        assert ("roofline" in d) == ("--full" in extra) and ("p50_step_latency_ms" in d) == ("--full" in extra)
+        for rank in (0, 1):
+            if extra == ["--finetune"]:
+                assert np.isfinite(np.load(dump / f"loss_rank{rank}.npy")).all()
+            else:
+                a = np.load(dump / f"actions_rank{rank}.npy")
+                assert a.shape == (8, 4, 7) and a.dtype == np.float32 and np.isfinite(a).all()
+                assert np.load(dump / f"gripper_logits_rank{rank}.npy").shape == (8, 4)
 
 
 @pytest.mark.gpu
