@@ -43,6 +43,7 @@ using hvla::pack::f2h;
 struct hvla_weights {
   int B = 0;
   DevBuf wh, wl, vf, ctx, ring, count;
+  DevBuf slot_count;             // int32 [B]: the episode pool's per-row ensemble counters (hvla_ensemble_slots)
 };
 
 struct hvla_ctx {
@@ -398,6 +399,42 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   return HVLA_OK;
 }
 
+// an arena of B episodes: one handed back by hvla_weights_free if the ctx holds one of that size, else a new allocation
+static int take_arena(hvla_ctx* ctx, int32_t B, std::unique_ptr<hvla_weights>& w) {
+  const PolicyLayout& pl = ctx->lay.pl;
+  const Geom& g = ctx->g;
+  {
+    std::lock_guard<std::mutex> lk(ctx->pool_mu);
+    for (size_t i = 0; i < ctx->arena_pool.size(); ++i)        // an arena of this batch size handed back earlier
+      if (ctx->arena_pool[i]->B == B) {
+        w.reset(ctx->arena_pool[i]);
+        ctx->arena_pool.erase(ctx->arena_pool.begin() + i);
+        return HVLA_OK;
+      }
+  }
+  w.reset(new hvla_weights);
+  w->B = B;
+  hipError_t e = hipSuccess;
+  auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
+  auto all = [&]() {
+    A(w->wh, (size_t)B * pl.Gm * 2); A(w->wl, (size_t)B * pl.Gm * 2); A(w->vf, (size_t)B * pl.Gv * 4);
+    A(w->ctx, (size_t)B * g.C * 4);
+    A(w->ring, (size_t)g.horizon * B * g.horizon * g.action_dim * 4); A(w->count, 16); A(w->slot_count, (size_t)B * 4);
+  };
+  all();
+  if (e != hipSuccess) {
+    {
+      std::lock_guard<std::mutex> lk(ctx->pool_mu);
+      for (hvla_weights* q : ctx->arena_pool) delete q;      // give the pooled arenas back to the device and retry once
+      ctx->arena_pool.clear();
+    }
+    e = hipSuccess;
+    all();
+  }
+  if (e != hipSuccess) FAIL(ctx, HVLA_E_ARENA_FULL, "weight arena for %d episodes: %s", B, hipGetErrorString(e));
+  return HVLA_OK;
+}
+
 int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const float* cls, int32_t B,
                   hvla_weights** out, void* stream) {
   if (!ctx || !out) return HVLA_E_STATE;
@@ -410,37 +447,9 @@ int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const fl
   const PolicyLayout& pl = ctx->lay.pl;
   const Geom& g = ctx->g;
   std::unique_ptr<hvla_weights> w;
-  {
-    std::lock_guard<std::mutex> lk(ctx->pool_mu);
-    for (size_t i = 0; i < ctx->arena_pool.size(); ++i)        // an arena of this batch size handed back earlier
-      if (ctx->arena_pool[i]->B == B) {
-        w.reset(ctx->arena_pool[i]);
-        ctx->arena_pool.erase(ctx->arena_pool.begin() + i);
-        break;
-      }
-  }
-  if (!w) {
-    w.reset(new hvla_weights);
-    w->B = B;
-    hipError_t e = hipSuccess;
-    auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
-    A(w->wh, (size_t)B * pl.Gm * 2); A(w->wl, (size_t)B * pl.Gm * 2); A(w->vf, (size_t)B * pl.Gv * 4);
-    A(w->ctx, (size_t)B * g.C * 4);
-    A(w->ring, (size_t)g.horizon * B * g.horizon * g.action_dim * 4); A(w->count, 16);
-    if (e != hipSuccess) {
-      {
-        std::lock_guard<std::mutex> lk(ctx->pool_mu);
-        for (hvla_weights* q : ctx->arena_pool) delete q;      // give the pooled arenas back to the device and retry once
-        ctx->arena_pool.clear();
-      }
-      e = hipSuccess;
-      A(w->wh, (size_t)B * pl.Gm * 2); A(w->wl, (size_t)B * pl.Gm * 2); A(w->vf, (size_t)B * pl.Gv * 4);
-      A(w->ctx, (size_t)B * g.C * 4);
-      A(w->ring, (size_t)g.horizon * B * g.horizon * g.action_dim * 4); A(w->count, 16);
-    }
-    if (e != hipSuccess) FAIL(ctx, HVLA_E_ARENA_FULL, "weight arena for %d episodes: %s", B, hipGetErrorString(e));
-  }
+  if (int r = take_arena(ctx, B, w)) return r;
   HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, st));
+  HIPCHK(ctx, hipMemsetAsync(w->slot_count.p, 0, w->slot_count.bytes, st));   // (the arena may have served as an episode pool)
   CtxParams cp = ctx->ctxp;
   cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
   cp.ctx = w->ctx.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
@@ -563,18 +572,24 @@ int hvla_encode_audit(hvla_ctx* ctx, const uint8_t* images, int32_t B, float* ma
   return HVLA_OK;
 }
 
+// slots (episode pool): call row b takes its weights from arena row slots[b]; the arena pointers then stay at row 0 and the
+// slot map moves with b0 instead
 static int policy_range(hvla_ctx* ctx, const hvla_weights* w, const float* tokens, float* actions, float* logits, int b0,
-                        int nb, hipStream_t st) {
+                        int nb, hipStream_t st, const int32_t* slots = nullptr) {
   const Geom& g = ctx->g;
   const PolicyLayout& pl = ctx->lay.pl;
-  PolicyParams p{pl, w->wh.as<__bf16>() + (size_t)b0 * pl.Gm, w->wl.as<__bf16>() + (size_t)b0 * pl.Gm,
-                 w->vf.as<float>() + (size_t)b0 * pl.Gv, tokens + (size_t)b0 * g.P() * g.E,
+  const size_t wb = slots ? 0 : (size_t)b0;
+  PolicyParams p{pl, w->wh.as<__bf16>() + wb * pl.Gm, w->wl.as<__bf16>() + wb * pl.Gm,
+                 w->vf.as<float>() + wb * pl.Gv, tokens + (size_t)b0 * g.P() * g.E,
                  actions + (size_t)b0 * g.horizon * g.action_dim, logits ? logits + (size_t)b0 * g.horizon : nullptr,
                  nb, g.E, g.P(), g.L, g.M, g.horizon, g.action_dim, g.tanh_scale, g.max_action};
   if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * g.P();
   ctx->prof.begin(HVLA_PROF_POLICY, st);
   ++ctx->prof.nlaunch;
-  HIPCHK(ctx, launch_policy(p, st));
+  if (slots)
+    HIPCHK(ctx, launch_policy_slots(p, slots + b0, w->B, st));
+  else
+    HIPCHK(ctx, launch_policy(p, st));
   ctx->prof.end(HVLA_PROF_POLICY, st);
   return HVLA_OK;
 }
@@ -627,6 +642,7 @@ int hvla_step(hvla_ctx* ctx, const hvla_weights* w, const uint8_t* images, float
 int hvla_ensemble_reset(hvla_ctx* ctx, hvla_weights* w, void* stream) {
   if (!ctx || !w) return HVLA_E_STATE;
   HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, reinterpret_cast<hipStream_t>(stream)));
+  HIPCHK(ctx, hipMemsetAsync(w->slot_count.p, 0, w->slot_count.bytes, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;
 }
 
@@ -638,6 +654,90 @@ int hvla_ensemble(hvla_ctx* ctx, hvla_weights* w, const float* actions, const fl
   ++ctx->prof.nlaunch;
   HIPCHK(ctx, launch_ensemble(actions, w->ring.as<float>(), w->count.as<int>(), mean, std, mask, out, w->B,
                               ctx->g.horizon, ctx->g.action_dim, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+// ------------------------------------------------------------------ episode pool (include/hvla.h)
+int hvla_weights_alloc(hvla_ctx* ctx, int32_t B, hvla_weights** out, void* stream) {
+  if (!ctx || !out) return HVLA_E_STATE;
+  *out = nullptr;
+  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "hvla_weights_alloc before hvla_load_weights");
+  if (B < 1 || B > ctx->cfg.max_batch) FAIL(ctx, HVLA_E_SHAPE, "pool of %d slots outside [1, %d]", B, ctx->cfg.max_batch);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  std::unique_ptr<hvla_weights> w;
+  if (int r = take_arena(ctx, B, w)) return r;
+  // empty slots: zero weights step to finite actions, zero counters start a fresh ensemble
+  for (DevBuf* b : {&w->wh, &w->wl, &w->vf, &w->ctx, &w->ring, &w->count, &w->slot_count})
+    HIPCHK(ctx, hipMemsetAsync(b->p, 0, b->bytes, st));
+  *out = w.release();
+  return HVLA_OK;
+}
+
+static int check_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K) {
+  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "called before hvla_load_weights");
+  if (!slots) FAIL(ctx, HVLA_E_SHAPE, "null slot map");
+  if (K < 1 || K > w->B || K > ctx->cfg.max_batch)
+    FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, min(%d slots of the pool, max_batch %d)]", K, w->B, ctx->cfg.max_batch);
+  return HVLA_OK;
+}
+
+int hvla_generate_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* tok, const int64_t* mask,
+                        const float* cls, void* stream) {
+  if (!ctx || !w) return HVLA_E_STATE;
+  if (int r = check_slots(ctx, w, slots, K)) return r;
+  if (!tok || !mask || !cls) FAIL(ctx, HVLA_E_SHAPE, "null input pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const PolicyLayout& pl = ctx->lay.pl;
+  const Geom& g = ctx->g;
+  // the K tasks through the unchanged context encoder into workspace rows 0 .. K-1, then into their slots
+  CtxParams cp = ctx->ctxp;
+  cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
+  cp.ctx = ctx->ctx_f32.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
+  HIPCHK(ctx, launch_ctx_encoder(cp, K, st));
+  WeightGenParams wp{ctx->wcat_hi.as<__bf16>(), ctx->wcat_lo.as<__bf16>(), ctx->bcat.as<float>(),
+                     ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
+                     w->vf.as<float>(), K, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
+  HIPCHK(ctx, launch_weightgen_slots(wp, g.C, slots, w->B, st));
+  HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.C, w->B, st));
+  return HVLA_OK;
+}
+
+int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K, const uint8_t* images, float* actions,
+                    float* logits, void* stream) {
+  if (!ctx || !w) return HVLA_E_STATE;
+  if (int r = check_slots(ctx, w, slots, K)) return r;
+  if (!images || !actions) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float* tokens = ctx->tokens.as<float>();
+  if (!ctx->side || K < 64) {
+    if (int r = encode_range(ctx, images, tokens, 0, K, false, st)) return r;
+    return policy_range(ctx, w, tokens, actions, logits, 0, K, st, slots);
+  }
+  const int b0 = K / 2;                                         // the two-stream form of hvla_step
+  HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
+  HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+  if (int r = encode_range(ctx, images, tokens, 0, b0, false, st)) return r;
+  if (int r = encode_range(ctx, images, tokens, b0, K - b0, false, ctx->side)) return r;
+  if (int r = policy_range(ctx, w, tokens, actions, logits, 0, b0, st, slots)) return r;
+  if (int r = policy_range(ctx, w, tokens, actions, logits, b0, K - b0, ctx->side, slots)) return r;
+  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
+  HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
+  return HVLA_OK;
+}
+
+int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* actions, const float* mean,
+                        const float* std, const uint8_t* mask, float* out, void* stream) {
+  if (!ctx || !w) return HVLA_E_STATE;
+  if (!slots) FAIL(ctx, HVLA_E_SHAPE, "null slot map");
+  if (K < 1 || K > w->B) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d]", K, w->B);
+  if (!actions || !mean || !std || !mask || !out) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_ensemble_slots(actions, w->ring.as<float>(), w->slot_count.as<int>(), slots, K, mean, std, mask, out, w->B,
+                                    ctx->g.horizon, ctx->g.action_dim, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;
 }
 

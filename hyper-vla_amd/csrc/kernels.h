@@ -36,6 +36,12 @@ struct WeightGenParams {
 hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st);
 size_t ctx_encoder_lds_bytes(int T, int C, int F, int E);       // dynamic LDS of ctx_encoder_kernel for a geometry (<= 160 KiB or refused at create)
 hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st);
+// episode pool: weightgen_kernel's output row of input episode r is arena row slot[r] of an arena of `rows`;
+// launch_pool_assign puts the K new context rows (f32 workspace rows 0 .. K-1) at arena rows slot[k] and zeroes those rows'
+// ensemble counters.  Slot entries outside [0, rows) are skipped by both.
+hipError_t launch_weightgen_slots(const WeightGenParams& p, int C, const int32_t* slot, int rows, hipStream_t st);
+hipError_t launch_pool_assign(const float* ctx_rows, float* ctx, int* count, const int32_t* slot, int K, int C, int rows,
+                              hipStream_t st);
 hipError_t launch_export_theta(const __bf16* wh, const __bf16* wl, const float* vf, const int32_t* perm,
                                int Gm, int Gv, int G, int B, float* theta, hipStream_t st);
 
@@ -133,11 +139,19 @@ struct PolicyParams {
 #endif
 };
 hipError_t launch_policy(const PolicyParams& p, hipStream_t st);
+// episode pool: workgroup b takes its weights from arena row slots[b] (p.wh / wl / vf point at row 0 of an arena of `rows`
+// episodes); tokens, actions, logits and attention rows stay call rows.  Entries outside [0, rows) are skipped.
+hipError_t launch_policy_slots(const PolicyParams& p, const int32_t* slots, int rows, hipStream_t st);
 
 // ---------------------------------------------------------------- caller-side device helpers
 hipError_t launch_ensemble(const float* actions, float* ring, int* count, const float* mean,
                            const float* std, const uint8_t* mask, float* out, int B, int horizon,
                            int action_dim, hipStream_t st);
+
+// episode pool: count [B] one counter per arena row; call row k is arena row slots[k]
+hipError_t launch_ensemble_slots(const float* actions, float* ring, int* count, const int32_t* slots, int K, const float* mean,
+                                 const float* std, const uint8_t* mask, float* out, int B, int horizon, int action_dim,
+                                 hipStream_t st);
 
 hipError_t launch_loss(const float* actions, const float* logits, const float* target, const uint8_t* tmask,
                        const uint8_t* amask, float* loss, int B, int horizon, int action_dim, float max_action,

@@ -23,7 +23,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_sizes", "hvla_train_step", "hvla_train_apply", "hvla_encode_hidden", "hvla_t5_load",
            "hvla_t5_encode", "hvla_preprocess", "hvla_encode_audit", "hvla_train_accumulate", "hvla_train_bucket_ranges",
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
-           "hvla_launches", "hvla_box_probe", "hvla_profile_select"]
+           "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
+           "hvla_step_slots", "hvla_ensemble_slots"]
 PROF_NAMES = ["patch_embed", "layernorm", "qkv_gemm", "attention", "out_gemm", "fc1_gemm", "fc2_gemm", "policy",
               "small_row_gemms"]      # mean rows + the 2 B latency-bound rows per GEMM: CLS rows and weight-rounding compensation rows
 
@@ -146,6 +147,14 @@ def load_library():
     lib.hvla_encode_audit.restype = C.c_int
     lib.hvla_set_attention_outputs.argtypes = [vp, vp, vp]
     lib.hvla_set_attention_outputs.restype = C.c_int
+    lib.hvla_weights_alloc.argtypes = [vp, i32, C.POINTER(vp), vp]
+    lib.hvla_weights_alloc.restype = C.c_int
+    lib.hvla_generate_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.hvla_generate_slots.restype = C.c_int
+    lib.hvla_step_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.hvla_step_slots.restype = C.c_int
+    lib.hvla_ensemble_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.hvla_ensemble_slots.restype = C.c_int
     lib.hvla_selftest.argtypes = [vp, vp]
     lib.hvla_selftest.restype = C.c_int
     _lib = lib
@@ -339,3 +348,21 @@ class Context:
     def ensemble(self, w, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr, stream=0):
         self._check(self.lib.hvla_ensemble(self.h, w, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr, C.c_void_p(stream)),
                     "hvla_ensemble")
+
+    # episode pool (include/hvla.h): `slots_ptr` is a device int32 [K] map that hypervla.pool.check_slots has accepted
+    def weights_alloc(self, B, stream=0):
+        w = C.c_void_p()
+        self._check(self.lib.hvla_weights_alloc(self.h, B, C.byref(w), C.c_void_p(stream)), "hvla_weights_alloc")
+        return w
+
+    def generate_slots(self, w, slots_ptr, K, tok_ptr, mask_ptr, cls_ptr, stream=0):
+        self._check(self.lib.hvla_generate_slots(self.h, w, C.c_void_p(slots_ptr), K, tok_ptr, mask_ptr, cls_ptr,
+                                                 C.c_void_p(stream)), "hvla_generate_slots")
+
+    def step_slots(self, w, slots_ptr, K, img_ptr, act_ptr, logit_ptr, stream=0):
+        self._check(self.lib.hvla_step_slots(self.h, w, C.c_void_p(slots_ptr), K, img_ptr, act_ptr, logit_ptr, C.c_void_p(stream)),
+                    "hvla_step_slots")
+
+    def ensemble_slots(self, w, slots_ptr, K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr, stream=0):
+        self._check(self.lib.hvla_ensemble_slots(self.h, w, C.c_void_p(slots_ptr), K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr,
+                                                 C.c_void_p(stream)), "hvla_ensemble_slots")

@@ -279,3 +279,89 @@ class BatchEvaluator:
                     active[i] = False
         return {"success": success, "steps": steps, "instructions": list(instructions), "model_seconds": t_model,
                 "sim_seconds": t_sim, "raw_actions": raw_log}
+
+    def run_episodes(self, venv, tokenize: Callable[[List[str]], Dict[str, np.ndarray]], episodes: int, max_steps: int,
+                     reset_kwargs_for: Optional[Callable[[int], dict]] = None,
+                     success_from: Callable[[bool, dict], bool] = lambda done, info: bool(done)) -> Dict[str, Any]:
+        """`episodes` episodes on the E simulators of `venv`, continuously: simulator i runs its episodes in slot i of one episode
+        pool of capacity E (`model.create_pool`).  When episodes end and work remains, only their simulators are reset (with
+        `reset_kwargs_for(n)` for episode n), their first frames are encoded in one `encode_initial_image` and their tasks
+        assigned in one `assign_tasks`; each then starts with a fresh `InferenceWrapper` state.  Each timestep steps only the
+        slots whose episode is running (`sample_actions(..., slots=)`).  An episode ends on success, truncation or after
+        `max_steps` steps.
+
+        Returns per-episode arrays in episode order -- `success`, `steps`, `instructions`, `env_index` (the simulator, = slot,
+        that ran it) -- and `model_seconds`, `sim_seconds` and `rows_stepped` (slot-steps sent to the device; == steps.sum())."""
+        E, N = len(venv), int(episodes)
+        if N < 1:
+            raise ValueError(f"episodes must be >= 1, got {episodes}")
+        success, steps = np.zeros(N, bool), np.zeros(N, int)
+        instructions: List[Optional[str]] = [None] * N
+        env_index = np.full(N, -1, int)
+        running = np.full(E, -1, int)                        # simulator / slot -> episode it runs (-1: idle)
+        wrappers: List[Optional[InferenceWrapper]] = [None] * E
+        t_sim = t_model = 0.0
+        rows = 0
+        t0 = time.perf_counter()
+        pool = self.model.create_pool(E)
+        t_model += time.perf_counter() - t0
+        nxt = 0
+
+        def start(sims: List[int]):
+            nonlocal nxt, t_sim, t_model
+            sims = sims[: N - nxt]
+            if not sims:
+                return
+            eps = list(range(nxt, nxt + len(sims)))
+            nxt += len(sims)
+            t0 = time.perf_counter()
+            if reset_kwargs_for is None:
+                venv.reset(ids=sims)
+            else:
+                for i, n in zip(sims, eps):
+                    venv.reset(ids=[i], **reset_kwargs_for(n))
+            instrs = list(venv.call("get_language_instruction", ids=sims))
+            frames = venv.frames[sims]
+            t_sim += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            first = self._frames_to_device(frames)
+            hidden = self.model.encode_initial_image(first)             # one launch for every episode that starts now
+            inst = {"language_instruction": tokenize(instrs)}
+            task = self.model.assign_tasks(pool, sims, inst, {"image_primary": first, "patch_embeddings": hidden,
+                                                               "pad_mask_dict": {"image_primary": np.ones((len(sims), 1))}})
+            for i, n, ins in zip(sims, eps, instrs):
+                w = InferenceWrapper(self.model, **self.kw)              # what InferenceWrapper.reset leaves behind
+                w.task_description, w.base_params, w.task, w.instruction_dict = ins, pool, task, inst
+                wrappers[i], running[i] = w, n
+                instructions[n], env_index[n] = ins, i
+            t_model += time.perf_counter() - t0
+
+        start(list(range(E)))
+        while (running >= 0).any():
+            ids = np.nonzero(running >= 0)[0]
+            t0 = time.perf_counter()
+            dev = self._frames_to_device(venv.frames[ids])
+            raw, _ = self.model.sample_actions(dev, None, None, None, pool, slots=ids)
+            raw = raw.cpu().numpy() if hasattr(raw, "cpu") else np.asarray(raw)
+            actions = np.zeros((len(ids), 7), np.float64)
+            for k, i in enumerate(ids):
+                _, actions[k] = wrappers[i].postprocess(raw[k])
+            rows += len(ids)
+            t_model += time.perf_counter() - t0
+            t0 = time.perf_counter()
+            _, done, trunc, infos = venv.step(actions, ids=ids)
+            t_sim += time.perf_counter() - t0
+            ended = []
+            for k, i in enumerate(ids):
+                n = running[i]
+                steps[n] += 1
+                if success_from(done[k], infos[k]):
+                    success[n] = True
+                if success[n] or trunc[k] or steps[n] >= max_steps:
+                    running[i], wrappers[i] = -1, None
+                    ended.append(int(i))
+            if ended:
+                start(ended)
+        return {"success": success, "steps": steps, "instructions": instructions, "env_index": env_index,
+                "model_seconds": t_model, "sim_seconds": t_sim, "rows_stepped": rows}
+

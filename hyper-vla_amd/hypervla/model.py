@@ -40,7 +40,9 @@ def _torch():
 
 class GeneratedWeights:
     """Handle to one batch of generated policy weights on the device (what the reference calls
-    ``base_params``).  Immutable from the caller's side; freed on garbage collection."""
+    ``base_params``); freed on garbage collection.  What `create_tasks` returns is immutable from the caller's side.  An
+    episode pool is mutable in place: `HyperVLA.assign_tasks` regenerates slots of a handle from `create_pool` (or from
+    `create_tasks`) and leaves its other rows as they are; `batch` is then the pool's capacity."""
 
     def __init__(self, model: "HyperVLA", handle, batch: int):
         self._model, self._h, self.batch = model, handle, batch
@@ -285,8 +287,8 @@ class HyperVLA:
         return out
 
     # ------------------------------------------------------------------ the hot path
-    def create_tasks(self, goals=None, instruction_dict: Dict = None, initial_state: Dict = None):
-        """hypervla/model.py:35-83.  Returns (base_params handle, tasks dict, intermediates)."""
+    def _task_inputs(self, instruction_dict: Dict, initial_state: Dict):
+        """(language_instruction dict, B, token_embedding, attention_mask, CLS rows) on the device, shapes checked."""
         torch = _torch()
         if instruction_dict is None or initial_state is None:
             raise ValueError("the built path is language + initial-image conditioned: instruction_dict and "
@@ -304,19 +306,83 @@ class HyperVLA:
                 or tuple(cls.shape) != (B, g.enc_dim):
             raise ValueError(f"bad shapes: token_embedding {tuple(tok.shape)}, attention_mask {tuple(mask.shape)}, "
                              f"patch_embeddings[:,0] {tuple(cls.shape)} for B={B}")
+        return li, B, tok, mask, cls
+
+    def create_tasks(self, goals=None, instruction_dict: Dict = None, initial_state: Dict = None):
+        """hypervla/model.py:35-83.  Returns (base_params handle, tasks dict, intermediates)."""
+        torch = _torch()
+        li, B, tok, mask, cls = self._task_inputs(instruction_dict, initial_state)
         h = self._ctx.generate(tok.data_ptr(), mask.data_ptr(), cls.data_ptr(), B, self._stream())
         torch.cuda.current_stream(self.device).synchronize()      # inputs may be temporaries
         tasks = {"pad_mask_dict": {"language_instruction": np.ones(B, dtype=bool)},     # model.py:51-70
                  "language_instruction": li}
         return GeneratedWeights(self, h, B), tasks, {}
 
+    # ------------------------------------------------------------------ episode pool (DESIGN.md §10)
+    def create_pool(self, capacity: int) -> GeneratedWeights:
+        """An episode pool of `capacity` empty slots (`hvla_weights_alloc`): zero weights, which step to finite actions, and
+        fresh ensemble counters.  Fill slots with :meth:`assign_tasks`; step any subset with ``sample_actions(..., slots=)``."""
+        capacity = int(capacity)
+        if not 1 <= capacity <= self.max_batch:
+            raise ValueError(f"pool capacity {capacity} outside [1, max_batch={self.max_batch}]")
+        h = self._ctx.weights_alloc(capacity, self._stream())
+        return GeneratedWeights(self, h, capacity)
+
+    def _slot_map(self, slots, pool: GeneratedWeights):
+        """`slots` checked on the host (hypervla.pool.check_slots), then as a device int32 tensor."""
+        from .pool import check_slots
+        s = check_slots(slots, pool.batch)
+        if len(s) > self.max_batch:
+            raise ValueError(f"{len(s)} slots in one call: more than max_batch={self.max_batch}")
+        return s, _torch().as_tensor(s).to(self.device)
+
+    def assign_tasks(self, pool: GeneratedWeights, slots, instruction_dict: Dict = None, initial_state: Dict = None):
+        """`create_tasks` for K new episodes into slots `slots` of `pool` (`hvla_generate_slots`): the same inputs for K episodes
+        (bare `input_ids` / `attention_mask` are encoded by a loaded T5 first).  Those slots' weights, context and ensemble
+        counter are replaced -- bitwise what `create_tasks` gives the same tasks -- and every other slot is left as it was.
+        Returns the tasks dict of the K episodes."""
+        torch = _torch()
+        if not isinstance(pool, GeneratedWeights) or pool._model is not self:
+            raise TypeError("pool must be a handle of this model (create_pool / create_tasks)")
+        s, sd = self._slot_map(slots, pool)
+        li, K, tok, mask, cls = self._task_inputs(instruction_dict, initial_state)
+        if K != len(s):
+            raise ValueError(f"{K} tasks for {len(s)} slots")
+        self._ctx.generate_slots(pool._h, sd.data_ptr(), K, tok.data_ptr(), mask.data_ptr(), cls.data_ptr(), self._stream())
+        torch.cuda.current_stream(self.device).synchronize()      # inputs may be temporaries
+        return {"pad_mask_dict": {"language_instruction": np.ones(K, dtype=bool)}, "language_instruction": li}
+
+    def ensemble_actions(self, pool: GeneratedWeights, actions, stats, slots):
+        """Un-normalise + temporal ensemble per slot on the device (`hvla_ensemble_slots`): actions [K, horizon, action_dim] of
+        slots `slots` -> [K, action_dim].  `stats` = (mean, std, mask) of `interface.device_unnormalization`.  Each slot keeps its
+        own history, restarted when `assign_tasks` fills the slot.  Numpy in -> numpy out, torch in -> torch out."""
+        torch = _torch()
+        g = self.geometry
+        s, sd = self._slot_map(slots, pool)
+        as_torch = isinstance(actions, torch.Tensor)
+        act = self._dev(actions, torch.float32)
+        if tuple(act.shape) != (len(s), g.horizon, g.action_dim):
+            raise ValueError(f"actions must be [{len(s)}, {g.horizon}, {g.action_dim}], got {tuple(act.shape)}")
+        mean, std, mask = (self._dev(stats[0], torch.float32), self._dev(stats[1], torch.float32), self._dev(stats[2], torch.uint8))
+        if not mean.numel() == std.numel() == mask.numel() == g.action_dim:
+            raise ValueError(f"mean / std / mask must have {g.action_dim} entries")
+        out = torch.empty(len(s), g.action_dim, dtype=torch.float32, device=self.device)
+        self._ctx.ensemble_slots(pool._h, sd.data_ptr(), len(s), act.data_ptr(), mean.data_ptr(), std.data_ptr(), mask.data_ptr(),
+                                 out.data_ptr(), self._stream())
+        if as_torch:
+            return out
+        torch.cuda.current_stream(self.device).synchronize()
+        return out.cpu().numpy()
+
     def sample_actions(self, images, instruction_dict=None, task=None, timestep_pad_mask=None,
                        base_params: GeneratedWeights = None, train: bool = False, rng=None,
-                       image_embeddings=None, attention_maps: bool = False):
+                       image_embeddings=None, attention_maps: bool = False, slots=None):
         """hypervla/model.py:85-137.  images uint8 [B, 1, H, W, 3] (or [B, H, W, 3]) -> actions
         [B, horizon, action_dim].  `attention_maps=True` also returns the two attention slices the reference's wrapper keeps
         from the intermediates (hypervla_interface.py:208-217): DINOv2's CLS-query attention over the patches, every layer and
-        head, and the generated policy's action-token attention over the patches."""
+        head, and the generated policy's action-token attention over the patches.
+        `slots` (episode pool): step only these K slots of `base_params` (`hvla_step_slots`): images [K, ...] in, every output
+        [K, ...] out, row k that of slot slots[k]."""
         torch = _torch()
         if train:
             # train=True switches on nn.Dropout(dropout_rate) (base_vit.py:205, transformer.py:67,74,192,244) and the
@@ -338,6 +404,9 @@ class HyperVLA:
                 raise ValueError("window size must be 1 (images.squeeze(1), model.py:117)")
             img = img[:, 0].contiguous()
         B = base_params.batch
+        if slots is not None:
+            slots_host, slots_dev = self._slot_map(slots, base_params)
+            B = len(slots_host)
         if tuple(img.shape) != (B, g.image_size, g.image_size, 3):    # base_vit.py:86-89
             raise ValueError(f"Input image size must be {g.image_size}x{g.image_size}: got {tuple(img.shape)} for B={B}")
         actions = torch.empty(B, g.horizon, g.action_dim, dtype=torch.float32, device=self.device)
@@ -348,7 +417,11 @@ class HyperVLA:
             inter["head_attention"] = torch.empty(B, g.layers, g.heads, g.patches, dtype=torch.float32, device=self.device)
             self._ctx.set_attention_outputs(inter["dino_cls_attention"].data_ptr(), inter["head_attention"].data_ptr())
         try:
-            self._ctx.step(base_params._h, img.data_ptr(), actions.data_ptr(), logits.data_ptr(), B, self._stream())
+            if slots is None:
+                self._ctx.step(base_params._h, img.data_ptr(), actions.data_ptr(), logits.data_ptr(), B, self._stream())
+            else:
+                self._ctx.step_slots(base_params._h, slots_dev.data_ptr(), B, img.data_ptr(), actions.data_ptr(), logits.data_ptr(),
+                                     self._stream())
         finally:
             if attention_maps:
                 self._ctx.set_attention_outputs(0, 0)

@@ -160,6 +160,36 @@ int hvla_ensemble_reset(hvla_ctx* ctx, hvla_weights* w, void* stream);
 int hvla_ensemble(hvla_ctx* ctx, hvla_weights* w, const float* actions, const float* mean,
                   const float* std, const uint8_t* mask, float* out, void* stream);
 
+/* Episode pool: episodes join and leave a running batch (no reference counterpart: the reference runs one episode at a time;
+ * hypervla.evaluate.BatchEvaluator.run_episodes drives it).  An arena of B slots; slot s is row s of wh / wl / vf / ctx and of
+ * the ensemble ring, and has an ensemble counter of its own.  `slots` is a DEVICE int32 [K] map owned by the caller, K distinct
+ * entries in [0, B) (hypervla.pool.check_slots refuses anything else before a map reaches the device); the kernels skip an entry
+ * outside [0, B): no load, no store.  Every slot is bit-batch-invariant: a slot's weights, actions and ensemble are bitwise those
+ * of the same episode run alone through hvla_generate / hvla_step, whatever else shares the pool or the call.  Apart from
+ * hvla_weights_alloc none of these calls allocates or synchronises the host: a pooled step loop can be captured in a hipGraph.
+ * hvla_weights_free / hvla_weights_export / hvla_weights_batch take a pool like any arena.
+ *
+ * hvla_weights_alloc: an arena of B (1 <= B <= max_batch) EMPTY slots (taken from the ctx's freed arenas when one of that size
+ * is parked, else allocated): weights and context zero-filled -- stepping a slot that was never assigned is defined and gives
+ * finite actions -- and every ensemble counter zero.                                                                         */
+int hvla_weights_alloc(hvla_ctx* ctx, int32_t B, hvla_weights** out, void* stream);
+/* hvla_generate for K (1 <= K <= min(B, max_batch)) new tasks into slots[0 .. K-1] of w: inputs as hvla_generate's for K
+ * episodes.  Writes only those rows of the weights and the context and zeroes those slots' ensemble counters; the rows are
+ * bitwise what hvla_generate gives the same tasks.                                                                          */
+int hvla_generate_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* token_embedding,
+                        const int64_t* attention_mask, const float* initial_cls, void* stream);
+/* hvla_step for K frames, frame k with the weights of slot slots[k]: images u8 [K, H, W, 3] -> actions f32 [K, horizon,
+ * action_dim], gripper_logits f32 [K, horizon] (nullable).  Attention outputs (hvla_set_attention_outputs) have K rows, one per
+ * call row.  With hvla_config.streams == 2 and K >= 64 the two halves run on two streams, as hvla_step's.                    */
+int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K, const uint8_t* images,
+                    float* actions, float* gripper_logits, void* stream);
+/* hvla_ensemble per slot: actions row k (f32 [K, horizon, action_dim]) is the prediction of slot slots[k], out f32 [K, action_dim]
+ * its un-normalised ensembled action; each slot counts its own calls since hvla_generate_slots assigned it (or since
+ * hvla_weights_alloc / hvla_generate / hvla_ensemble_reset).  A slot's ring rows are those hvla_ensemble uses for that row: an
+ * arena is ensembled either through hvla_ensemble or through hvla_ensemble_slots, not both.                                  */
+int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* actions,
+                        const float* mean, const float* std, const uint8_t* mask, float* out, void* stream);
+
 /* Replaces: MixActionHead.loss evaluated per sample (vmap of sample_loss_fn) on the policy's outputs
  * (hypervla/components/action_heads.py:474-522, scripts/train.py:326-346): the forward half of the
  * fine-tune step.  actions / logits as written by hvla_policy / hvla_step; target f32 [B, horizon,
