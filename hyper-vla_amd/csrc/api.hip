@@ -46,6 +46,12 @@ struct hvla_weights {
   DevBuf slot_count;             // int32 [B]: the episode pool's per-row ensemble counters (hvla_ensemble_slots)
 };
 
+struct hvla_post {               // per-slot post-processing state (hvla_post_*, postprocess.hip)
+  int B = 0, H = 0;
+  DevBuf ring;                   // f64 [B][H][H][HVLA_POST_DIM]
+  DevBuf state;                  // PostSlot [B]
+};
+
 struct hvla_ctx {
   hvla_config cfg{};
   Geom g{};
@@ -738,6 +744,58 @@ int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, in
   ++ctx->prof.nlaunch;
   HIPCHK(ctx, launch_ensemble_slots(actions, w->ring.as<float>(), w->slot_count.as<int>(), slots, K, mean, std, mask, out, w->B,
                                     ctx->g.horizon, ctx->g.action_dim, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+// ------------------------------------------------------------------ post-processing of pool slots (include/hvla.h)
+int hvla_post_create(hvla_ctx* ctx, int32_t B, hvla_post** out, void* stream) {
+  if (!ctx || !out) return HVLA_E_STATE;
+  *out = nullptr;
+  const Geom& g = ctx->g;
+  if (g.action_dim != HVLA_POST_DIM) FAIL(ctx, HVLA_E_SHAPE, "post-processing needs action_dim %d, the ctx has %d", HVLA_POST_DIM, g.action_dim);
+  if (g.horizon < 1 || g.horizon > POST_MAX_HORIZON) FAIL(ctx, HVLA_E_SHAPE, "horizon %d outside [1, %d]", g.horizon, POST_MAX_HORIZON);
+  if (B < 1 || B > ctx->cfg.max_batch) FAIL(ctx, HVLA_E_SHAPE, "%d post-processing slots outside [1, %d]", B, ctx->cfg.max_batch);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  std::unique_ptr<hvla_post> p(new hvla_post);
+  p->B = B;
+  p->H = g.horizon;
+  HIPCHK(ctx, p->ring.alloc((size_t)B * g.horizon * g.horizon * HVLA_POST_DIM * sizeof(double)));
+  HIPCHK(ctx, p->state.alloc((size_t)B * sizeof(PostSlot)));
+  HIPCHK(ctx, hipMemsetAsync(p->ring.p, 0, p->ring.bytes, st));
+  HIPCHK(ctx, hipMemsetAsync(p->state.p, 0, p->state.bytes, st));
+  *out = p.release();
+  return HVLA_OK;
+}
+
+int hvla_post_free(hvla_ctx* ctx, hvla_post* p) {
+  if (!p) return HVLA_OK;
+  if (ctx) (void)hipSetDevice(ctx->device);
+  delete p;                                                  // hipFree waits for the device
+  return HVLA_OK;
+}
+
+int hvla_post_assign(hvla_ctx* ctx, hvla_post* p, const int32_t* slots, int32_t K, const int32_t* rows, const uint8_t* ensemble,
+                     void* stream) {
+  if (!ctx || !p) return HVLA_E_STATE;
+  if (!slots || !rows || !ensemble) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  if (K < 1 || K > p->B) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d]", K, p->B);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_post_assign(p->state.as<PostSlot>(), slots, K, p->B, rows, ensemble, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+int hvla_post_step(hvla_ctx* ctx, hvla_post* p, const int32_t* slots, int32_t K, const float* actions, const hvla_post_row* table,
+                   int32_t n_rows, double* raw_out, double* env_out, void* stream) {
+  if (!ctx || !p) return HVLA_E_STATE;
+  if (!slots || !actions || !table || !env_out) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  if (K < 1 || K > p->B) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d]", K, p->B);
+  if (n_rows < 1) FAIL(ctx, HVLA_E_SHAPE, "empty post-processing table");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_post_step(actions, slots, K, p->B, p->H, p->ring.as<double>(), p->state.as<PostSlot>(), table, n_rows, raw_out,
+                               env_out, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;
 }
 

@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "../../include/hvla.h"
 #include "layout.h"
 
 namespace hvla {
@@ -152,6 +153,22 @@ hipError_t launch_ensemble(const float* actions, float* ring, int* count, const 
 hipError_t launch_ensemble_slots(const float* actions, float* ring, int* count, const int32_t* slots, int K, const float* mean,
                                  const float* std, const uint8_t* mask, float* out, int B, int horizon, int action_dim,
                                  hipStream_t st);
+
+// episode pool post-processing (postprocess.hip, include/hvla.h hvla_post_*): the caller-side state of one slot's episode
+// (InferenceWrapper's ensemble counter and gripper fields), next to a ring of its last `horizon` un-normalised predictions
+constexpr int POST_MAX_HORIZON = 16;          // the ensemble weights 1 / n come from a table of this many entries
+constexpr int POST_STICKY_REPEATS = 15;       // google_robot's sticky_gripper_num_repeat (hypervla_interface.py:49-53)
+struct PostSlot {
+  double prev_grip;                           // previous_gripper_action (valid when has_prev)
+  double sticky_value;                        // sticky_gripper_action
+  int32_t calls;                              // postprocess calls since the slot was assigned
+  int32_t row;                                // row of the caller's hvla_post_row table
+  int32_t ensemble, has_prev, sticky_on, repeat;
+};
+hipError_t launch_post_assign(PostSlot* state, const int32_t* slots, int K, int B, const int32_t* rows, const uint8_t* ensemble,
+                              hipStream_t st);
+hipError_t launch_post_step(const float* actions, const int32_t* slots, int K, int B, int H, double* ring, PostSlot* state,
+                            const hvla_post_row* table, int n_rows, double* raw_out, double* env_out, hipStream_t st);
 
 hipError_t launch_loss(const float* actions, const float* logits, const float* target, const uint8_t* tmask,
                        const uint8_t* amask, float* loss, int B, int horizon, int action_dim, float max_action,

@@ -24,7 +24,10 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_t5_encode", "hvla_preprocess", "hvla_encode_audit", "hvla_train_accumulate", "hvla_train_bucket_ranges",
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
-           "hvla_step_slots", "hvla_ensemble_slots"]
+           "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step"]
+HVLA_POST_DIM = 7
+HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
+HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
 PROF_NAMES = ["patch_embed", "layernorm", "qkv_gemm", "attention", "out_gemm", "fc1_gemm", "fc2_gemm", "policy",
               "small_row_gemms"]      # mean rows + the 2 B latency-bound rows per GEMM: CLS rows and weight-rounding compensation rows
 
@@ -57,6 +60,12 @@ class hvla_train_hyper(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("lr", "b1", "b2", "eps", "weight_decay", "clip", "ema_decay")] + \
                [("step", C.c_int32), ("forward_only", C.c_int32), ("base_lr", C.c_float),
                 ("base_weight_decay", C.c_float), ("train_encoder", C.c_int32)]
+
+
+class hvla_post_row(C.Structure):
+    """One row of hvla_post_step's caller-owned table (include/hvla.h)."""
+    _fields_ = [("normalization", C.c_int32), ("setup", C.c_int32), ("p0", C.c_double * HVLA_POST_DIM),
+                ("p1", C.c_double * HVLA_POST_DIM), ("mask", C.c_uint8 * HVLA_POST_DIM)]
 
 
 _lib = None
@@ -155,6 +164,14 @@ def load_library():
     lib.hvla_step_slots.restype = C.c_int
     lib.hvla_ensemble_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.hvla_ensemble_slots.restype = C.c_int
+    lib.hvla_post_create.argtypes = [vp, i32, C.POINTER(vp), vp]
+    lib.hvla_post_create.restype = C.c_int
+    lib.hvla_post_free.argtypes = [vp, vp]
+    lib.hvla_post_free.restype = C.c_int
+    lib.hvla_post_assign.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.hvla_post_assign.restype = C.c_int
+    lib.hvla_post_step.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.hvla_post_step.restype = C.c_int
     lib.hvla_selftest.argtypes = [vp, vp]
     lib.hvla_selftest.restype = C.c_int
     _lib = lib
@@ -366,3 +383,20 @@ class Context:
     def ensemble_slots(self, w, slots_ptr, K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr, stream=0):
         self._check(self.lib.hvla_ensemble_slots(self.h, w, C.c_void_p(slots_ptr), K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr,
                                                  C.c_void_p(stream)), "hvla_ensemble_slots")
+
+    # post-processing of pool slots (include/hvla.h hvla_post_*; hypervla.postprocess drives these)
+    def post_create(self, B, stream=0):
+        p = C.c_void_p()
+        self._check(self.lib.hvla_post_create(self.h, B, C.byref(p), C.c_void_p(stream)), "hvla_post_create")
+        return p
+
+    def post_free(self, p):
+        self.lib.hvla_post_free(self.h, p)
+
+    def post_assign(self, p, slots_ptr, K, rows_ptr, ensemble_ptr, stream=0):
+        self._check(self.lib.hvla_post_assign(self.h, p, C.c_void_p(slots_ptr), K, C.c_void_p(rows_ptr), C.c_void_p(ensemble_ptr),
+                                              C.c_void_p(stream)), "hvla_post_assign")
+
+    def post_step(self, p, slots_ptr, K, act_ptr, table_ptr, n_rows, raw_ptr, env_ptr, stream=0):
+        self._check(self.lib.hvla_post_step(self.h, p, C.c_void_p(slots_ptr), K, C.c_void_p(act_ptr), C.c_void_p(table_ptr), n_rows,
+                                            C.c_void_p(raw_ptr or None), C.c_void_p(env_ptr), C.c_void_p(stream)), "hvla_post_step")

@@ -8,7 +8,8 @@ next to them (data/utils/venv.py:183-297 `ShArray` / `_worker`, :357-520 `Subpro
 processes and write their camera frames into ONE shared `uint8 [E, H, W, 3]` block; each timestep that block goes to
 the device once, is resized there (`hvla_preprocess`), and all E episodes take one `sample_actions` step with their own
 generated weights; the per-episode caller logic (un-normalisation, temporal ensemble, euler -> axis-angle, gripper
-rules) is the `InferenceWrapper`'s.  No simulator is part of this package: anything with `reset()` / `step(action)` /
+rules) is the `InferenceWrapper`'s, run on the host per episode (`postprocess="host"`) or for all of them in one launch
+(`postprocess="device"`, hypervla.postprocess).  No simulator is part of this package: anything with `reset()` / `step(action)` /
 `get_language_instruction()` works (`EnvLike`), and the tests use a toy one.
 """
 from __future__ import annotations
@@ -16,7 +17,7 @@ from __future__ import annotations
 import multiprocessing as mp
 import time
 from multiprocessing import shared_memory
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -208,15 +209,42 @@ class ShmemVectorEnv:
 
 class BatchEvaluator:
     """E episodes in lockstep.  Per episode it keeps an `InferenceWrapper` for the caller-side state (ensemble history,
-    sticky gripper, ...), but the model is stepped ONCE per timestep for all of them."""
+    sticky gripper, ...), but the model is stepped ONCE per timestep for all of them.
 
-    def __init__(self, model, policy_setup: str = "libero", pred_action_horizon: int = 4, action_ensemble: bool = True,
-                 crop: bool = False, image_size: Optional[int] = None, padded_resize: bool = False):
+    `postprocess="device"` keeps that caller-side state on the device instead (one `DevicePostprocessor` of capacity E, slot i =
+    simulator i) and post-processes all running episodes in one launch; the simulators receive the same actions (translation and
+    gripper exact, rotation within 1 f32 ulp).  Only then may `policy_setup` be a sequence of E setups, one per simulator."""
+
+    def __init__(self, model, policy_setup: Union[str, Sequence[str]] = "libero", pred_action_horizon: int = 4,
+                 action_ensemble: bool = True, crop: bool = False, image_size: Optional[int] = None, padded_resize: bool = False,
+                 postprocess: str = "host"):
+        if postprocess not in ("host", "device"):
+            raise ValueError(f"postprocess must be 'host' or 'device', got {postprocess!r}")
+        per_sim = not isinstance(policy_setup, str)
+        if per_sim and postprocess != "device":
+            raise ValueError("one policy setup per simulator needs postprocess='device'")
+        if postprocess == "device":
+            from .postprocess import SETUP_CODES
+            for p in ([policy_setup] if not per_sim else list(policy_setup)):
+                if p not in SETUP_CODES:
+                    raise ValueError(f"Unknown policy setup: {p}")
+            if pred_action_horizon != model.geometry.horizon:     # InferenceWrapper.postprocess asserts the same
+                raise ValueError(f"pred_action_horizon {pred_action_horizon} != the model's horizon {model.geometry.horizon}")
         self.model = model
+        self.postprocess = postprocess
+        self.setups = list(policy_setup) if per_sim else policy_setup
         self.kw = dict(policy_setup=policy_setup, horizon=1, pred_action_horizon=pred_action_horizon,
                        image_size=image_size or model.geometry.image_size, action_ensemble=action_ensemble, crop=crop,
                        padded_resize=padded_resize)
         self.crop, self.padded_resize = crop, padded_resize
+
+    def _device_post(self, E: int):
+        """(DevicePostprocessor of capacity E, the setup of each simulator) for postprocess='device'."""
+        from .postprocess import DevicePostprocessor
+        setups = [self.setups] * E if isinstance(self.setups, str) else self.setups
+        if len(setups) != E:
+            raise ValueError(f"{len(setups)} policy setups for {E} simulators")
+        return DevicePostprocessor(self.model, E), setups
 
     def _frames_to_device(self, frames: np.ndarray):
         import torch
@@ -240,7 +268,13 @@ class BatchEvaluator:
         if instructions is None:
             instructions = venv.call("get_language_instruction")
         t_sim += time.perf_counter() - t0
-        wrappers = [InferenceWrapper(self.model, **self.kw) for _ in range(E)]
+        device_post = self.postprocess == "device"
+        if device_post:
+            import torch
+            post, setups = self._device_post(E)
+            wrappers = []
+        else:
+            wrappers = [InferenceWrapper(self.model, **self.kw) for _ in range(E)]
         t0 = time.perf_counter()
         first = self._frames_to_device(venv.frames)
         hidden = self.model.encode_initial_image(first)                      # evaluate.py:264-274, all episodes at once
@@ -250,6 +284,8 @@ class BatchEvaluator:
                                                   "pad_mask_dict": {"image_primary": np.ones((E, 1))}})
         for w, ins in zip(wrappers, instructions):                           # what InferenceWrapper.reset leaves behind
             w.task_description, w.base_params, w.task, w.instruction_dict = ins, weights, task, inst
+        if device_post:
+            post.assign(range(E), setups, self.kw["action_ensemble"])
         t_model += time.perf_counter() - t0
         active = np.ones(E, bool)
         success = np.zeros(E, bool)
@@ -262,9 +298,14 @@ class BatchEvaluator:
             t0 = time.perf_counter()
             dev = self._frames_to_device(venv.frames)                        # finished episodes keep their last frame
             raw, _ = self.model.sample_actions(dev, inst, task, None, weights)
+            if device_post:
+                ids = np.nonzero(active)[0]
+                _, env = post.step(raw[torch.as_tensor(ids, device=raw.device)], ids)   # raw: the device tensor
+                actions[ids] = env.cpu().numpy()
             raw = raw.cpu().numpy() if hasattr(raw, "cpu") else np.asarray(raw)
-            for i in np.nonzero(active)[0]:
-                _, actions[i] = wrappers[i].postprocess(raw[i])
+            if not device_post:
+                for i in np.nonzero(active)[0]:
+                    _, actions[i] = wrappers[i].postprocess(raw[i])
             raw_log.append(raw)
             t_model += time.perf_counter() - t0
             t0 = time.perf_counter()
@@ -302,8 +343,11 @@ class BatchEvaluator:
         wrappers: List[Optional[InferenceWrapper]] = [None] * E
         t_sim = t_model = 0.0
         rows = 0
+        device_post = self.postprocess == "device"
         t0 = time.perf_counter()
         pool = self.model.create_pool(E)
+        if device_post:
+            post, setups = self._device_post(E)
         t_model += time.perf_counter() - t0
         nxt = 0
 
@@ -329,10 +373,14 @@ class BatchEvaluator:
             inst = {"language_instruction": tokenize(instrs)}
             task = self.model.assign_tasks(pool, sims, inst, {"image_primary": first, "patch_embeddings": hidden,
                                                                "pad_mask_dict": {"image_primary": np.ones((len(sims), 1))}})
+            if device_post:                                              # those slots restart their post-processing state
+                post.assign(sims, [setups[i] for i in sims], self.kw["action_ensemble"])
             for i, n, ins in zip(sims, eps, instrs):
-                w = InferenceWrapper(self.model, **self.kw)              # what InferenceWrapper.reset leaves behind
-                w.task_description, w.base_params, w.task, w.instruction_dict = ins, pool, task, inst
-                wrappers[i], running[i] = w, n
+                if not device_post:
+                    w = InferenceWrapper(self.model, **self.kw)          # what InferenceWrapper.reset leaves behind
+                    w.task_description, w.base_params, w.task, w.instruction_dict = ins, pool, task, inst
+                    wrappers[i] = w
+                running[i] = n
                 instructions[n], env_index[n] = ins, i
             t_model += time.perf_counter() - t0
 
@@ -342,10 +390,13 @@ class BatchEvaluator:
             t0 = time.perf_counter()
             dev = self._frames_to_device(venv.frames[ids])
             raw, _ = self.model.sample_actions(dev, None, None, None, pool, slots=ids)
-            raw = raw.cpu().numpy() if hasattr(raw, "cpu") else np.asarray(raw)
-            actions = np.zeros((len(ids), 7), np.float64)
-            for k, i in enumerate(ids):
-                _, actions[k] = wrappers[i].postprocess(raw[k])
+            if device_post:
+                actions = post.step(raw, ids)[1].cpu().numpy()
+            else:
+                raw = raw.cpu().numpy() if hasattr(raw, "cpu") else np.asarray(raw)
+                actions = np.zeros((len(ids), 7), np.float64)
+                for k, i in enumerate(ids):
+                    _, actions[k] = wrappers[i].postprocess(raw[k])
             rows += len(ids)
             t_model += time.perf_counter() - t0
             t0 = time.perf_counter()

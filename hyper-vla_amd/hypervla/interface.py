@@ -78,6 +78,24 @@ class ActionEnsembler:
 _DATASET = {"google_robot": "fractal20220817_data", "widowx_bridge": "bridge_dataset", "libero": "libero"}
 
 
+def action_statistics(model, policy_setup: str):
+    """(action statistics, normalization type) the episodes of `policy_setup` un-normalise with (hypervla_interface.py:50-86):
+    the dataset's ``dataset_statistics[...]["action"]`` (or the top-level ``"action"`` entry of a single-dataset checkpoint) and its
+    ``action_proprio_normalization_type`` from ``dataset_kwargs`` / ``dataset_kwargs_list``."""
+    if policy_setup not in _DATASET:
+        raise ValueError(f"Unknown policy setup: {policy_setup}")
+    dataset = _DATASET[policy_setup]
+    stats = model.dataset_statistics
+    action = stats["action"] if "action" in stats else stats[dataset]["action"]
+    dk = model.config["dataset_kwargs"]
+    if "dataset_kwargs" in dk:
+        normalization_type = dk["dataset_kwargs"]["action_proprio_normalization_type"]
+    else:
+        normalization_type = next(d["action_proprio_normalization_type"]
+                                  for d in dk["dataset_kwargs_list"] if d["name"] == dataset)
+    return action, normalization_type
+
+
 class InferenceWrapper:
     def __init__(self, model=None, policy_setup: str = "libero", horizon: int = 1, pred_action_horizon: int = 1,
                  exec_horizon: int = 1, image_size: int = 256, init_rng: int = 0, action_ensemble: bool = False,
@@ -91,15 +109,7 @@ class InferenceWrapper:
         self.pred_action_horizon, self.exec_horizon = pred_action_horizon, exec_horizon
         self.action_ensemble, self.crop, self.padded_resize = action_ensemble, crop, padded_resize
         self.sticky_gripper_num_repeat = {"google_robot": 15, "widowx_bridge": 1}.get(policy_setup, 0)
-        dataset = _DATASET[policy_setup]
-        stats = model.dataset_statistics
-        self.unnormalization_statistics = stats["action"] if "action" in stats else stats[dataset]["action"]
-        dk = model.config["dataset_kwargs"]
-        if "dataset_kwargs" in dk:
-            self.normalization_type = dk["dataset_kwargs"]["action_proprio_normalization_type"]
-        else:
-            self.normalization_type = next(d["action_proprio_normalization_type"]
-                                           for d in dk["dataset_kwargs_list"] if d["name"] == dataset)
+        self.unnormalization_statistics, self.normalization_type = action_statistics(model, policy_setup)
         self.action_ensembler = ActionEnsembler(pred_action_horizon, 0.0) if action_ensemble else None
         self.image_history = deque(maxlen=horizon)
         self.task = self.task_description = self.base_params = self.instruction_dict = None

@@ -190,6 +190,50 @@ int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, 
 int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* actions,
                         const float* mean, const float* std, const uint8_t* mask, float* out, void* stream);
 
+/* Episode pool post-processing: replaces InferenceWrapper.postprocess (data/utils/hypervla_interface.py:219-304: un-normalisation
+ * :219-242, temporal ensemble :250-253 == data/utils/action_ensemble.py:15-27 with temperature 0, euler -> axis-angle :261-267,
+ * gripper rules :269-299) for every running episode of a pool at once; hypervla.postprocess.DevicePostprocessor drives it and
+ * hypervla.evaluate.BatchEvaluator(postprocess="device") steps its simulators with the result.  A hvla_post holds B slots of
+ * caller-side state next to (not inside) an arena: a ring of the last `horizon` un-normalised predictions (f64 [B][horizon]
+ * [horizon][7]), a call counter, a table row, an ensemble flag and the sticky-gripper state.  Slot maps follow the episode pool's
+ * rules (distinct entries; entries outside [0, B) are skipped).  Only hvla_post_create allocates and only hvla_post_free waits for
+ * the device: a pooled loop of hvla_preprocess -> hvla_step_slots -> hvla_post_step can be captured in a hipGraph.
+ *
+ * The caller owns the table: one hvla_post_row per (policy setup, dataset statistics) pair, in device memory.
+ *   HVLA_NORM_NORMAL: p0 = mean, p1 = std;          value = where(mask, a * std + mean, a)
+ *   HVLA_NORM_BOUNDS: p0 = p01,  p1 = p99 - p01 + 1e-8 evaluated as the host evaluates it (in the statistics' own dtype);
+ *                                                   value = where(mask, (a + 1) * p1 / 2 + p01, a)
+ * Arithmetic: f64 in the host's operation order and without contraction, so raw_action and the env action's translation are
+ * bitwise numpy's; the rotation (cos / sin / atan2 of the device library) is within 1 ulp after its f32 rounding; the gripper is
+ * exact.  A row with a normalisation or setup code not listed here gives NaN outputs and leaves its slot's state alone.          */
+#define HVLA_POST_DIM 7             /* action width of every policy setup: xyz, roll pitch yaw, gripper                         */
+#define HVLA_NORM_NORMAL 0
+#define HVLA_NORM_BOUNDS 1
+#define HVLA_SETUP_LIBERO 0         /* gripper 2 g - 1                                                                           */
+#define HVLA_SETUP_WIDOWX_BRIDGE 1  /* gripper 2 (g > 0.5) - 1                                                                   */
+#define HVLA_SETUP_GOOGLE_ROBOT 2   /* relative gripper action held for 15 calls once |previous - g| > 0.5 (sticky gripper)      */
+typedef struct hvla_post hvla_post;
+typedef struct hvla_post_row {
+  int32_t normalization;            /* HVLA_NORM_*                                                                               */
+  int32_t setup;                    /* HVLA_SETUP_*                                                                              */
+  double p0[HVLA_POST_DIM], p1[HVLA_POST_DIM];
+  uint8_t mask[HVLA_POST_DIM];      /* 1: un-normalise this column                                                              */
+} hvla_post_row;
+/* B (1 <= B <= max_batch) slots, zeroed: a slot that was never assigned steps with table row 0 and no ensemble.  HVLA_E_SHAPE when
+ * the ctx's action_dim is not 7 or its horizon exceeds 16.                                                                     */
+int hvla_post_create(hvla_ctx* ctx, int32_t B, hvla_post** out, void* stream);
+int hvla_post_free(hvla_ctx* ctx, hvla_post* p);
+/* InferenceWrapper.reset (:140-160) of slots[0 .. K-1]: slot slots[k] starts a fresh episode with table row rows[k] and the
+ * temporal ensemble on iff ensemble[k] != 0.  rows i32 [K], ensemble u8 [K]: device.  Other slots keep their state.            */
+int hvla_post_assign(hvla_ctx* ctx, hvla_post* p, const int32_t* slots, int32_t K, const int32_t* rows, const uint8_t* ensemble,
+                     void* stream);
+/* One postprocess call for each of K slots: actions f32 [K, horizon, 7] (row k the prediction of slot slots[k], as written by
+ * hvla_step_slots); table: n_rows hvla_post_row (device); raw_out f64 [K, 7] (nullable) = raw_action; env_out f64 [K, 7] = the env
+ * action: translation f64, rotation and gripper f32 values.  A slot whose row is outside [0, n_rows) is skipped.  Slots left out
+ * of the map keep their state.                                                                                                  */
+int hvla_post_step(hvla_ctx* ctx, hvla_post* p, const int32_t* slots, int32_t K, const float* actions, const hvla_post_row* table,
+                   int32_t n_rows, double* raw_out, double* env_out, void* stream);
+
 /* Replaces: MixActionHead.loss evaluated per sample (vmap of sample_loss_fn) on the policy's outputs
  * (hypervla/components/action_heads.py:474-522, scripts/train.py:326-346): the forward half of the
  * fine-tune step.  actions / logits as written by hvla_policy / hvla_step; target f32 [B, horizon,
