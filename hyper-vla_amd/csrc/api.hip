@@ -121,10 +121,15 @@ extern "C" {
 
 const char* hvla_last_error(const hvla_ctx* ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
 
-int hvla_create(const hvla_config* c, int device, hvla_ctx** out) {
+int hvla_create(const hvla_config* c, int device, hvla_ctx** out) { return hvla_create_with(c, nullptr, device, out); }
+
+int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int device, hvla_ctx** out) {
   if (!c || !out) return HVLA_E_SHAPE;
   *out = nullptr;
   if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
+  if (opts && opts->struct_size != sizeof(hvla_policy_options)) return HVLA_E_SHAPE;   // the same rule for the options
+  const int lang = opts ? opts->use_language_token : 0;
+  if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return HVLA_E_DEVICE;
   hipDeviceProp_t prop;
@@ -137,7 +142,7 @@ int hvla_create(const hvla_config* c, int device, hvla_ctx** out) {
   g = Geom{c->image_size, c->patch, c->enc_dim, c->enc_layers, c->enc_heads, c->enc_mlp,
            c->dim, c->layers, c->heads, c->mlp, c->horizon, c->action_dim, c->tanh_scale, c->max_action,
            c->ctx_dim, c->ctx_layers, c->ctx_heads, c->ctx_mlp, c->lang_tokens, c->lang_dim, c->scale_context,
-           c->clip_target != 0};
+           c->clip_target != 0, lang};
   // what the hand-written kernels are specialised for (anything else is refused, never emulated)
   const int P = g.P();
   const bool ok = c->dim == 64 && c->heads == 4 && c->mlp % 32 == 0 && c->mlp >= 32 && c->enc_dim % 128 == 0 &&
@@ -149,6 +154,9 @@ int hvla_create(const hvla_config* c, int device, hvla_ctx** out) {
                   c->horizon * (c->action_dim - 1) + c->horizon <= 32 && c->max_batch >= 1 &&
                   (c->enc_dtype == HVLA_ENC_F16 || c->enc_dtype == HVLA_ENC_BF16);
   if (!ok) return c->enc_dtype != HVLA_ENC_F16 && c->enc_dtype != HVLA_ENC_BF16 ? HVLA_E_DTYPE : HVLA_E_SHAPE;
+  // use_language_token: the language prefix is one 32-key tile of the policy kernel, its projection runs in k-steps of 64
+  if (lang && (c->lang_tokens > 32 || c->lang_dim % 64 != 0)) return HVLA_E_SHAPE;
+  if (lang && c->dim / 16 * 512 != 4 * 512) return HVLA_E_SHAPE;    // policy_body.inc finds the prefix at m_head + 4 fragments
   // the context encoder keeps its token block, q / k / v and the MLP hidden rows in LDS: a geometry that does not fit is
   // refused here, not at the first hvla_generate
   if (ctx_encoder_lds_bytes(c->lang_tokens, c->ctx_dim, c->ctx_mlp, c->enc_dim) > 160 * 1024) return HVLA_E_SHAPE;
@@ -441,6 +449,19 @@ static int take_arena(hvla_ctx* ctx, int32_t B, std::unique_ptr<hvla_weights>& w
   return HVLA_OK;
 }
 
+// use_language_token: K episodes' language tokens (tok [K, T, lang_dim]) through the policy once, into the language prefix of their
+// arena rows (slots[k], or k) (lang_prefix_kernel); nothing to do without the option
+static int lang_prefix(hvla_ctx* ctx, hvla_weights* w, const float* tok, int K, const int32_t* slots, hipStream_t st) {
+  const LangLayout& ll = ctx->lay.ll;
+  if (!ll.on) return HVLA_OK;
+  const Geom& g = ctx->g;
+  LangPrefixParams lp{ctx->lay.pl, ll.m_lproj, ll.m_lkv, ll.v_lproj_b, ll.v_lpos, w->wh.as<__bf16>(), w->wl.as<__bf16>(),
+                      w->vf.as<float>(), tok, slots, w->B, g.T, g.lang_dim, g.L, g.M};
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_lang_prefix(lp, K, st));
+  return HVLA_OK;
+}
+
 int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const float* cls, int32_t B,
                   hvla_weights** out, void* stream) {
   if (!ctx || !out) return HVLA_E_STATE;
@@ -464,6 +485,7 @@ int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const fl
                      ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
                      w->vf.as<float>(), B, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
   HIPCHK(ctx, launch_weightgen(wp, g.C, st));
+  if (int r = lang_prefix(ctx, w.get(), tok, B, nullptr, st)) return r;
   *out = w.release();
   return HVLA_OK;
 }
@@ -589,13 +611,15 @@ static int policy_range(hvla_ctx* ctx, const hvla_weights* w, const float* token
                  w->vf.as<float>() + wb * pl.Gv, tokens + (size_t)b0 * g.P() * g.E,
                  actions + (size_t)b0 * g.horizon * g.action_dim, logits ? logits + (size_t)b0 * g.horizon : nullptr,
                  nb, g.E, g.P(), g.L, g.M, g.horizon, g.action_dim, g.tanh_scale, g.max_action};
-  if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * g.P();
+  const LangLayout& ll = ctx->lay.ll;
+  const int lang_T = ll.on ? g.T : 0;                           // use_language_token: the head map has lang_T + P keys
+  if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * (g.P() + lang_T);
   ctx->prof.begin(HVLA_PROF_POLICY, st);
   ++ctx->prof.nlaunch;
   if (slots)
-    HIPCHK(ctx, launch_policy_slots(p, slots + b0, w->B, st));
+    HIPCHK(ctx, launch_policy_slots(p, slots + b0, w->B, st, lang_T));
   else
-    HIPCHK(ctx, launch_policy(p, st));
+    HIPCHK(ctx, launch_policy(p, st, lang_T));
   ctx->prof.end(HVLA_PROF_POLICY, st);
   return HVLA_OK;
 }
@@ -707,7 +731,7 @@ int hvla_generate_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, in
                      w->vf.as<float>(), K, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
   HIPCHK(ctx, launch_weightgen_slots(wp, g.C, slots, w->B, st));
   HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.C, w->B, st));
-  return HVLA_OK;
+  return lang_prefix(ctx, w, tok, K, slots, st);
 }
 
 int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K, const uint8_t* images, float* actions,
@@ -813,6 +837,7 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* logits, const fl
 int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[4]) {
   if (!ctx || !out) return HVLA_E_STATE;
   if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
   const TrainLayout L = make_train_layout(ctx->g);
   out[0] = L.total + (train_encoder ? L.enc_total : 0); out[1] = L.G;
@@ -839,6 +864,7 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
     FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   if ((tokens != nullptr) == (images != nullptr)) FAIL(ctx, HVLA_E_SHAPE, "pass exactly one of tokens (frozen encoder) / images (trained encoder)");
   if ((images != nullptr) != (hy->train_encoder != 0)) FAIL(ctx, HVLA_E_STATE, "hyper.train_encoder does not match the inputs");
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const TrainLayout L = make_train_layout(ctx->g);
@@ -859,6 +885,7 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
 
 int hvla_train_bucket_ranges(hvla_ctx* ctx, int32_t train_encoder, int64_t out[6]) {
   if (!ctx || !out) return HVLA_E_STATE;
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
   out[0] = L.total; out[1] = train_encoder ? L.enc_total : 0;     // the shared DINOv2 leaves
   out[2] = L.wcat; out[3] = L.total - L.wcat;                     // the output heads (W_cat, b_cat)
@@ -897,6 +924,7 @@ int hvla_train_apply(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_tr
   if (!ctx || !buf || !hy) return HVLA_E_STATE;
   if (!buf->params || !buf->grads || !buf->mu || !buf->nu || !buf->sqsum) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
   HIPCHK(ctx, train_apply(L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;
@@ -907,6 +935,7 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
   if (!ctx || !buf || !hy) return HVLA_E_STATE;
   if (!buf->grads || !buf->sqsum || !acc) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
   HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;

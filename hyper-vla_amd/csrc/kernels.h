@@ -139,10 +139,24 @@ struct PolicyParams {
   unsigned long long* stamps = nullptr;   // libhvla_bench.so: shader-clock time stamps of episode 0 / wave 0 at the phase boundaries
 #endif
 };
-hipError_t launch_policy(const PolicyParams& p, hipStream_t st);
+// lang_T > 0: use_language_token (policy_kernel_lang): the arena rows hold the language prefix lang_prefix_kernel
+// wrote (LangLayout::m_lkv), lang_T is the number of language tokens; p.amap is then [B, L, heads, lang_T + P]
+hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0);
 // episode pool: workgroup b takes its weights from arena row slots[b] (p.wh / wl / vf point at row 0 of an arena of `rows`
 // episodes); tokens, actions, logits and attention rows stay call rows.  Entries outside [0, rows) are skipped.
-hipError_t launch_policy_slots(const PolicyParams& p, const int32_t* slots, int rows, hipStream_t st);
+hipError_t launch_policy_slots(const PolicyParams& p, const int32_t* slots, int rows, hipStream_t st, int lang_T = 0);
+// use_language_token: the language tokens of K episodes through the policy once (lang_prefix_kernel): K / V of every layer into
+// the episodes' arena rows (LangLayout::m_lkv)
+struct LangPrefixParams {
+  PolicyLayout pl;
+  int m_lproj, m_lkv, v_lproj_b, v_lpos;   // LangLayout
+  __bf16 *wh, *wl;                   // arena row 0 [rows, Gm]
+  const float* vf;                   // [rows, Gv]
+  const float* tok;                  // [K, T, lang_dim] (hvla_generate's token_embedding)
+  const int32_t* slots;              // [K] arena row of episode k, or null: row k
+  int rows, T, lang_dim, L, M;
+};
+hipError_t launch_lang_prefix(const LangPrefixParams& p, int K, hipStream_t st);
 
 // ---------------------------------------------------------------- caller-side device helpers
 hipError_t launch_ensemble(const float* actions, float* ring, int* count, const float* mean,

@@ -29,11 +29,13 @@ struct Geom {
   float tanh_scale, max_action;
   int C, ctx_layers, ctx_heads, ctx_mlp, T, lang_dim, scale_context;
   int clip_target = 1;       // MixActionHead.loss: clip the action target to +-max_action (action_heads.py:499-500)
+  int lang_in_policy = 0;    // vit_kwargs.use_language_token (base_vit.py:159-166,207-212): [T language | P patches | 1 action]
   int grid() const { return image_size / patch; }
   int P() const { return grid() * grid(); }
   int S() const { return P() + 1; }
   int hd() const { return D / H; }
   int A() const { return horizon * (action_dim - 1); }
+  int pos_rows() const { return S() + (lang_in_policy ? T : 0); }   // rows of the policy's pos_embedding
 };
 
 // one generated leaf in reference (jax pytree) order
@@ -82,7 +84,11 @@ inline std::vector<LeafInfo> generated_leaves(const Geom& g) {
   }
   add("encoder_image_embedding_projection_bias", {D});
   add("encoder_image_embedding_projection_kernel", {g.E, D});
-  add("encoder_pos_embedding", {1, g.S(), D});
+  if (g.lang_in_policy) {
+    add("encoder_language_token_projection_bias", {D});
+    add("encoder_language_token_projection_kernel", {g.lang_dim, D});
+  }
+  add("encoder_pos_embedding", {1, g.pos_rows(), D});
   return v;
 }
 
@@ -113,8 +119,25 @@ inline int kphi(int ks, int half, int j) {
 // pair of k-steps:  32 * (ks >> 1) + 16 * h + 8 * (ks & 1) + j
 inline int kproj(int ks, int half, int j) { return 32 * (ks >> 1) + 16 * half + 8 * (ks & 1) + j; }
 
+// use_language_token: where the language leaves sit.  Kept out of PolicyLayout, which policy_kernel takes by value:
+// with the flag off the arena and every kernel argument are those of the model without it.
+//   m_lkv     the episode's language K / V prefix, written by lang_prefix_kernel once per episode, read by policy_kernel_lang
+//             (policy.hip): right behind the head's fragments, for layer l and head pair ph 2048 elements at m_lkv + (2 l + ph) 2048
+//             of the hi plane (head 2 ph) and of the lo plane (head 2 ph + 1), each [K hi 1 KiB | K lo 1 KiB | V^T 2 KiB] -- the
+//             8 KiB of one staged weight tile.  Not generated: perm -1 (the weight generation writes zeros there first)
+//   m_lproj   language_token_projection kernel [lang_dim, D], [D/32 mtile][lang_dim/16 kstep] frags in the projection's kproj order
+//   v_lproj_b its bias, C-layout (D floats)
+//   v_lpos    pos_embedding rows [0, T), one C-layout row of D floats each; PolicyLayout::v_pos then holds rows [T, T + P + 1),
+//             so the policy kernel's patch / action rows need no change
+constexpr int LANG_PAIR_BYTES = 8192;
+struct LangLayout {
+  int on = 0;
+  int m_lkv = 0, m_lproj = 0, v_lproj_b = 0, v_lpos = 0;
+};
+
 struct PackedLayout {
   PolicyLayout pl;
+  LangLayout ll;
   std::vector<int32_t> perm;   // [Gm + Gv] -> reference flat index or -1
 };
 
@@ -141,11 +164,21 @@ inline PackedLayout build_layout(const Geom& g) {
   p.m_layer_stride = p.m_fc2 + TM * TD * 2 * 512;
   p.m_layer0 = m;  m += g.L * p.m_layer_stride;
   p.m_head = m;  m += (D / 16) * 512;
+  LangLayout& ll = out.ll;
+  ll.on = g.lang_in_policy ? 1 : 0;
+  if (ll.on) {
+    ll.m_lkv = m;  m += g.L * 2 * (LANG_PAIR_BYTES / 4);             // (policy_body.inc derives it as m_head + 4 frags)
+    ll.m_lproj = m;  m += TD * (g.lang_dim / 16) * 512;
+  }
   p.Gm = m;
   // ---- vector region offsets
   int v = 0;
   p.v_proj_bias = v;  v += D;
   p.v_pos = v;  v += S * D;
+  if (ll.on) {
+    ll.v_lproj_b = v;  v += D;
+    ll.v_lpos = v;  v += g.T * D;
+  }
   p.v_ln0_s = 0;  p.v_ln0_b = D;  p.v_qkv_b = 2 * D;  p.v_out_b = 5 * D;
   p.v_ln1_s = 6 * D;  p.v_ln1_b = 7 * D;  p.v_fc1_b = 8 * D;  p.v_fc2_b = 8 * D + M;
   p.v_layer_stride = 9 * D + M;
@@ -185,8 +218,21 @@ inline PackedLayout build_layout(const Geom& g) {
         put_frag(p.m_proj, f, mt, ks, kproj, 0, [&](int k, int n) { return (int32_t)(K.offset + (int64_t)k * D + n); });
     cvec(p.v_proj_bias, TD, [&](int n) { return (int32_t)(Bv.offset + n); });
     const LeafInfo& Pe = find("encoder_pos_embedding");
+    const int t0 = ll.on ? g.T : 0;                       // patch / action rows follow the language rows
     for (int t = 0; t < S; ++t)
-      cvec(p.v_pos + t * D, TD, [&](int n) { return (int32_t)(Pe.offset + (int64_t)t * D + n); });
+      cvec(p.v_pos + t * D, TD, [&](int n) { return (int32_t)(Pe.offset + (int64_t)(t0 + t) * D + n); });
+    if (ll.on) {
+      for (int t = 0; t < g.T; ++t)
+        cvec(ll.v_lpos + t * D, TD, [&](int n) { return (int32_t)(Pe.offset + (int64_t)t * D + n); });
+      const LeafInfo& Kl = find("encoder_language_token_projection_kernel");
+      const LeafInfo& Bl = find("encoder_language_token_projection_bias");
+      const int El = g.lang_dim;
+      int fl = 0;
+      for (int mt = 0; mt < TD; ++mt)
+        for (int ks = 0; ks < El / 16; ++ks, ++fl)
+          put_frag(ll.m_lproj, fl, mt, ks, kproj, 0, [&](int k, int n) { return (int32_t)(Kl.offset + (int64_t)k * D + n); });
+      cvec(ll.v_lproj_b, TD, [&](int n) { return (int32_t)(Bl.offset + n); });
+    }
   }
   for (int l = 0; l < g.L; ++l) {
     const std::string Bn = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_";

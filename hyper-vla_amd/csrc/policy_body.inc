@@ -3,13 +3,29 @@
 // row slots[b] (one wave-uniform load at entry; a row outside [0, p.B), the arena's rows, is skipped) and writes tokens / actions / logits /
 // attention at call row b as always.  With HVLA_POLICY_SLOTS 0 the preprocessor hands the compiler the kernel's text as it was
 // before the pool existed, so policy_kernel<8, 2> compiles to the same code (DESIGN.md §10).
+// HVLA_POLICY_LANG 1 (policy_kernel_lang / policy_kernel_slots_lang, DESIGN.md §11): use_language_token.  The episode's language
+// tokens lead the sequence; their K / V of every layer were written once per episode by lang_prefix_kernel (policy.hip) into the
+// episode's arena row (LangLayout::m_lkv).  Patch queries and the action query attend over one more key tile, the prefix of the
+// current layer and head pair, staged by LDS-DMA into `pre` at the q tile of the pair; its keys >= lang_T are masked.  Undefined = 0.
   extern __shared__ __attribute__((aligned(16))) char smem[];
+#if HVLA_POLICY_LANG
+  constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 10;          // NP: <= 8 waves + the language prefix + the own key
+  constexpr int NPART = NW + 1, SPX = SP + 32;                         // partials before the own key; keys of the attention-map export
+  static_assert(NW + 2 <= NP, "partial table");
+#else
   constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 9;           // NHR heads resident in LDS at a time; NP: partials per head (<= 8 waves + the own key)
+  constexpr int NPART = NW, SPX = SP;
   static_assert(NW + 1 <= NP, "partial table");
+#endif
   // the action token's scratch sits at the START of the dynamic LDS (compile-time addresses: every access is an immediate
   // offset from a lane term, instead of a loop-invariant address register per buffer that the allocator then spills)
-  constexpr int ACT_FLOATS = 384 + 2 * NP * 20 + NW * 32 + 2 * SP + 96 + NW * 64, ACT_BYTES = (ACT_FLOATS * 4 + 1023) & ~1023;
+  constexpr int ACT_FLOATS = 384 + 2 * NP * 20 + NW * 32 + 2 * SPX + 96 + NW * 64, ACT_BYTES = (ACT_FLOATS * 4 + 1023) & ~1023;
+#if HVLA_POLICY_LANG
+  constexpr bool SPREAD = false;               // (the language variant runs the action row's jobs one wave per tile: with act_rows64
+                                               // it does not fit policy_kernel's register budget, DESIGN.md §11)
+#else
   constexpr bool SPREAD = NW == 8;             // the action row's jobs over all eight waves (act_rows64); fewer waves: one wave per tile
+#endif
   char* ring = smem + ACT_BYTES;                                       // [PRING][8 KiB] staged weight tiles
   // K of the resident heads: [head][key tile][d half][32 keys][8 d] -- inside a key tile the 16-byte piece of (key, half) sits at
   // lane position half * 32 + key, so a wave's write of its tile and every wave's ds_read_b128 of a tile are lane-linear 1 KiB
@@ -30,13 +46,23 @@
   }
 #endif
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#if HVLA_POLICY_LANG
+  char* pre = reinterpret_cast<char*>(Vt + NHR * 32 * VLD);           // [8 KiB] the resident head pair's language prefix:
+                                                                       // [head][K hi 1 KiB | K lo 1 KiB | V^T 2 KiB] (lang_prefix_kernel)
+  char* park = pre + LANG_PAIR_BYTES + wave * 4096;
+#else
   char* park = reinterpret_cast<char*>(Vt + NHR * 32 * VLD) + wave * 4096;   // [NW][4 KiB]: phase A's attention outputs
+#endif
   // The per-layer vectors of the episode (LayerNorm scale / bias, the four biases; then encoder_norm and the head bias:
   // Gv - v_layer0 floats, 12 KB at the README geometry) are copied to LDS once.  Read from global memory where they are
   // used, each of them -- one per staged tile -- made the compiler wait with vmcnt(0), i.e. for the weight tiles whose DMA
   // had just been issued as well: the three-tile prefetch was undone by a 64-byte bias load (tools/policy_timeline.py:
   // 4 us per tile step for 0.2 us of MFMAs).
+#if HVLA_POLICY_LANG
+  float* vlds = reinterpret_cast<float*>(pre + LANG_PAIR_BYTES + NW * 4096);
+#else
   float* vlds = reinterpret_cast<float*>(reinterpret_cast<char*>(Vt + NHR * 32 * VLD) + NW * 4096);
+#endif
   const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
   const int P = NW * 32;
   const int token = wave * 32 + col;
@@ -50,8 +76,8 @@
   float* ga = xa + 352;                                                // [32] GELU(fc1) of the current hidden tile
   float* part = xa + 384;                                              // [2][NP][20]: per head and wave (max, sum, P.V[16])
   float* pbuf = part + 2 * NP * 20;                                    // [NW][32] wave-private: p in V^T column order
-  float* pexp = pbuf + NW * 32;                                        // [2][SP] p per key (attention-map export only)
-  float* qkv1 = pexp + 2 * SP;                                         // [96] q / k / v of head pair 1 (SPREAD: pair 0's are still being combined
+  float* pexp = pbuf + NW * 32;                                        // [2][SPX] p per key (attention-map export only; LANG: the prefix at SP)
+  float* qkv1 = pexp + 2 * SPX;                                        // [96] q / k / v of head pair 1 (SPREAD: pair 0's are still being combined
                                                                        //      by one wave while every wave writes pair 1's)
   float* hpriv = qkv1 + 96 + wave * 64;                                // [NW][64] this wave's own LayerNorm output (SPREAD)
   const __bf16* __restrict__ wh = p.wh + (size_t)b * L.Gm;
@@ -59,12 +85,18 @@
   const float* __restrict__ vf = p.vf + (size_t)b * L.Gv;
   const int E = p.E;
   const int nproj = 2 * (E / 64), TM = p.M / 32, ntiles = nproj + p.L * (8 + 2 * TM) + 1;
+#if HVLA_POLICY_LANG
+  // lang_T and the prefix's offset in the arena row (LangLayout::m_lkv: behind the head's four fragments) are held in VGPRs: this
+  // variant's SGPRs are all taken (held to policy_kernel's budget of SGPRs parked in VGPR lanes, tests/test_abi.py)
+  const int lang_Tv = opaque(lang_T);
+  const int lkv0 = opaque(L.m_head + 4 * 512);
+#endif
 
   // ---- the staging pipeline (see PRING above)
   const uint32_t lds_ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
-#if HVLA_POLICY_SLOTS
-  constexpr bool stream_nt = true;                                     // the pool form streams its weights non-temporally at every K:
-                                                                       // one SGPR fewer, which keeps it at policy_kernel's SGPR budget
+#if HVLA_POLICY_SLOTS || HVLA_POLICY_LANG
+  constexpr bool stream_nt = true;                                     // the pool and language forms stream their weights non-temporally at
+                                                                       // every K: one SGPR fewer, which keeps them at policy_kernel's SGPR budget
 #else
   const bool stream_nt = (int)gridDim.x >= 64;                         // (uniform) see dma()
 #endif
@@ -92,6 +124,22 @@
       }
     }
   };
+#if HVLA_POLICY_LANG
+  // the language prefix of layer l, head pair ph (arena rows, LangLayout::m_lkv: head 0 in the hi plane, head 1 in the lo plane)
+  // -> pre: issued right behind the q tile's barrier (every wave is done with the previous pair's prefix); the k and v tiles'
+  // full fences land it before the attention reads it
+  const uint32_t lds_pre = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)pre;
+  auto dma_lang = [&](int l, int ph) {
+    const int off = opaque(lkv0) + (2 * l + ph) * 2048;
+    for (int f = wave; f < 8; f += NW) {
+      const __bf16* src = (f < 4 ? wh : wl) + off + (f & 3) * 512 + lane * 8;
+      const uint32_t dst = __builtin_amdgcn_readfirstlane(opaque((int)(lds_pre + (uint32_t)(f * 1024))));
+      uint32_t keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+    }
+  };
+#endif
   // tile `ti` has landed for every wave and every wave is done with tile ti - 1 (LDS reads and writes retired in front of
   // the barrier), whose slot then takes tile ti + PRING - 1.  With one DMA per wave and tile (NW = 8) a wave's DMA of tile
   // ti is older than its DMAs of tiles ti + 1 and ti + 2, so all but the two youngest vector-memory operations suffice
@@ -214,7 +262,7 @@
       const float ls = wsum64(half == 0 ? pj : 0.f);
       float* pb = pbuf + wave * 32;
       if (half == 0) pb[vperm32(col)] = pj;     // the order of the V^T image's columns
-      if (p.amap && half == 0) pexp[hl * SP + slot_k] = pj;
+      if (p.amap && half == 0) pexp[hl * SPX + slot_k] = pj;
       const _Float16* vrow = Vt + (hl * 32 + col) * VLD + wave * 32 + 16 * half;      // row col: d (hi) or 16 + d (lo x 2^10)
       const f16x8 v0 = *reinterpret_cast<const f16x8*>(vrow), v1 = *reinterpret_cast<const f16x8*>(vrow + 8);
       float a = 0.f;
@@ -233,6 +281,47 @@
       if (lane == 0) pp[0] = m, pp[1] = ls;
       if (lane < 16) pp[2 + lane] = od;
     };
+#if HVLA_POLICY_LANG
+    // the same over the language prefix's 32 keys (keys >= lang_T masked) -> part[hl][NW]; one wave
+    auto act_attend_lang = [&](int hl, const float* qbase) {
+      const int lane = opaque((int)(threadIdx.x & 63)), col = lane & 31, half = lane >> 5;
+      const float* qv = qbase + hl * 16 + 4 * half;
+      const f32x4 q0 = *reinterpret_cast<const f32x4*>(qv), q1 = *reinterpret_cast<const f32x4*>(qv + 8);
+      const char* ph_ = pre + hl * 4096;
+      const bf16x8 khi = *reinterpret_cast<const bf16x8*>(ph_ + lane * 16);
+      const bf16x8 klo = *reinterpret_cast<const bf16x8*>(ph_ + 1024 + lane * 16);
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s = fmaf((float)khi[j] + (float)klo[j], q0[j], s);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s = fmaf((float)khi[4 + j] + (float)klo[4 + j], q1[j], s);
+      s += __shfl_xor(s, 32, 64);
+      if (col >= opaque(lang_Tv)) s = -1e30f;            // padding of the 32-key tile (not T5 padding: that is attended, base_vit.py:207-212)
+      const float m = wmax64(s);
+      const float pj = __builtin_amdgcn_exp2f(s - m);
+      const float ls = wsum64(half == 0 ? pj : 0.f);
+      float* pb = pbuf + wave * 32;
+      if (half == 0) pb[vperm32(col)] = pj;
+      if (p.amap && half == 0) pexp[hl * SPX + SP + col] = pj;
+      const _Float16* vrow = reinterpret_cast<const _Float16*>(ph_ + 2048) + col * 32 + 16 * half;
+      const f16x8 v0 = *reinterpret_cast<const f16x8*>(vrow), v1 = *reinterpret_cast<const f16x8*>(vrow + 8);
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const f32x4 pa = *reinterpret_cast<const f32x4*>(pb + 16 * half + 4 * i);
+        const f32x4 pc = *reinterpret_cast<const f32x4*>(pb + 16 * half + 8 + 4 * i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a = fmaf((float)v0[4 * i + j], pa[j], a);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a = fmaf((float)v1[4 * i + j], pc[j], a);
+      }
+      a += __shfl_xor(a, 32, 64);
+      const float od = fmaf(__shfl_xor(a, 16, 64), 1.f / 1024.f, a);
+      float* pp = part + (hl * NP + NW) * 20;
+      if (lane == 0) pp[0] = m, pp[1] = ls;
+      if (lane < 16) pp[2 + lane] = od;
+    };
+#endif
     // combine the partials of head pair `pair` (all waves' keys + the action token's own key, base_vit.py:209-214: the
     // action row sees every token) -> oa[(2 pair + hl) * 16 + d]; run by ONE wave, after the barrier that follows the
     // attention of that pair and before anything overwrites qa / ka / va
@@ -244,20 +333,32 @@
       for (int hl = 0; hl < NHR; ++hl) {
         const float self = wsum64(lane < 16 ? qa[hl * 16 + lane] * ka[hl * 16 + lane] : 0.f);
         const float* pt = part + hl * NP * 20;
-        const float mt = lane < NW ? pt[lane * 20] : (lane == NW ? self : -1e30f);
-        const float lt = lane < NW ? pt[lane * 20 + 1] : (lane == NW ? 1.f : 0.f);
+        const float mt = lane < NPART ? pt[lane * 20] : (lane == NPART ? self : -1e30f);
+        const float lt = lane < NPART ? pt[lane * 20 + 1] : (lane == NPART ? 1.f : 0.f);
         const float M = wmax64(mt);
         const float f = __builtin_amdgcn_exp2f(mt - M);
         const float inv = 1.f / wsum64(f * lt);
         float od = 0.f;
 #pragma unroll
-        for (int t = 0; t < NW; ++t) od = fmaf(__shfl(f, t, 64), pt[t * 20 + 2 + (lane & 15)], od);
-        od = fmaf(__shfl(f, NW, 64), va[hl * 16 + (lane & 15)], od);
+        for (int t = 0; t < NPART; ++t) od = fmaf(__shfl(f, t, 64), pt[t * 20 + 2 + (lane & 15)], od);
+        od = fmaf(__shfl(f, NPART, 64), va[hl * 16 + (lane & 15)], od);
         if (lane < 16) oa[(2 * pair + hl) * 16 + lane] = od * inv;
         if (p.amap) {                           // attention_weights[0][0, head, -1, :-1] (hypervla_interface.py:213-215)
           constexpr int HEADS = 2 * NHR;      // the kernel is specialised for 64 features = 4 heads of 16 (hvla_create refuses anything else):
+#if HVLA_POLICY_LANG
+          // [B, L, heads, lang_T + P]: the language keys first (the reference's sequence order).  Key j of pexp: patch j < SP, or
+          // language key j - SP (partial NW = j >> 5 as well)
+          const int lT = opaque(lang_Tv);
+          float* am = p.amap + (((size_t)b * p.L + l) * HEADS + 2 * pair + hl) * (P + lT);
+          for (int j = lane; j < SPX; j += 64) {
+            const float v = pexp[hl * SPX + j] * __shfl(f, j >> 5, 64) * inv;
+            if (j < SP) am[lT + j] = v;
+            else if (j - SP < lT) am[j - SP] = v;
+          }
+#else
           float* am = p.amap + (((size_t)b * p.L + l) * HEADS + 2 * pair + hl) * P;   // the caller's [B, L, heads, P] buffer
           for (int j = lane; j < SP; j += 64) am[j] = pexp[hl * SP + j] * __shfl(f, j >> 5, 64) * inv;
+#endif
         }
       }
     };
@@ -275,6 +376,9 @@
         for (int k = 0; k < 3; ++k) {         // q, k, v tile of this head pair
           const int t = 2 * k + ph;
           const char* slot = acquire();
+#if HVLA_POLICY_LANG
+          if (k == 0) dma_lang(l, ph);
+#endif
           if constexpr (SPREAD) {             // the action row through this tile: four of its 32 outputs per wave
             const int lane = opaque((int)(threadIdx.x & 63));
             if (k == 0) {
@@ -350,6 +454,12 @@
       HVLA_STAMP();                             // 2 + 6 l + 2 ph: q / k / v of the head pair done
 #pragma unroll
       for (int hl = 0; hl < NHR; ++hl) act_attend(hl, (SPREAD && ph) ? qkv1 : qa);
+#if HVLA_POLICY_LANG
+      if (wave == NW - 1) {                   // the action row over the language prefix: one more partial
+#pragma unroll
+        for (int hl = 0; hl < NHR; ++hl) act_attend_lang(hl, (SPREAD && ph) ? qkv1 : qa);
+      }
+#endif
       if (full) {
 #pragma unroll
         for (int hl = 0; hl < NHR; ++hl) {
@@ -363,14 +473,45 @@
             for (int r = 0; r < 16; ++r) sc[r] = init;
             return mma32_x3p<TIE>(kf, qf[hl], sc);
           };
+#if HVLA_POLICY_LANG
+          auto lscores = [&](float init) {             // the language prefix tile, keys >= lang_T masked
+            const int ln = opaque((int)(threadIdx.x & 63));
+            Split8 kf;
+            kf.hi = *reinterpret_cast<const bf16x8*>(pre + hl * 4096 + ln * 16);
+            kf.lo = *reinterpret_cast<const bf16x8*>(pre + hl * 4096 + 1024 + ln * 16);
+            f32x16 sc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sc[r] = init;
+            sc = mma32_x3p<TIE>(kf, qf[hl], sc);
+            // key crow(r, half) >= lang_T is padding of the tile.  The limit goes through an empty asm here: sixteen compares against
+            // a loop-invariant value would otherwise be hoisted out of the layer loop as sixteen lane masks (SGPR pairs) kept live
+            const int lim = opaque(lang_Tv) - 4 * (ln >> 5);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if ((r & 3) + 8 * (r >> 2) >= lim) sc[r] = -1e30f;
+            return sc;
+          };
+#endif
           // pass 1: row maximum (scores are in the log2 domain: q carries 1/sqrt(hd) log2 e).  Patches cannot see the
           // action token (base_vit.py:209-214): structural, its key is in no tile.
           float m2 = -1e30f;
+#if HVLA_POLICY_LANG
+          // (rolled in this variant: unrolled, the lane's addresses of the eight key tiles are hoisted out of the layer loop into
+          // registers it does not have, DESIGN.md §11)
+#pragma unroll 1
+#endif
           for (int kt = 0; kt < NW; ++kt) {
             const f32x16 sc = scores(kt, 0.f);
 #pragma unroll
             for (int r = 0; r < 16; ++r) m2 = fmaxf(m2, sc[r]);
           }
+#if HVLA_POLICY_LANG
+          {
+            const f32x16 sc = lscores(0.f);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) m2 = fmaxf(m2, sc[r]);
+          }
+#endif
           m2 = fmaxf(m2, __shfl_xor(m2, 32, 64));
           // pass 2: p = exp2(s - max) straight out of the accumulator (initialised to -max); P = hi + lo in fp16 against
           // V = [hi | lo x 2^10] in fp16: four MFMAs per key tile, all four hi / lo cross terms
@@ -378,6 +519,9 @@
           f32x16 O;
 #pragma unroll
           for (int r = 0; r < 16; ++r) O[r] = 0.f;
+#if HVLA_POLICY_LANG
+#pragma unroll 1
+#endif
           for (int kt = 0; kt < NW; ++kt) {
             const f32x16 sc = scores(kt, -m2);
             const _Float16* vp = Vt + (hl * 32 + col) * VLD + kt * 32 + half * 8;
@@ -398,6 +542,29 @@
               __builtin_amdgcn_sched_barrier(0);
             }
           }
+#if HVLA_POLICY_LANG
+          {
+            const f32x16 sc = lscores(-m2);
+            const int ln = opaque((int)(threadIdx.x & 63));
+            const _Float16* vp = reinterpret_cast<const _Float16*>(pre + hl * 4096 + 2048) + (ln & 31) * 32 + (ln >> 5) * 8;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+              f16x8 phi, plo;
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
+                const float e = __builtin_amdgcn_exp2f(sc[8 * ks + r]);
+                lsum += e;
+                phi[r] = (_Float16)e;
+                plo[r] = (_Float16)(e - (float)phi[r]);
+              }
+              f16x8 v = *reinterpret_cast<const f16x8*>(vp + 16 * ks);
+              if constexpr (TIE == 1 || TIE == 2) asm volatile("" : "+v"(v));
+              O = __builtin_amdgcn_mfma_f32_32x32x16_f16(v, plo, O, 0, 0, 0);
+              O = __builtin_amdgcn_mfma_f32_32x32x16_f16(v, phi, O, 0, 0, 0);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+#endif
           const float inv = 1.f / wave_xor_sum32(lsum);
           float ov[8];
 #pragma unroll

@@ -24,7 +24,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_t5_encode", "hvla_preprocess", "hvla_encode_audit", "hvla_train_accumulate", "hvla_train_bucket_ranges",
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
-           "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step"]
+           "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
+           "hvla_create_with"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -40,6 +41,11 @@ class hvla_config(C.Structure):
                [("tanh_scale", C.c_float), ("max_action", C.c_float)] + \
                [(n, C.c_int32) for n in ("ctx_dim", "ctx_layers", "ctx_heads", "ctx_mlp", "lang_tokens",
                                          "lang_dim", "scale_context", "max_batch", "enc_dtype", "streams", "clip_target")]
+
+
+class hvla_policy_options(C.Structure):
+    """Model options outside hvla_config (include/hvla.h): struct_size must be sizeof(hvla_policy_options)."""
+    _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32)]
 
 
 class hvla_tensor_desc(C.Structure):
@@ -87,6 +93,8 @@ def load_library():
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     lib.hvla_create.argtypes = [C.POINTER(hvla_config), C.c_int, C.POINTER(vp)]
     lib.hvla_create.restype = C.c_int
+    lib.hvla_create_with.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options), C.c_int, C.POINTER(vp)]
+    lib.hvla_create_with.restype = C.c_int
     lib.hvla_destroy.argtypes = [vp]
     lib.hvla_destroy.restype = None
     lib.hvla_last_error.argtypes = [vp]
@@ -198,7 +206,11 @@ class Context:
                                int(getattr(g, "clip_target", True)))
         self.geometry, self.device, self.max_batch, self.enc_dtype = g, device, max_batch, enc_dtype
         h = C.c_void_p()
-        rc = self.lib.hvla_create(C.byref(self.cfg), device, C.byref(h))
+        if getattr(g, "lang_in_policy", False):       # use_language_token: the options struct (hvla_config's size is ABI)
+            self.options = hvla_policy_options(C.sizeof(hvla_policy_options), 1)
+            rc = self.lib.hvla_create_with(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
+        else:
+            rc = self.lib.hvla_create(C.byref(self.cfg), device, C.byref(h))
         if rc != 0:
             raise NativeError(f"hvla_create failed: {_ERRORS.get(rc, rc)} (geometry outside the hand-written "
                               f"kernels' specialisation, or device {device} is not a gfx950 GPU)")

@@ -48,6 +48,9 @@ class Geometry:
     lang_tokens: int = 32       # T5 max_length (hypervla_pretrain_config.py:302-312)
     lang_dim: int = 768         # T5-base hidden size
     scale_context: bool = True
+    # base_net_kwargs.vit_kwargs.use_language_token (base_vit.py:159-166,207-212): the T5 token embeddings, projected to D,
+    # lead the policy's sequence [T language | P patches | 1 action]; language queries see only language keys
+    lang_in_policy: bool = False
 
     @property
     def grid(self) -> int:
@@ -60,6 +63,10 @@ class Geometry:
     @property
     def seq(self) -> int:          # S = patches + 1 action token (policy) / + CLS (encoder)
         return self.patches + 1
+
+    @property
+    def policy_seq(self) -> int:   # rows of the policy's pos_embedding: [T language if lang_in_policy | P patches | 1 action]
+        return self.seq + (self.lang_tokens if self.lang_in_policy else 0)
 
     @property
     def ctx_seq(self) -> int:      # language tokens + initial-image CLS + 1 layer token
@@ -151,7 +158,8 @@ class Leaf:
 
 
 def generated_leaves(g: Geometry) -> List[Leaf]:
-    """The 73 HN-generated leaves in jax pytree order (dict keys sorted at every level).
+    """The 73 HN-generated leaves in jax pytree order (dict keys sorted at every level); 75 with ``lang_in_policy``, which adds
+    ``encoder/language_token_projection`` (base_vit.py:162-165) between the image projection and the position embedding.
 
     ``shared_modules=("image_encoder",)`` removes the DINOv2 leaves (hypervla/model.py:439-451);
     ``share_layer_index=True`` makes every leaf read context token 0 (model.py:400-402).
@@ -179,8 +187,11 @@ def generated_leaves(g: Geometry) -> List[Leaf]:
                   (A_ + ("query", "bias"), (H, hd)), (A_ + ("query", "kernel"), (D, H, hd)),
                   (A_ + ("value", "bias"), (H, hd)), (A_ + ("value", "kernel"), (D, H, hd))]
     items += [(("encoder", "image_embedding_projection", "bias"), (D,)),
-              (("encoder", "image_embedding_projection", "kernel"), (E, D)),
-              (("encoder", "pos_embedding"), (1, g.seq, D))]
+              (("encoder", "image_embedding_projection", "kernel"), (E, D))]
+    if g.lang_in_policy:
+        items += [(("encoder", "language_token_projection", "bias"), (D,)),
+                  (("encoder", "language_token_projection", "kernel"), (g.lang_dim, D))]
+    items += [(("encoder", "pos_embedding"), (1, g.policy_seq, D))]
     leaves, off = [], 0
     for path, shape in items:
         leaves.append(Leaf(path, tuple(shape), off))
@@ -231,7 +242,7 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
             action_dim=g.action_dim,
             vit_kwargs=dict(encoder_type="DINOv2", patch_size=16, hidden_dim=g.dim,
                             num_layers=g.layers, num_heads=g.heads, mlp_dim=g.mlp,
-                            dropout_rate=0.0, use_language_token=False,
+                            dropout_rate=0.0, use_language_token=bool(g.lang_in_policy),
                             fine_tune_pretrained_image_encoder=True, image_embedding_noise=0.0,
                             use_differential_transformer=False, return_attention_map=False,
                             add_positional_embedding=True, include_class_token=False),
@@ -249,6 +260,7 @@ def geometry_from_config(cfg: Dict) -> Geometry:
     """Inverse of :func:`default_config` (rejects branches the path does not build)."""
     b, h = cfg["base_net_kwargs"], cfg["hypernet_kwargs"]
     v, a = b["vit_kwargs"], b["action_head_kwargs"]
+    ge = cfg.get("geometry", {})
     if b["model_type"] != "vit" or b["action_head_type"] != "mix" or v["encoder_type"] != "DINOv2":
         raise ValueError("only model_type=vit / encoder_type=DINOv2 / action_head_type=mix is built "
                          "(README.md:45-56); got %r/%r/%r" % (b["model_type"], v["encoder_type"],
@@ -261,10 +273,19 @@ def geometry_from_config(cfg: Dict) -> Geometry:
                              f"(README.md:33-44 uses {want!r})")
     if a.get("token_per_horizon") or a.get("hidden_dims"):
         raise ValueError("token_per_horizon / hidden_dims action heads are not built")
+    lang_in_policy = bool(v.get("use_language_token", False))
+    for key, want in (("include_class_token", False), ("add_positional_embedding", True),
+                      ("use_differential_transformer", False)):
+        if bool(v.get(key, want)) != want:
+            raise ValueError(f"base_net_kwargs.vit_kwargs.{key}={v.get(key)!r} is outside the built path (only {want!r} is built)")
+    if b.get("action_token_num", 1) != 1 or v.get("action_token_num", 1) != 1:
+        raise ValueError("action_token_num != 1 is not built: the policy kernels run exactly one action token")
+    if lang_in_policy and ge.get("lang_tokens", 32) > 32:
+        raise ValueError(f"use_language_token with lang_tokens={ge.get('lang_tokens')} is not built: the language prefix must fit "
+                         "one 32-key tile of the policy kernel")
     if not a.get("squash_continuous_action", True):
         raise ValueError("squash_continuous_action=False is not built: the mix head kernels apply tanh(x / s) * max_action "
                          "(action_heads.py:469-470)")
-    ge = cfg.get("geometry", {})
     ce = h["context_encoder_kwargs"]
     return Geometry(
         image_size=ge.get("image_size", 224), patch=ge.get("patch", 14),
@@ -277,7 +298,7 @@ def geometry_from_config(cfg: Dict) -> Geometry:
         ctx_dim=h["context_embedding_dim"], ctx_layers=ce["num_layers"],
         ctx_heads=ce["num_attention_heads"], ctx_mlp=ce["mlp_dim"],
         lang_tokens=ge.get("lang_tokens", 32), lang_dim=ge.get("lang_dim", 768),
-        scale_context=bool(h.get("scale_context_embedding", False)))
+        scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy)
 
 
 # --------------------------------------------------------------------------------------

@@ -380,7 +380,10 @@ class HyperVLA:
         """hypervla/model.py:85-137.  images uint8 [B, 1, H, W, 3] (or [B, H, W, 3]) -> actions
         [B, horizon, action_dim].  `attention_maps=True` also returns the two attention slices the reference's wrapper keeps
         from the intermediates (hypervla_interface.py:208-217): DINOv2's CLS-query attention over the patches, every layer and
-        head, and the generated policy's action-token attention over the patches.
+        head, and the generated policy's action-token attention over the patches (with use_language_token: over the language
+        tokens first, then the patches, [B, layers, heads, lang_tokens + P]).
+        With use_language_token the language tokens the policy reads are those given to create_tasks / assign_tasks for these
+        episodes (kept beside their weights); `instruction_dict` is not read here, as before.
         `slots` (episode pool): step only these K slots of `base_params` (`hvla_step_slots`): images [K, ...] in, every output
         [K, ...] out, row k that of slot slots[k]."""
         torch = _torch()
@@ -414,7 +417,9 @@ class HyperVLA:
         inter = {"gripper_logits": logits}
         if attention_maps:
             inter["dino_cls_attention"] = torch.empty(B, g.enc_layers, g.enc_heads, g.patches, dtype=torch.float32, device=self.device)
-            inter["head_attention"] = torch.empty(B, g.layers, g.heads, g.patches, dtype=torch.float32, device=self.device)
+            # with use_language_token the action token's keys are [T language | P patches] (hypervla_interface.py:215 `[:-1]`)
+            keys = g.patches + (g.lang_tokens if g.lang_in_policy else 0)
+            inter["head_attention"] = torch.empty(B, g.layers, g.heads, keys, dtype=torch.float32, device=self.device)
             self._ctx.set_attention_outputs(inter["dino_cls_attention"].data_ptr(), inter["head_attention"].data_ptr())
         try:
             if slots is None:

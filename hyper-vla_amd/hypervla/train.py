@@ -170,6 +170,9 @@ class FineTuner:
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
                  accept_baked_position_table: bool = False):
+        if getattr(model.geometry, "lang_in_policy", False):
+            raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
+                             "policy without language tokens (serving it is, DESIGN.md §11)")
         import torch
         self.torch, self.model, self.g, self.B = torch, model, model.geometry, batch
         self.train_encoder = bool(train_encoder)

@@ -82,6 +82,22 @@ typedef struct hvla_tensor_desc {
 
 /* Replaces: HyperVLA.load_pretrained's model construction (hypervla/model.py:197-208).          */
 int hvla_create(const hvla_config* cfg, int device, hvla_ctx** out);
+
+/* Model options outside hvla_config (whose size is part of the ABI).  Follows hvla_config's rule: struct_size must be
+ * sizeof(hvla_policy_options) of this header, or hvla_create_with returns HVLA_E_SHAPE before reading anything else.
+ *   use_language_token  base_net_kwargs.vit_kwargs.use_language_token (base_vit.py:159-166,207-212): the token embeddings
+ *                       given to hvla_generate, projected by the generated language_token_projection, lead the policy's
+ *                       sequence [lang_tokens language | P patches | 1 action]; language queries see only language keys.
+ *                       Needs lang_tokens <= 32 and lang_dim % 64 == 0.  hvla_generate / hvla_generate_slots then also run
+ *                       the language tokens through the policy once per episode and keep their K / V of every layer beside
+ *                       the episode's weights; the training entry points refuse such a ctx.            */
+typedef struct hvla_policy_options {
+  uint32_t struct_size;                      /* = sizeof(hvla_policy_options)                                           */
+  int32_t use_language_token;                /* 0 (default) or 1                                                        */
+} hvla_policy_options;
+
+/* hvla_create with options; opts == NULL is hvla_create (the same ctx, byte for byte).                               */
+int hvla_create_with(const hvla_config* cfg, const hvla_policy_options* opts, int device, hvla_ctx** out);
 void hvla_destroy(hvla_ctx* ctx);
 const char* hvla_last_error(const hvla_ctx* ctx);
 
@@ -138,7 +154,9 @@ int hvla_policy(hvla_ctx* ctx, const hvla_weights* w, const float* tokens, float
  *   dino_cls_attention f32 [B, enc_layers, enc_heads, P]  DINOv2: attention of the CLS query over the P patch keys
  *                                                          (`DINO_attention_map[0][layer][b, :, 0, 1:]`)
  *   head_attention     f32 [B, layers, heads, P]          generated policy: attention of the action token over the P patch
- *                                                          keys (`attention_weights[0][b, :, -1, :-1]`)
+ *                                                          keys (`attention_weights[0][b, :, -1, :-1]`); with
+ *                                                          use_language_token [B, layers, heads, lang_tokens + P]: the
+ *                                                          language keys first, as the reference's sequence has them
  * Opt-in: the DEVICE buffers registered here (either may be NULL) are written by every following hvla_encode /
  * hvla_policy / hvla_step on this ctx until the call is repeated with NULLs; rows are the episodes of that call.   */
 int hvla_set_attention_outputs(hvla_ctx* ctx, float* dino_cls_attention, float* head_attention);
