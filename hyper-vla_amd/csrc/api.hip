@@ -1146,6 +1146,36 @@ int hvla_debug_bgemm(const float* A, const float* B, float* C, int M, int N, int
   return hipGetLastError() == hipSuccess ? HVLA_OK : HVLA_E_HIP;
 }
 
+// ONE launch of the fine-tune path's batched GEMM with every field of the descriptor in the caller's hands (tools/bgemm_check.py,
+// tests/test_gpu_train_gemm.py): a plain-C mirror of BG (train.h) plus the operand orders and the outer batch count.  Null stream,
+// synchronised; returns the HIP status (0 = hipSuccess).  chosen[4] = what bgemm_launch selected: tile rows (64 / 128 / 256), float4
+// staging, the effective ksplit, and 1 for bgemm_kernel (hvla_debug_train_gemm_exact).
+struct hvla_bgemm_desc {
+  const float* A;
+  const float* B;
+  float* C;
+  const float* bias;
+  int32_t M, N, K, lda, ldb, ldc;
+  int64_t sA0, sA1, sB0, sB1, sC0, sC1, sBias0, sBias1;
+  int32_t nb1;
+  float alpha;
+  int32_t accumulate, ksplit, allow_split, a_padded;
+  int32_t ta, tb, nb0;
+};
+int hvla_debug_bgemm_once(const hvla_bgemm_desc* d, int32_t* chosen) {
+  if (!d || !chosen || d->nb0 < 1 || d->nb1 < 1 || d->ksplit < 1 || d->M < 1 || d->N < 1 || d->K < 1) return (int)hipErrorInvalidValue;
+  BG g{d->A, d->B, d->C, d->bias, d->M, d->N, d->K, d->lda, d->ldb, d->ldc, (long)d->sA0, (long)d->sA1, (long)d->sB0, (long)d->sB1,
+       (long)d->sC0, (long)d->sC1, (long)d->sBias0, d->nb1, d->alpha, d->accumulate, d->ksplit, d->allow_split, d->a_padded, (long)d->sBias1};
+  (void)hipGetLastError();
+  bgemm(nullptr, d->ta != 0, d->tb != 0, g, d->nb0);
+  hipError_t e = hipGetLastError();
+  const hipError_t s = hipDeviceSynchronize();
+  if (e == hipSuccess) e = s;
+  const BgemmChoice& c = last_bgemm_choice();
+  chosen[0] = c.tile, chosen[1] = c.vec, chosen[2] = c.ksplit, chosen[3] = c.exact;
+  return (int)e;
+}
+
 // phase time stamps of attention_kernel for workgroups `wgs[i]` (8 stamps each), on the ctx's workspace (contents irrelevant)
 int hvla_debug_attention_stamps(hvla_ctx* ctx, int32_t B, const int32_t* wgs, int32_t nwg, unsigned long long* out) {
   if (!ctx || !out || !wgs) return HVLA_E_STATE;

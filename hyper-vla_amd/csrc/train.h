@@ -43,6 +43,10 @@ struct TrainLayout {
 TrainLayout make_train_layout(const Geom& g);
 #ifdef HVLA_BENCH_HOOKS
 void set_train_gemm_exact(bool on);
+// what the last bgemm() launch of this process chose (hvla_debug_bgemm_once reports it; tools/bgemm_check.py): tile = 64 / 128 / 256 rows
+// (256 x 128, else square), vec = float4 staging, ksplit = the K chunks on blockIdx.z, exact = bgemm_kernel (f32 instruction; tile 64)
+struct BgemmChoice { int tile, vec, ksplit, exact; };
+const BgemmChoice& last_bgemm_choice();
 #endif
 size_t train_workspace_floats(const Geom& g, int B, bool train_encoder);
 

@@ -341,8 +341,12 @@ static void launch_bgemm3(hipStream_t st, bool ta, bool tb, const BG& g, dim3 gr
 static bool g_train_gemm_exact = false;
 void set_train_gemm_exact(bool on) { g_train_gemm_exact = on; }
 static bool train_gemm_exact() { return g_train_gemm_exact; }
+static BgemmChoice g_bgemm_choice{0, 0, 0, 0};
+const BgemmChoice& last_bgemm_choice() { return g_bgemm_choice; }
+#define HVLA_BGEMM_CHOSE(tile, vec, ks, ex) (g_bgemm_choice = BgemmChoice{tile, vec, ks, ex})
 #else
 static constexpr bool train_gemm_exact() { return false; }
+#define HVLA_BGEMM_CHOSE(tile, vec, ks, ex) ((void)0)
 #endif
 
 // Optional live timing of the batched GEMM launches (hvla_train_profile: bench.py --finetune's `roofline` block): HIP events on
@@ -446,13 +450,16 @@ static void bgemm_launch(hipStream_t st, bool ta, bool tb, BG g, int nb0) {
     // between one and two 128 x 128 workgroups per CU: 256 x 128 tiles (eight waves) make it one round
     const long t128 = (long)grid.x * grid.y * grid.z, t256 = (long)grid.x * ((g.M + 255) / 256) * grid.z;
     if (T == 128 && vec && t128 > want && t128 <= 2 * want && t256 <= want) {
+      HVLA_BGEMM_CHOSE(256, 1, g.ksplit, 0);
       launch_bgemm3<256, 128, true>(st, ta, tb, g, dim3(grid.x, (g.M + 255) / 256, grid.z));
       return;
     }
+    HVLA_BGEMM_CHOSE(T, vec ? 1 : 0, g.ksplit, 0);
     if (T == 128) { if (vec) launch_bgemm3<128, 128, true>(st, ta, tb, g, grid); else launch_bgemm3<128, 128, false>(st, ta, tb, g, grid); }
     else { if (vec) launch_bgemm3<64, 64, true>(st, ta, tb, g, grid); else launch_bgemm3<64, 64, false>(st, ta, tb, g, grid); }
     return;
   }
+  HVLA_BGEMM_CHOSE(64, 0, g.ksplit, 1);
   if (!ta && !tb) hipLaunchKernelGGL((bgemm_kernel<false, false>), grid, dim3(256), 0, st, g);
   else if (!ta && tb) hipLaunchKernelGGL((bgemm_kernel<false, true>), grid, dim3(256), 0, st, g);
   else if (ta && !tb) hipLaunchKernelGGL((bgemm_kernel<true, false>), grid, dim3(256), 0, st, g);

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from adamw_ref import bf16_round as _bf16_round, optax_step as _optax_step
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -163,7 +165,7 @@ def test_full_geometry_gradients(golden_dir):
 
 
 # ------------------------------------------------------------------ trained image encoder (README.md:55)
-def _encoder_case(g, B, tol, seed_rank=0):
+def _encoder_case(g, B, tol, seed_rank=0, stats=None):
     from hypervla import synthetic as syn
     from hypervla.config import encoder_leaves, generated_leaves
     from hypervla.model import HyperVLA
@@ -186,6 +188,17 @@ def _encoder_case(g, B, tol, seed_rank=0):
     enc_rel = [r for r in rel if r[1].startswith("encoder_image_encoder_")]
     assert len(enc_rel) == len(encoder_leaves(g))
     assert any(float(grads[k].abs().max()) > 0 for _, k in enc_rel)
+    if stats is not None:
+        # the bias and LayerScale leaves of the encoder are the outputs of the column-sum / LayerScale kernels (colsum*_kernel,
+        # ls_bwd*_kernel, the LayerNorm parameter gradients): per ELEMENT against the leaf's RMS, so that a lost column group or row
+        # block is not hidden behind a large neighbour of the same leaf
+        for k, v in grads.items():
+            if k.startswith("encoder_image_encoder_encoder_layer_") and (k.endswith("bias") or k.endswith("lambda1") or k.endswith("scale")):
+                ref = v.numpy()
+                rms = float(np.sqrt((ref * ref).mean()))
+                if rms > 1e-6 * gmax:                   # (key biases: the softmax is invariant to them, their gradient is rounding noise)
+                    stats[k] = float(np.abs(got[k].reshape(ref.shape) - ref).max() / rms)
+        stats["__max_metric__"] = rel[0]
     assert rel[0][0] <= tol, rel[:6]
     return model, ft, (ins, st, im, batch)
 
@@ -201,6 +214,38 @@ def test_encoder_gradients_match_autograd():
 def test_encoder_gradients_full_geometry():
     from hypervla.config import FULL
     _encoder_case(FULL, 1, 3e-3)
+
+
+@pytest.mark.timeout(1200)
+@pytest.mark.parametrize("B,layers", [(8, 2), (32, 1)])
+def test_encoder_gradients_where_the_large_batch_kernels_run(B, layers):
+    """DINOv2-base widths, few layers, against float64 autograd -- at row counts where block_bwd selects the kernels that exist for large
+    batches (rows = B x 257):
+      B = 8, 2 layers   2 056 rows: colsum4b_kernel (rows >= 2048, N = 768 and 3 072), ls_bwd4_kernel (rows >= 1024), ln_bwd_shared_kernel,
+                        launcher-chosen split-K on every shared weight gradient, the one-launch QKV products
+      B = 32, 1 layer   8 224 rows: also the 256 x 128 GEMM tile for the N = 768 products and the column-sum tail 8 224 = 64 x 128 + 32
+    (DESIGN.md section 9 has the kernel names of a trace of the B = 32 case).  Tolerance: the full-width figure of _encoder_case, 3e-3.
+    The bias / LayerScale / LayerNorm leaves of the encoder layers are also held PER ELEMENT against the leaf's RMS: at most twice what
+    the B = 1 run of the same geometry (the small-row kernels, oracle-checked by test_encoder_gradients_full_geometry) shows."""
+    from hypervla.config import Geometry
+    g = Geometry(enc_layers=layers)
+    small, big = {}, {}
+    _encoder_case(g, 1, 3e-3, stats=small)
+    _encoder_case(g, B, 3e-3, stats=big)
+    mx_small, mx_big = small.pop("__max_metric__"), big.pop("__max_metric__")
+    assert set(small) == set(big) and len(big) >= 10 * layers, (len(small), len(big))
+    # leaf by leaf; the floor (a tenth of the worst B = 1 leaf) keeps a leaf that happens to be almost exact at B = 1 from setting an
+    # unreachable bound for itself, and is still an order of magnitude below what a lost column group or row block would cost
+    floor = 0.1 * max(small.values())
+    ratio = {k: big[k] / max(small[k], floor) for k in big}
+    kw = max(ratio, key=ratio.get)
+    print(f"layers {layers}: max-metric B = 1 {mx_small}, B = {B} {mx_big}; per element / leaf RMS over {len(big)} bias / LayerScale / norm leaves: "
+          f"worst B = 1 {max(small.values()):.3e}, worst B = {B} {max(big.values()):.3e}; worst leaf ratio B = {B} / B = 1: {ratio[kw]:.2f} at {kw} "
+          f"({big[kw]:.3e} / {small[kw]:.3e})")
+    for k in sorted(big):
+        print(f"    {k}: B = 1 {small[k]:.3e}  B = {B} {big[k]:.3e}")
+    bad = {k: (big[k], small[k]) for k in big if big[k] > 2 * max(small[k], floor)}
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("strategy", ["v5", "v1"])
@@ -507,3 +552,109 @@ def test_bucketed_all_reduce_path_on_one_rank(tmp_path):
         assert float(((ft.params - ref.params).abs() > 1e-5).float().mean()) < 1e-2
     finally:
         dist.destroy_process_group()
+
+
+# ------------------------------------------------------------------ AdamW past its first update
+@pytest.mark.parametrize("case", ["frozen", "encoder", "frozen-unclipped", "frozen-clipped"])
+def test_adamw_six_updates_against_the_optax_chain(setup, case):
+    """Six consecutive forward_backward + apply with the gradients the device produced; before each apply params / mu / nu / ema /
+    grads are read back and after it the state is compared with a float64 restatement of ONE optax step from that read-back state (a
+    bf16 tie in mu cannot propagate).  `frozen`: adamw_kernel; `encoder`: train_encoder=True with base_weight_decay > 0, i.e.
+    adamw_shared_kernel with the v5 mask and the pull towards the pretrained leaves; `frozen-unclipped`: FineTuner(clip=1e6), the
+    norm < clip branch; `frozen-clipped`: clip = 1e-2, the other branch whatever the gradient norm of the fixture is.
+
+    params  atol 2e-6 at lr = 1e-3 (the first-step test's figure)
+    nu      rtol 1e-6 with the clip scale taken from the device's own sqsum (f32 sqrt and division restated in numpy f32, both
+            correctly rounded): given the scale, nu is three f32 roundings away from float64
+    sqsum   against float64 sum(g^2): all terms positive, so the relative error is at most (additions on the longest chain + the
+            square's rounding) x 2^-24; sqsum_kernel runs 1024 x 256 threads, a thread adds ceil(n / 262144) terms, a wave 6 shuffle
+            steps, and the 4096 waves one atomic each into the same word
+    mu      bf16(m), or its bf16 neighbour where m lies within the device's f32 roundings (2^-24 relative each: g sc, (1 - b1) x,
+            b1 mu, the sum) of a tie.  A deliberate departure from a single 2^-24 |m| band: the kernel forms m with four f32
+            roundings (fewer if the compiler contracts into an fma), so a one-rounding band rejects a correct kernel.  The band is
+            2^-24 (|m| + |b1 mu| + 2 |(1 - b1) g sc|), about 3 - 5 x 2^-24 |m|; bf16 ties are 2^-8 |m| apart at the least, so the
+            share of elements that may sit at the neighbour is about 2 x band / 2^-8 = 1e-4 -- the 1e-3 cap below is ten times
+            that, and a wrong rounding mode (half of all elements at a neighbour) cannot hide under it
+    ema     as the first-step test
+    From the second update on the device must tell t from t - 1: the parameters expected with t - 1 in the bias corrections are at
+    least 10 x the tolerance further from the device's than those with t (not vacuous: fails if lr made the two indistinguishable)."""
+    from hypervla.train import FineTuner
+    s = setup
+    enc = case == "encoder"
+    kw = dict(ema_start_step=0)
+    if enc:
+        kw.update(train_encoder=True, base_weight_decay=0.01)
+    if case == "frozen-unclipped":
+        kw.update(clip=1e6)
+    if case == "frozen-clipped":
+        kw.update(clip=1e-2)
+    ft = FineTuner(s["model"], s["B"], **kw)
+    obs = s["im"] if enc else s["tok"].astype(np.float32)
+    lr, blr, tol = 1e-3, 1e-3, 2e-6
+    hy = dict(ft.hy, lr=lr, base_lr=blr)
+    nh, n = ft.n_hyper, ft.n
+    assert (n > nh) == enc
+    chain = -(-n // (1024 * 256)) + 6 + 1024 * 256 // 64 + 1
+    r64 = lambda x: x.float().cpu().numpy().astype(np.float64)
+    worst = dict(p=0.0, nu=0.0, sq=0.0, ties=0.0, gap=np.inf)
+    for it in range(6):
+        ft.forward_backward(s["ins"], s["st"], obs, s["batch"])
+        st = dict(p=r64(ft.params), mu=r64(ft.mu), nu=r64(ft.nu), ema=r64(ft.ema), g=r64(ft.grads), mask=ft.wd_mask.cpu().numpy(),
+                  p0=r64(ft.params0) if ft.params0 is not None else None)
+        assert ft.step_count == it
+        assert ft.apply(lr=lr, base_lr=blr) is True
+        t = it + 1
+        sq_dev = np.float32(ft.sqsum.cpu().numpy()[0])
+        sq64 = float((st["g"] * st["g"]).sum())
+        rel_sq = abs(float(sq_dev) - sq64) / sq64
+        norm32 = np.sqrt(sq_dev)
+        clip32 = np.float32(hy["clip"])
+        sc = 1.0 if norm32 < clip32 else float(clip32 / norm32)
+        if case == "frozen-unclipped":
+            assert sc == 1.0
+        if case == "frozen-clipped":
+            assert sc < 1.0
+        want = _optax_step(st, hy, t, sc, nh)
+        got_p, got_mu, got_nu, got_ema = r64(ft.params), r64(ft.mu), r64(ft.nu), r64(ft.ema)
+        dp = np.abs(got_p - want["p"]).max()
+        dnu = (np.abs(got_nu - want["nu"]) / np.maximum(np.abs(want["nu"]), 1e-31)).max()
+        lo, hi = _bf16_round(want["m"] - want["band"]), _bf16_round(want["m"] + want["band"])
+        exact = got_mu == _bf16_round(want["m"])
+        within = (got_mu >= np.minimum(lo, hi)) & (got_mu <= np.maximum(lo, hi))
+        print(f"{case} update {t}: clip scale {sc:.4g}; params max |d| {dp:.2e}; nu max rel {dnu:.2e}; sqsum rel {rel_sq:.2e} (bound {chain * 2.0 ** -24:.2e}); "
+              f"mu at a neighbour of bf16(m): {int((~exact).sum())} of {n}, outside the tie band: {int((~within).sum())}")
+        assert rel_sq <= chain * 2.0 ** -24, (t, rel_sq)
+        np.testing.assert_allclose(got_p, want["p"], rtol=0, atol=tol)
+        np.testing.assert_allclose(got_nu, want["nu"], rtol=1e-6, atol=1e-37)
+        assert within.all() and (~exact).mean() <= 1e-3, (t, int((~within).sum()), int((~exact).sum()))
+        np.testing.assert_allclose(got_ema, want["ema"], rtol=0, atol=tol)
+        if t > 1:
+            prev = _optax_step(st, hy, t - 1, sc, nh)
+            for sl in ([slice(0, nh)] + ([slice(nh, n)] if enc else [])):
+                gap = np.abs(got_p[sl] - prev["p"][sl]).max() - np.abs(got_p[sl] - want["p"][sl]).max()
+                worst["gap"] = min(worst["gap"], gap)
+                assert gap >= 10 * tol, (t, sl, gap)
+        worst.update(p=max(worst["p"], dp), nu=max(worst["nu"], dnu), sq=max(worst["sq"], rel_sq), ties=max(worst["ties"], float((~exact).mean())))
+    print(case, "worst over six updates:", worst)
+
+
+def test_default_schedule_starts_at_zero(setup):
+    """FineTuner.apply() without lr uses lr_rsqrt(step_count, peak): 0 at the first update -- nothing moves, bit for bit, although mu and
+    nu are written -- and peak / warmup at the second."""
+    from hypervla.train import FineTuner, lr_rsqrt
+    s = setup
+    ft = FineTuner(s["model"], s["B"])
+    seen = []
+    hyper = ft._hyper
+    ft._hyper = lambda lr, *a, **k: (seen.append(lr), hyper(lr, *a, **k))[1]
+    ft.forward_backward(s["ins"], s["st"], s["tok"].astype(np.float32), s["batch"])
+    p0 = ft.params.clone()
+    assert ft.apply() is True and ft.step_count == 1
+    assert seen[-1] == lr_rsqrt(0, ft.peak_lr) == 0.0
+    assert torch.equal(ft.params, p0) and float(ft.nu.abs().max()) > 0
+    ft.forward_backward(s["ins"], s["st"], s["tok"].astype(np.float32), s["batch"])
+    ft.apply()
+    lr1 = lr_rsqrt(1, ft.peak_lr)
+    assert seen[-1] == lr1 == ft.peak_lr / 2000
+    moved = float((ft.params - p0).abs().max())
+    assert 0 < moved <= 10 * lr1, (moved, lr1)

@@ -278,3 +278,20 @@ def test_bench_names_the_kernel_symbols_the_committed_profile_lists():
     assert "OpBF16" in bench.big_gemm_symbols(256, FULL, "bf16")["qkv_gemm"][0]
     assert bench.big_gemm_symbols(128, FULL, "f16")["out_gemm"][0].endswith("3, false, true, true>(hvla::GemmArgs)")
     assert bench.big_gemm_symbols(256, SMALL_E, "f16") is not None
+
+
+def test_lr_rsqrt_schedule_points():
+    """octo/utils/train_utils.py:212-225 ("rsqrt"): linear warm-up from `init` to `peak` over `warmup` updates, then
+    peak / sqrt((s + timescale) / timescale) with s counted from the end of the warm-up -- FineTuner.apply's default schedule."""
+    from hypervla.train import lr_rsqrt
+    peak, warmup, ts = 3e-4, 2000, 10000
+    assert lr_rsqrt(0, peak) == 0.0
+    assert lr_rsqrt(1, peak) == pytest.approx(peak / warmup, rel=1e-12)
+    assert lr_rsqrt(warmup - 1, peak) == pytest.approx(peak * (warmup - 1) / warmup, rel=1e-12)
+    assert lr_rsqrt(warmup, peak) == pytest.approx(peak, rel=1e-12)
+    assert lr_rsqrt(warmup + ts, peak) == pytest.approx(peak / 2 ** 0.5, rel=1e-12)
+    assert lr_rsqrt(warmup + 3 * ts, peak) == pytest.approx(peak / 2, rel=1e-12)
+    # continuous at the joint, increasing before it and decreasing after it; the other arguments are honoured
+    assert lr_rsqrt(warmup - 1, peak) < lr_rsqrt(warmup, peak) > lr_rsqrt(warmup + 1, peak)
+    assert lr_rsqrt(0, peak, init=1e-5) == 1e-5 and lr_rsqrt(50, peak, warmup=100, init=1e-4) == pytest.approx(2e-4, rel=1e-12)
+    assert lr_rsqrt(100 + 300, 1.0, warmup=100, timescale=100) == pytest.approx(0.5, rel=1e-12)
