@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "layout.h"
 #include "pack.h"
+#include "publish_map.h"
 #include "t5.h"
 #include "train.h"
 
@@ -938,6 +939,33 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
   HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int32_t train_encoder, void* stream) {
+  if (!ctx) return HVLA_E_STATE;
+  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "hvla_train_publish before hvla_load_weights");
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
+  if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
+  if (!params) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  const Geom& g = ctx->g;
+  const TrainLayout L = make_train_layout(g);
+  const int64_t want = L.total + (train_encoder ? L.enc_total : 0);
+  if (n_params != want) FAIL(ctx, HVLA_E_SHAPE, "n_params %lld, the training vector has %lld", (long long)n_params, (long long)want);
+  // the tables restate hvla_load_weights' order: a buffer of another size means they do not describe this context
+  const PolicyLayout& pl = ctx->lay.pl;
+  const int Gtot = pl.Gm + pl.Gv;
+  const pubmap::EncMap em = pubmap::enc_map(g, L);
+  if (pubmap::ctx_table(g, L).dst_total * 4 != (int64_t)ctx->hn_f32.bytes || (size_t)Gtot * 4 != ctx->bcat.bytes ||
+      (size_t)(Gtot / 32) * (g.C / 16) * 1024 != ctx->wcat_hi.bytes || em.n16 * 2 != (int64_t)ctx->enc16.bytes ||
+      em.vec.dst_total * 4 != (int64_t)ctx->encf32.bytes || em.Kp != ctx->Kp || g.E % pubmap::TR_TILE || g.enc_mlp % pubmap::TR_TILE)
+    FAIL(ctx, HVLA_E_STATE, "the publish tables do not match this context's buffers");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  PublishArgs a{g, params, ctx->hn_f32.as<float>(), ctx->perm.as<int32_t>(), ctx->wcat_hi.as<uint16_t>(), ctx->wcat_lo.as<uint16_t>(),
+                ctx->bcat.as<float>(), Gtot, ctx->enc16.as<uint16_t>(), ctx->encd16.as<uint16_t>(), ctx->encf32.as<float>(),
+                ctx->cfg.enc_dtype == HVLA_ENC_BF16, train_encoder != 0};
+  ctx->prof.nlaunch += train_encoder ? 6 : 2;
+  HIPCHK(ctx, launch_publish(a, reinterpret_cast<hipStream_t>(stream)));
   return HVLA_OK;
 }
 

@@ -188,6 +188,22 @@ hipError_t launch_loss(const float* actions, const float* logits, const float* t
                        const uint8_t* amask, float* loss, int B, int horizon, int action_dim, float max_action,
                        bool clip_target, hipStream_t st);
 
+// ---------------------------------------------------------------- publish (publish.hip, include/hvla.h hvla_train_publish)
+// the flat training vector `params` into the serving buffers; the encoder's three only with train_encoder
+struct PublishArgs {
+  Geom g;
+  const float* params;
+  float* hn;
+  const int32_t* perm;
+  uint16_t *wcat_hi, *wcat_lo;
+  float* bcat;
+  int Gtot;                     // Gm + Gv, packed positions
+  uint16_t *enc16, *encd16;
+  float* encf32;
+  int bf, train_encoder;
+};
+hipError_t launch_publish(const PublishArgs& a, hipStream_t st);
+
 // ---------------------------------------------------------------- self test
 hipError_t launch_selftest(int* fail_flags, hipStream_t st);
 hipError_t run_box_probe(float* sink, unsigned long long* ticks, float out[3], hipStream_t st);   // selftest.hip: sustained clock / MFMA rate of this box

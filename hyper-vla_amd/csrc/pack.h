@@ -1,5 +1,6 @@
 // pack.h — host-only packing of checkpoint tensors into the device layouts (used by api.hip; no HIP types, so that
-// tests/native/pack_asan.cpp can run it under -fsanitize=address,undefined on the CPU).
+// tests/native/pack_asan.cpp can run it under -fsanitize=address,undefined on the CPU).  The rounding functions are also the
+// device's (publish.hip): HVLA_HD is `__host__ __device__` under hipcc and empty for a host compiler, so one text serves both.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -8,23 +9,29 @@
 
 #include "layout.h"
 
+#if defined(__HIPCC__)
+#define HVLA_HD __host__ __device__
+#else
+#define HVLA_HD
+#endif
+
 namespace hvla {
 namespace pack {
 
-inline uint16_t f2bf(float f) {          // round-to-nearest-even, NaN preserved
+HVLA_HD inline uint16_t f2bf(float f) {          // round-to-nearest-even, NaN preserved
   uint32_t u;
   memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-inline float bf2f(uint16_t h) {
+HVLA_HD inline float bf2f(uint16_t h) {
   uint32_t u = (uint32_t)h << 16;
   float f;
   memcpy(&f, &u, 4);
   return f;
 }
 // IEEE binary16, round-to-nearest-even, subnormals kept, overflow to infinity (== the hardware conversion)
-inline uint16_t f2h(float f) {
+HVLA_HD inline uint16_t f2h(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
   const uint32_t sign = (u >> 16) & 0x8000u;
@@ -41,7 +48,7 @@ inline uint16_t f2h(float f) {
   const uint32_t v = u - 0x38000000u;                                // rebias 127 -> 15
   return (uint16_t)(sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13));
 }
-inline float h2f(uint16_t h) {
+HVLA_HD inline float h2f(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
   uint32_t u;
   if (e == 0) {
@@ -58,8 +65,8 @@ inline float h2f(uint16_t h) {
   memcpy(&f, &u, 4);
   return f;
 }
-inline uint16_t to16(float f, bool bf) { return bf ? f2bf(f) : f2h(f); }
-inline float from16(uint16_t h, bool bf) { return bf ? bf2f(h) : h2f(h); }
+HVLA_HD inline uint16_t to16(float f, bool bf) { return bf ? f2bf(f) : f2h(f); }
+HVLA_HD inline float from16(uint16_t h, bool bf) { return bf ? bf2f(h) : h2f(h); }
 
 // W_cat^T as MFMA A fragments (layout.h): tile pt, k-step ks, lane (rho = l & 31, hk = l >> 5), j; hi / lo bf16 planes, and
 // b_cat in packed order.  lk[i] / lb[i]: kernel [C][size_i] / bias [size_i] of generated leaf i.

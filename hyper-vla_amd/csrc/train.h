@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "layout.h"
+#include "train_layout.h"
 
 namespace hvla {
 
@@ -31,16 +32,6 @@ void train_gemm_timer(bool on, bool first_use_by_this_context);                 
 void train_gemm_timer_release();                                                 // hvla_destroy of a context that used it: the events go with the last user
 hipError_t train_gemm_timer_read(float* ms, double* flops, int* launches);      // since the last read
 
-// flat layout of the trainable hypernetwork parameters (float32 elements)
-// `total` = the hypernetwork's own parameters; the shared DINOv2 leaves follow at [total, total + enc_total) when the
-// image encoder is trained too (`fine_tune_pretrained_image_encoder=True`), in hypervla.config.encoder_leaves order.
-struct TrainLayout {
-  long w_tok, b_tok, w_img, b_img, pos_tok, pos_img, pos_layer, norm_s, norm_b, wcat, bcat, total, G;
-  struct CL { long ln0_s, ln0_b, ln1_s, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, w1, b1, w2, b2; } layer[8];
-  long e_cls, e_mask, e_pb, e_pk, e_pos, e_lnb, e_lns, enc_total;
-  struct EL { long kb, kk, qb, qk, vb, vk, ob, ok, ls1, ls2, f1b, f1k, f2b, f2k, n1b, n1s, n2b, n2s; } enc[24];
-};
-TrainLayout make_train_layout(const Geom& g);
 #ifdef HVLA_BENCH_HOOKS
 void set_train_gemm_exact(bool on);
 // what the last bgemm() launch of this process chose (hvla_debug_bgemm_once reports it; tools/bgemm_check.py): tile = 64 / 128 / 256 rows

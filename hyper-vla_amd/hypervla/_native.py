@@ -25,7 +25,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
-           "hvla_create_with"]
+           "hvla_create_with", "hvla_train_publish"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -145,6 +145,8 @@ def load_library():
     lib.hvla_train_apply.argtypes = [vp, C.POINTER(hvla_train_buffers), C.POINTER(hvla_train_hyper), vp]
     lib.hvla_train_accumulate.argtypes = [vp, C.POINTER(hvla_train_buffers), vp, C.c_float, C.POINTER(hvla_train_hyper), vp]
     lib.hvla_train_accumulate.restype = C.c_int
+    lib.hvla_train_publish.argtypes = [vp, vp, i64, i32, vp]
+    lib.hvla_train_publish.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -370,6 +372,11 @@ class Context:
     def train_accumulate(self, buf, acc_ptr, inv_k, hyper, stream=0):
         self._check(self.lib.hvla_train_accumulate(self.h, C.byref(buf), C.c_void_p(acc_ptr), C.c_float(inv_k), C.byref(hyper),
                                                    C.c_void_p(stream)), "hvla_train_accumulate")
+
+    def train_publish(self, params_ptr, n_params, train_encoder=False, stream=0):
+        """Pack the flat training vector at `params_ptr` (device f32 [n_params]) into this context's serving buffers, in place."""
+        self._check(self.lib.hvla_train_publish(self.h, C.c_void_p(params_ptr or None), int(n_params), int(bool(train_encoder)),
+                                                C.c_void_p(stream)), "hvla_train_publish")
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

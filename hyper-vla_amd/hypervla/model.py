@@ -104,6 +104,19 @@ class HyperVLA:
             raise ValueError(f"checkpoint is missing {len(missing)} tensors, e.g. {missing[:3]}")
         self._ctx.load_weights({k: params[k] for k in want})
 
+    @property
+    def params(self) -> Dict[str, np.ndarray]:
+        """The host tensors of the weights being served.  After `FineTuner.publish(host_copy=False)` the device serves weights
+        the host has no copy of: reading them (and `save_pretrained`) raises until a `publish(host_copy=True)`."""
+        if self._params_stale:
+            raise RuntimeError("the device serves weights published without a host copy (FineTuner.publish(host_copy=False)): "
+                               "model.params would be stale; call publish(host_copy=True) first")
+        return self._params
+
+    @params.setter
+    def params(self, value: Dict[str, np.ndarray]) -> None:
+        self._params, self._params_stale = value, False
+
     def release_pooled_arenas(self) -> None:
         """Free the generated-weight arenas that freed `GeneratedWeights` parked for re-use (hvla_release_pooled_arenas:
         up to four per context, about 0.8 MB per episode each).  `create_tasks` allocates again when it next needs one."""

@@ -325,3 +325,27 @@ class FineTuner:
         loss = self.forward_backward(instruction_dict, initial_state, obs, batch)
         self.apply(lr, base_lr)
         return loss.mean()
+
+    def publish(self, ema: bool = False, host_copy: bool = True, audit: bool = False):
+        """Serve the fine-tuned weights in place (`hvla_train_publish`): the parameters, or with `ema` their moving average
+        (the reference evaluates `model.replace(params=ema)`, data/simpler/evaluate.py:440-444), are packed on the device into
+        the buffers the model's context serves from, on the model's stream.  The context stays the one it was: its language
+        encoder, pooled arenas, `GeneratedWeights` and captured graphs remain valid; weights generated earlier keep their
+        values, `create_tasks` / `assign_tasks` from now on use the new ones.  The image encoder is rewritten only when this
+        FineTuner trains it.
+
+        `host_copy=True` also replaces `model.params` by the published tensors (encoder leaves that were not trained are
+        kept), so that `save_pretrained` writes what is being served.  With `host_copy=False` nothing leaves the device and
+        `model.params` / `save_pretrained` raise until a later `publish(host_copy=True)`.
+        `audit=True` runs `model.audit_operand_range()` afterwards: a trained encoder is where fp16 operands can leave their
+        range; it returns that audit's result, otherwise None."""
+        m = self.model
+        vec = self.ema if ema else self.params
+        m._ctx.train_publish(vec.data_ptr(), self.n, self.train_encoder, m._stream())
+        if host_copy:
+            new = dict(m._params)
+            new.update(unpack_params(self.g, vec.cpu().numpy(), self.train_encoder))
+            m.params = new
+        else:
+            m._params_stale = True
+        return m.audit_operand_range() if audit else None

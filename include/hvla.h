@@ -324,6 +324,18 @@ int hvla_train_profile_read(hvla_ctx* ctx, float* gemm_ms, double* gemm_flops, i
  * After k micro-steps the caller runs hvla_train_apply with `grads` pointing at acc and hyper.clip = +inf.        */
 int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* acc, float inv_k,
                           const hvla_train_hyper* hyper, void* stream);
+/* Replaces: `model.replace(params=ema)` between fine-tuning and evaluation (data/simpler/evaluate.py:440-444), without the
+ * host: `params` (DEVICE, f32 [n_params] in the flat training order; the parameters and the EMA are both such vectors) is
+ * packed in place into every device buffer hvla_load_weights fills -- the context encoder, the W_cat hi / lo fragment planes
+ * and b_cat, and with train_encoder != 0 the image encoder's 16-bit matrices, rounding residues and f32 vectors (enc_dtype
+ * honoured).  The bytes are those hvla_load_weights writes for the same tensors; with train_encoder == 0 the image encoder's
+ * buffers are not touched.  Allocates nothing, does not synchronise with the host, launches only on `stream`; no buffer address
+ * changes, so the context's arenas, pools and captured graphs stay valid and read the new weights from their next launch on.
+ * Weights generated earlier (hvla_generate) keep their values: they were generated already.  Ordering against work of this
+ * context on OTHER streams (a step in flight, a second stream of cfg.streams == 2 is joined by hvla_step itself) is the
+ * caller's.  Refused before any launch: not loaded -> HVLA_E_STATE; n_params != hvla_train_sizes(...)[0] for that flag, NULL
+ * params, or a use_language_token geometry -> HVLA_E_SHAPE.                                                                 */
+int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int32_t train_encoder, void* stream);
 
 /* Replaces: InferenceWrapper._resize_image (data/utils/hypervla_interface.py:89-121): optionally
  * tf.image.resize_with_pad(image, 256, 320) (bilinear, zero padding; `padded_resize`), then
