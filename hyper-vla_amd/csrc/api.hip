@@ -15,7 +15,7 @@
 #include "kernels.h"
 #include "layout.h"
 #include "pack.h"
-#include "publish_map.h"
+#include "serving_layout.h"
 #include "t5.h"
 #include "train.h"
 
@@ -163,7 +163,7 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
   if (ctx_encoder_lds_bytes(c->lang_tokens, c->ctx_dim, c->ctx_mlp, c->enc_dim) > 160 * 1024) return HVLA_E_SHAPE;
   if (hipSetDevice(device) != hipSuccess) return HVLA_E_DEVICE;
   ctx->lay = build_layout(g);
-  ctx->Kp = 2 * ((g.patch * g.patch * 3 + 63) / 64 * 64);     // [W_hi | W_lo] along K (encoder.hip)
+  ctx->Kp = serving::patch_kp(g);
   {  // the packed order must be a bijection onto the reference parameter vector
     std::vector<uint8_t> seen(ctx->lay.pl.G, 0);
     for (int32_t r : ctx->lay.perm)
@@ -218,196 +218,62 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
     if (!t[i].name || !t[i].data) FAIL(ctx, HVLA_E_WEIGHTS, "tensor %d has null name/data", i);
     m[t[i].name] = &t[i];
   }
-  const char* missing = nullptr;
-  std::string missing_s;
-  auto get = [&](const std::string& name, int64_t numel) -> const float* {
+  // ---- pack on the host: the order, the names and the arithmetic are serving_layout.h's
+  serving::HostImages h;
+  auto lookup = [&](const std::string& name) {
     auto it = m.find(name);
-    if (it == m.end() || it->second->numel != numel) {
-      if (!missing) {
-        missing_s = name + (it == m.end() ? " (absent)" : " (wrong size)");
-        missing = missing_s.c_str();
-      }
-      return nullptr;
-    }
-    return it->second->data;
+    using R = std::pair<const float*, int64_t>;
+    return it == m.end() ? R{nullptr, 0} : R{it->second->data, it->second->numel};
   };
-  const int C = g.C, Hc = g.ctx_heads, F = g.ctx_mlp, T = g.T, E = g.E;
-  // ------------------------------------------------------------ context encoder (f32, natural layout)
-  std::vector<float> hn;
-  std::vector<std::pair<const float**, size_t>> fix;     // pointer slot -> offset
-  auto push = [&](const float** slot, const std::string& name, int64_t numel) {
-    const float* src = get(name, numel);
-    const size_t off = hn.size();
-    hn.resize(off + ((numel + 3) / 4) * 4, 0.f);
-    if (src) memcpy(hn.data() + off, src, numel * 4);
-    fix.push_back({slot, off});
+  if (!serving::pack_serving(g, ctx->cfg.enc_dtype == HVLA_ENC_BF16, lookup, h))
+    FAIL(ctx, HVLA_E_WEIGHTS, "checkpoint tensor %s", h.missing.c_str());
+  // W_cat^T fragments (layout.h): tile pt, k-step ks, lane (rho = l & 31, hk = l >> 5), j
+  std::vector<uint16_t> hi, lo;
+  std::vector<float> bc;
+  pack::pack_wcat(ctx->lay, h.leaves, h.lk, h.lb, g.C, hi, lo, bc);
+
+  // ---- upload
+  auto up = [&](DevBuf& b, const void* src, size_t bytes) {
+    const hipError_t e = b.alloc(bytes);
+    return e != hipSuccess ? e : hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
   };
+  HIPCHK(ctx, up(ctx->hn_f32, h.hn.data(), h.hn.size() * 4));
+  HIPCHK(ctx, up(ctx->wcat_hi, hi.data(), hi.size() * 2));
+  HIPCHK(ctx, up(ctx->wcat_lo, lo.data(), lo.size() * 2));
+  HIPCHK(ctx, up(ctx->bcat, bc.data(), bc.size() * 4));
+  HIPCHK(ctx, up(ctx->perm, ctx->lay.perm.data(), ctx->lay.perm.size() * 4));
+  HIPCHK(ctx, up(ctx->enc16, h.enc16.data(), h.enc16.size() * 2));
+  HIPCHK(ctx, up(ctx->encd16, h.encd16.data(), h.encd16.size() * 2));
+  HIPCHK(ctx, up(ctx->encf32, h.encf.data(), h.encf.size() * 4));
+
+  // ---- the kernels' pointers, each from the offset of the tensor it names (q / k / v lie one behind the other: one pointer)
+  const serving::Offsets& at = h.at;
+  const float* hn = ctx->hn_f32.as<float>();
   CtxParams& cp = ctx->ctxp;
   cp = CtxParams{};
-  cp.T = T; cp.C = C; cp.F = F; cp.heads = Hc; cp.layers = g.ctx_layers; cp.lang_dim = g.lang_dim; cp.E = E;
+  cp.T = g.T; cp.C = g.C; cp.F = g.ctx_mlp; cp.heads = g.ctx_heads; cp.layers = g.ctx_layers; cp.lang_dim = g.lang_dim; cp.E = g.E;
   cp.scale_context = g.scale_context;
-  push(&cp.w_tok, "task_token_projection/kernel", (int64_t)g.lang_dim * C);
-  push(&cp.b_tok, "task_token_projection/bias", C);
-  push(&cp.w_img, "initial_image_projection/kernel", (int64_t)E * C);
-  push(&cp.b_img, "initial_image_projection/bias", C);
-  push(&cp.pos_tok, "task_pos_embedding", (int64_t)T * C);
-  push(&cp.pos_img, "initial_image_pos_embedding", C);
-  push(&cp.pos_layer, "layer_pos_embedding", C);
-  push(&cp.norm_s, "Transformer_0/encoder_norm/scale", C);
-  push(&cp.norm_b, "Transformer_0/encoder_norm/bias", C);
+#define HN(to, from, f) to.f = hn + from.f           // the context encoder's pointers carry the names of TrainLayout's members
+  HN(cp, at, w_tok); HN(cp, at, b_tok); HN(cp, at, w_img); HN(cp, at, b_img); HN(cp, at, pos_tok); HN(cp, at, pos_img);
+  HN(cp, at, pos_layer); HN(cp, at, norm_s); HN(cp, at, norm_b);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    const std::string b = "Transformer_0/encoderblock_" + std::to_string(l) + "/";
-    const std::string a = b + "MultiHeadDotProductAttention_0/";
-    CtxLayer& L = cp.layer[l];
-    push(&L.ln0_s, b + "LayerNorm_0/scale", C); push(&L.ln0_b, b + "LayerNorm_0/bias", C);
-    push(&L.wq, a + "query/kernel", (int64_t)C * C); push(&L.bq, a + "query/bias", C);
-    push(&L.wk, a + "key/kernel", (int64_t)C * C); push(&L.bk, a + "key/bias", C);
-    push(&L.wv, a + "value/kernel", (int64_t)C * C); push(&L.bv, a + "value/bias", C);
-    push(&L.wo, a + "out/kernel", (int64_t)C * C); push(&L.bo, a + "out/bias", C);
-    push(&L.ln1_s, b + "LayerNorm_1/scale", C); push(&L.ln1_b, b + "LayerNorm_1/bias", C);
-    push(&L.w1, b + "MlpBlock_0/Dense_0/kernel", (int64_t)C * F); push(&L.b1, b + "MlpBlock_0/Dense_0/bias", F);
-    push(&L.w2, b + "MlpBlock_0/Dense_1/kernel", (int64_t)F * C); push(&L.b2, b + "MlpBlock_0/Dense_1/bias", C);
+    const TrainLayout::CL& o = at.layer[l];
+    CtxLayer& c = cp.layer[l];
+    HN(c, o, ln0_s); HN(c, o, ln0_b); HN(c, o, wq); HN(c, o, bq); HN(c, o, wk); HN(c, o, bk); HN(c, o, wv); HN(c, o, bv);
+    HN(c, o, wo); HN(c, o, bo); HN(c, o, ln1_s); HN(c, o, ln1_b); HN(c, o, w1); HN(c, o, b1); HN(c, o, w2); HN(c, o, b2);
   }
-  // ------------------------------------------------------------ W_cat / b_cat in packed order
-  const PolicyLayout& pl = ctx->lay.pl;
-  const int Gtot = pl.Gm + pl.Gv;
-  auto leaves = generated_leaves(g);
-  std::vector<const float*> lk(leaves.size()), lb(leaves.size());
-  for (size_t i = 0; i < leaves.size(); ++i) {
-    lk[i] = get("output_head_" + leaves[i].flat + "/kernel", (int64_t)C * leaves[i].size);
-    lb[i] = get("output_head_" + leaves[i].flat + "/bias", leaves[i].size);
-  }
-  // ------------------------------------------------------------ DINOv2 (shared leaves, flat vectors)
-  const std::string ep = "encoder_image_encoder_";
-  const int Fe = g.enc_mlp, p = g.patch, S = g.S(), Kp = ctx->Kp, Kreal = p * p * 3;
-  const float* e_cls = get(ep + "embeddings_cls_token", E);
-  (void)get(ep + "embeddings_mask_token", E);
-  const float* e_pk = get(ep + "embeddings_patch_embeddings_projection_kernel", (int64_t)Kreal * E);
-  const float* e_pb = get(ep + "embeddings_patch_embeddings_projection_bias", E);
-  const float* e_pos = get(ep + "embeddings_position_embeddings", (int64_t)S * E);
-  const float* e_lns = get(ep + "layernorm_scale", E);
-  const float* e_lnb = get(ep + "layernorm_bias", E);
-  struct LSrc { const float *q, *qb, *k, *kb, *v, *vb, *o, *ob, *l1, *l2, *f1, *f1b, *f2, *f2b, *n1s, *n1b, *n2s, *n2b; };
-  std::vector<LSrc> ls(g.enc_layers);
+#undef HN
+  const uint16_t *e16 = ctx->enc16.as<uint16_t>(), *dd = ctx->encd16.as<uint16_t>();
+  const float* df = ctx->encf32.as<float>();
+  EncWeights& w = ctx->encw;
+  w.w_patch = e16 + at.e_pk; w.b_patch = df + at.e_pb; w.pos = df + at.e_pos; w.lnf_s = df + at.e_lns; w.lnf_b = df + at.e_lnb;
   for (int i = 0; i < g.enc_layers; ++i) {
-    const std::string L = ep + "encoder_layer_" + std::to_string(i) + "_";
-    LSrc& s = ls[i];
-    s.q = get(L + "attention_attention_query_kernel", (int64_t)E * E); s.qb = get(L + "attention_attention_query_bias", E);
-    s.k = get(L + "attention_attention_key_kernel", (int64_t)E * E); s.kb = get(L + "attention_attention_key_bias", E);
-    s.v = get(L + "attention_attention_value_kernel", (int64_t)E * E); s.vb = get(L + "attention_attention_value_bias", E);
-    s.o = get(L + "attention_output_dense_kernel", (int64_t)E * E); s.ob = get(L + "attention_output_dense_bias", E);
-    s.l1 = get(L + "layer_scale1_lambda1", E); s.l2 = get(L + "layer_scale2_lambda1", E);
-    s.f1 = get(L + "mlp_fc1_kernel", (int64_t)E * Fe); s.f1b = get(L + "mlp_fc1_bias", Fe);
-    s.f2 = get(L + "mlp_fc2_kernel", (int64_t)Fe * E); s.f2b = get(L + "mlp_fc2_bias", E);
-    s.n1s = get(L + "norm1_scale", E); s.n1b = get(L + "norm1_bias", E);
-    s.n2s = get(L + "norm2_scale", E); s.n2b = get(L + "norm2_bias", E);
-  }
-  if (missing) FAIL(ctx, HVLA_E_WEIGHTS, "checkpoint tensor %s", missing);
-
-  // ---- upload the context encoder
-  HIPCHK(ctx, ctx->hn_f32.alloc(hn.size() * 4));
-  HIPCHK(ctx, hipMemcpy(ctx->hn_f32.p, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
-  for (auto& f : fix) *f.first = ctx->hn_f32.as<float>() + f.second;
-
-  // ---- pack W_cat^T fragments (layout.h): tile pt, k-step ks, lane (rho = l & 31, hk = l >> 5), j
-  {
-    std::vector<uint16_t> hi, lo;
-    std::vector<float> bc;
-    for (size_t i = 0; i < leaves.size(); ++i)
-      if (!lk[i] || !lb[i]) FAIL(ctx, HVLA_E_WEIGHTS, "output head %s missing", leaves[i].flat.c_str());
-    pack::pack_wcat(ctx->lay, leaves, lk, lb, C, hi, lo, bc);
-    HIPCHK(ctx, ctx->wcat_hi.alloc(hi.size() * 2));
-    HIPCHK(ctx, ctx->wcat_lo.alloc(lo.size() * 2));
-    HIPCHK(ctx, ctx->bcat.alloc(bc.size() * 4));
-    HIPCHK(ctx, ctx->perm.alloc(ctx->lay.perm.size() * 4));
-    HIPCHK(ctx, hipMemcpy(ctx->wcat_hi.p, hi.data(), hi.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->wcat_lo.p, lo.data(), lo.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->bcat.p, bc.data(), bc.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->perm.p, ctx->lay.perm.data(), ctx->lay.perm.size() * 4, hipMemcpyHostToDevice));
-  }
-
-  // ---- pack the image encoder: 16-bit [N][K] matrices, f32 vectors
-  {
-    const bool bf = ctx->cfg.enc_dtype == HVLA_ENC_BF16;
-    auto cv = [&](float f) { return bf ? f2bf(f) : f2h(f); };
-    const size_t per_layer16 = (size_t)3 * E * E + (size_t)E * E + (size_t)2 * E * Fe;
-    std::vector<uint16_t> w16((size_t)E * Kp + per_layer16 * g.enc_layers), d16(w16.size(), 0);
-    const size_t per_layerf = (size_t)3 * E + E + Fe + E + 6 * (size_t)E;
-    std::vector<float> wf((size_t)E + (size_t)S * E + 2 * (size_t)E + per_layerf * g.enc_layers);
-    size_t o16 = 0, of = 0;
-    std::vector<size_t> off16, offf;
-    auto mark16 = [&](size_t n) { off16.push_back(o16); o16 += n; };
-    auto markf = [&](size_t n) { offf.push_back(of); of += n; };
-    // patch embedding: ((p/255 - mean)/std) . w  ==  (p - 128) . w' / 256 + const with w' = 256 w / (255 std)
-    // (x256 keeps small weights in the 16-bit normal range); w' is stored split [hi | lo] along K.
-    const double mean[3] = {0.485, 0.456, 0.406}, sd[3] = {0.229, 0.224, 0.225};
-    const int Kp1 = Kp / 2;
-    mark16((size_t)E * Kp);
-    markf(E);
-    auto back = [&](uint16_t h) -> float { return pack::from16(h, bf); };
-    for (int nn = 0; nn < E; ++nn) {
-      double bacc = e_pb[nn];
-      for (int k = 0; k < Kp1; ++k) {
-        uint16_t hi = 0, lo = 0;
-        if (k < Kreal) {
-          const int c = k % 3;
-          const double wk = e_pk[(size_t)k * E + nn];
-          const float w = (float)(wk * 256.0 / (255.0 * sd[c]));
-          hi = cv(w);
-          lo = cv(w - back(hi));
-          bacc += wk * (128.0 / 255.0 - mean[c]) / sd[c];
-        }
-        w16[off16.back() + (size_t)nn * Kp + k] = hi;
-        w16[off16.back() + (size_t)nn * Kp + Kp1 + k] = lo;
-      }
-      wf[offf.back() + nn] = (float)bacc;
-    }
-    markf((size_t)S * E);
-    for (size_t i = 0; i < (size_t)S * E; ++i) wf[offf.back() + i] = e_pos[i] + (i < (size_t)E ? e_cls[i] : 0.f);
-    markf(E); memcpy(&wf[offf.back()], e_lns, E * 4);
-    markf(E); memcpy(&wf[offf.back()], e_lnb, E * 4);
-    // flax [K][N] -> [N][K] 16-bit, and what the rounding dropped (x 4096: stays in the normal range of fp16) for the
-    // per-image compensation of the encoder GEMMs (encoder.hip corr_kernel)
-    auto tr = [&](const float* src, int K, int N, size_t dst) { pack::pack_matrix_t(src, K, N, bf, &w16[dst], &d16[dst]); };
-    for (int i = 0; i < g.enc_layers; ++i) {
-      const LSrc& s = ls[i];
-      mark16((size_t)3 * E * E);
-      tr(s.q, E, E, off16.back()); tr(s.k, E, E, off16.back() + (size_t)E * E); tr(s.v, E, E, off16.back() + (size_t)2 * E * E);
-      mark16((size_t)E * E); tr(s.o, E, E, off16.back());
-      mark16((size_t)E * Fe); tr(s.f1, E, Fe, off16.back());
-      mark16((size_t)Fe * E); tr(s.f2, Fe, E, off16.back());
-      markf(3 * E);
-      memcpy(&wf[offf.back()], s.qb, E * 4); memcpy(&wf[offf.back() + E], s.kb, E * 4); memcpy(&wf[offf.back() + 2 * E], s.vb, E * 4);
-      markf(E); memcpy(&wf[offf.back()], s.ob, E * 4);
-      markf(Fe); memcpy(&wf[offf.back()], s.f1b, Fe * 4);
-      markf(E); memcpy(&wf[offf.back()], s.f2b, E * 4);
-      const float* six[6] = {s.n1s, s.n1b, s.n2s, s.n2b, s.l1, s.l2};
-      for (int q = 0; q < 6; ++q) { markf(E); memcpy(&wf[offf.back()], six[q], E * 4); }
-    }
-    HIPCHK(ctx, ctx->enc16.alloc(w16.size() * 2));
-    HIPCHK(ctx, ctx->encd16.alloc(d16.size() * 2));
-    HIPCHK(ctx, ctx->encf32.alloc(wf.size() * 4));
-    HIPCHK(ctx, hipMemcpy(ctx->enc16.p, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->encd16.p, d16.data(), d16.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(ctx->encf32.p, wf.data(), wf.size() * 4, hipMemcpyHostToDevice));
-    const uint16_t* e16 = ctx->enc16.as<uint16_t>();
-    const float* df = ctx->encf32.as<float>();
-    EncWeights& w = ctx->encw;
-    size_t i16 = 0, iff = 0;
-    w.w_patch = e16 + off16[i16++];
-    w.b_patch = df + offf[iff++];
-    w.pos = df + offf[iff++];
-    w.lnf_s = df + offf[iff++];
-    w.lnf_b = df + offf[iff++];
-    for (int i = 0; i < g.enc_layers; ++i) {
-      EncLayerW& L = w.layer[i];
-      const uint16_t* dd = ctx->encd16.as<uint16_t>();
-      L.dqkv = dd + off16[i16]; L.wqkv = e16 + off16[i16++]; L.dwo = dd + off16[i16]; L.wo = e16 + off16[i16++];
-      L.dw1 = dd + off16[i16]; L.w1 = e16 + off16[i16++]; L.dw2 = dd + off16[i16]; L.w2 = e16 + off16[i16++];
-      L.bqkv = df + offf[iff++]; L.bo = df + offf[iff++]; L.b1 = df + offf[iff++]; L.b2 = df + offf[iff++];
-      L.ln1_s = df + offf[iff++]; L.ln1_b = df + offf[iff++]; L.ln2_s = df + offf[iff++]; L.ln2_b = df + offf[iff++];
-      L.ls1 = df + offf[iff++]; L.ls2 = df + offf[iff++];
-    }
+    const TrainLayout::EL& o = at.enc[i];
+    EncLayerW& L = w.layer[i];
+    L.wqkv = e16 + o.qk; L.wo = e16 + o.ok; L.w1 = e16 + o.f1k; L.w2 = e16 + o.f2k;
+    L.dqkv = dd + o.qk; L.dwo = dd + o.ok; L.dw1 = dd + o.f1k; L.dw2 = dd + o.f2k;
+    L.bqkv = df + o.qb; L.bo = df + o.ob; L.b1 = df + o.f1b; L.b2 = df + o.f2b;
+    L.ln1_s = df + o.n1s; L.ln1_b = df + o.n1b; L.ln2_s = df + o.n2s; L.ln2_b = df + o.n2b; L.ls1 = df + o.ls1; L.ls2 = df + o.ls2;
   }
   HIPCHK(ctx, hipDeviceSynchronize());
   ctx->loaded = true;
@@ -952,14 +818,9 @@ int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int
   const TrainLayout L = make_train_layout(g);
   const int64_t want = L.total + (train_encoder ? L.enc_total : 0);
   if (n_params != want) FAIL(ctx, HVLA_E_SHAPE, "n_params %lld, the training vector has %lld", (long long)n_params, (long long)want);
-  // the tables restate hvla_load_weights' order: a buffer of another size means they do not describe this context
+  // (the transposing kernel's whole 64 x 64 tiles: hvla_create admits encoder widths in multiples of 128 only)
   const PolicyLayout& pl = ctx->lay.pl;
   const int Gtot = pl.Gm + pl.Gv;
-  const pubmap::EncMap em = pubmap::enc_map(g, L);
-  if (pubmap::ctx_table(g, L).dst_total * 4 != (int64_t)ctx->hn_f32.bytes || (size_t)Gtot * 4 != ctx->bcat.bytes ||
-      (size_t)(Gtot / 32) * (g.C / 16) * 1024 != ctx->wcat_hi.bytes || em.n16 * 2 != (int64_t)ctx->enc16.bytes ||
-      em.vec.dst_total * 4 != (int64_t)ctx->encf32.bytes || em.Kp != ctx->Kp || g.E % pubmap::TR_TILE || g.enc_mlp % pubmap::TR_TILE)
-    FAIL(ctx, HVLA_E_STATE, "the publish tables do not match this context's buffers");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   PublishArgs a{g, params, ctx->hn_f32.as<float>(), ctx->perm.as<int32_t>(), ctx->wcat_hi.as<uint16_t>(), ctx->wcat_lo.as<uint16_t>(),
                 ctx->bcat.as<float>(), Gtot, ctx->enc16.as<uint16_t>(), ctx->encd16.as<uint16_t>(), ctx->encf32.as<float>(),

@@ -1,6 +1,6 @@
-// pack.h — host-only packing of checkpoint tensors into the device layouts (used by api.hip; no HIP types, so that
-// tests/native/pack_asan.cpp can run it under -fsanitize=address,undefined on the CPU).  The rounding functions are also the
-// device's (publish.hip): HVLA_HD is `__host__ __device__` under hipcc and empty for a host compiler, so one text serves both.
+// pack.h — the element formulas of the serving buffers and the host packing of W_cat and the encoder matrices (no HIP types: the
+// programs of tests/native/ run it under -fsanitize=address,undefined on the CPU).  Every formula exists once: the host packer
+// (serving_layout.h) and publish.hip run this text.  HVLA_HD is `__host__ __device__` under hipcc, empty for a host compiler.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -68,6 +68,47 @@ HVLA_HD inline float h2f(uint16_t h) {
 HVLA_HD inline uint16_t to16(float f, bool bf) { return bf ? f2bf(f) : f2h(f); }
 HVLA_HD inline float from16(uint16_t h, bool bf) { return bf ? bf2f(h) : h2f(h); }
 
+// one element of a transposing pack: the 16-bit weight and what the rounding dropped, x 4096 (stays in the normal range of fp16)
+HVLA_HD inline void round_pair(float w, bool bf, uint16_t& w16, uint16_t& d16) {
+  w16 = to16(w, bf);
+  d16 = to16((w - from16(w16, bf)) * 4096.f, bf);
+}
+// one element of W_cat: hi = bf16(w), lo = bf16(w - hi)
+HVLA_HD inline void split_pair(float w, uint16_t& hi, uint16_t& lo) {
+  hi = f2bf(w);
+  lo = f2bf(w - bf2f(hi));
+}
+// fragment lane rho (+ 32 for the upper eight k of a k-step) holds column tau of its 32-column tile, and the inverse
+HVLA_HD inline int tau_of_rho(int rho) { return 16 * ((rho >> 2) & 1) + (rho & 3) + 4 * (rho >> 3); }
+HVLA_HD inline int rho_of_tau(int tau) { return (tau & 3) + 4 * (tau >> 4) + 8 * ((tau >> 2) & 3); }
+
+// output channel nn of the patch embedding: row nn of [E][hi Kp/2 | lo Kp/2] and its bias.  `pk` [Kreal][E].
+// ((p/255 - mean)/std) . w  ==  (p - 128) . w' / 256 + const with w' = 256 w / (255 std): x256 keeps small weights in the 16-bit
+// normal range.  The rescale is done in double and rounded to f32 once; the bias is accumulated in double, ascending k.
+HVLA_HD inline float patch_channel(const float* pk, float pb, int E, int nn, int Kreal, int Kp, bool bf, uint16_t* row) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  // (selected, not indexed: a table indexed by k % 3 would sit in the kernel's private segment)
+  const int Kp1 = Kp / 2;
+  double bacc = pb;
+  for (int k = 0; k < Kp1; ++k) {
+    uint16_t hi = 0, lo = 0;
+    if (k < Kreal) {
+      const int c = k % 3;
+      const double mean = c == 0 ? 0.485 : c == 1 ? 0.456 : 0.406, sd = c == 0 ? 0.229 : c == 1 ? 0.224 : 0.225;
+      const double wk = pk[(size_t)k * E + nn];
+      const float w = (float)(wk * 256.0 / (255.0 * sd));
+      hi = to16(w, bf);
+      lo = to16(w - from16(hi, bf), bf);
+      bacc += wk * (128.0 / 255.0 - mean) / sd;
+    }
+    row[k] = hi;
+    row[Kp1 + k] = lo;
+  }
+  return (float)bacc;
+}
+
 // W_cat^T as MFMA A fragments (layout.h): tile pt, k-step ks, lane (rho = l & 31, hk = l >> 5), j; hi / lo bf16 planes, and
 // b_cat in packed order.  lk[i] / lb[i]: kernel [C][size_i] / bias [size_i] of generated leaf i.
 inline void pack_wcat(const PackedLayout& lay, const std::vector<LeafInfo>& leaves, const std::vector<const float*>& lk,
@@ -90,8 +131,7 @@ inline void pack_wcat(const PackedLayout& lay, const std::vector<LeafInfo>& leav
   for (int pt = 0; pt < ntiles; ++pt)
     for (int lane = 0; lane < 64; ++lane) {
       const int rho = lane & 31, hk = lane >> 5;
-      const int tau = 16 * ((rho >> 2) & 1) + (rho & 3) + 4 * (rho >> 3);
-      const int ref = perm[pt * 32 + tau];
+      const int ref = perm[pt * 32 + tau_of_rho(rho)];
       const float* col = nullptr;
       int64_t n_leaf = 0;
       if (ref >= 0) {
@@ -102,25 +142,17 @@ inline void pack_wcat(const PackedLayout& lay, const std::vector<LeafInfo>& leav
       for (int ks = 0; ks < KS; ++ks)
         for (int j = 0; j < 8; ++j) {
           const int k = 16 * ks + 8 * hk + j;
-          const float w = col ? col[(int64_t)k * n_leaf] : 0.f;
-          const uint16_t h = f2bf(w);
           const size_t o = ((size_t)(pt * KS + ks) * 64 + lane) * 8 + j;
-          hi[o] = h;
-          lo[o] = f2bf(w - bf2f(h));
+          split_pair(col ? col[(int64_t)k * n_leaf] : 0.f, hi[o], lo[o]);
         }
     }
 }
 
-// flax [K][N] -> [N][K] 16-bit, and what the rounding dropped (x 4096: stays in the normal range of fp16) for the
-// per-image compensation of the encoder GEMMs
+// flax [K][N] -> [N][K] 16-bit, and the rounding residues for the per-image compensation of the encoder GEMMs (encoder.hip
+// corr_kernel)
 inline void pack_matrix_t(const float* src, int K, int N, bool bf, uint16_t* w16, uint16_t* d16) {
   for (int n = 0; n < N; ++n)
-    for (int k = 0; k < K; ++k) {
-      const float wv = src[(size_t)k * N + n];
-      const uint16_t h = to16(wv, bf);
-      w16[(size_t)n * K + k] = h;
-      d16[(size_t)n * K + k] = to16((wv - from16(h, bf)) * 4096.f, bf);
-    }
+    for (int k = 0; k < K; ++k) round_pair(src[(size_t)k * N + n], bf, w16[(size_t)n * K + k], d16[(size_t)n * K + k]);
 }
 
 }  // namespace pack

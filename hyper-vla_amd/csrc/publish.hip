@@ -1,17 +1,18 @@
 // publish.hip — hvla_train_publish: the flat training vector (parameters or EMA) into the serving buffers, on the device.
 //
 // Everything here is an index permutation with a rounding, bound by memory traffic; no matrix core is involved.  The index maps
-// are the tables of publish_map.h and the roundings are pack.h's own functions, compiled for the device, so that the bytes are
-// those hvla_load_weights writes for the same tensors (tests/native/publish_map_check.cpp runs the same tables on the CPU against
-// the host packer; tests/test_gpu_publish.py compares the device buffers' effect bit for bit against a freshly loaded model).
+// come from the enumeration of serving_layout.h that hvla_load_weights packs by, the roundings are the functions of pack.h that it
+// calls: the bytes are the loader's (tests/native/publish_map_check.cpp runs both on the CPU against a frozen copy of the earlier
+// loader; tests/test_gpu_publish.py compares the device buffers' effect bit for bit against a freshly loaded model).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "publish_map.h"
+#include "serving_layout.h"
 
 namespace hvla {
 
-using namespace pubmap;
+using namespace serving;
+using namespace pack;
 
 // ---- f32 copies driven by a table (context encoder -> hn_f32, encoder vectors -> encf32) ----
 // grid (x, segment, layer); a segment that exists once is written by layer 0's blocks only

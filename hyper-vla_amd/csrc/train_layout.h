@@ -1,5 +1,5 @@
-// train_layout.h — flat layout of the trainable parameter vector (hvla_train_*).  No HIP types: train.hip, api.hip and the CPU
-// check of the publish tables (tests/native/publish_map_check.cpp) share this one text.
+// train_layout.h — flat layout of the trainable parameter vector (hvla_train_*).  No HIP types: train.hip, api.hip, the layout of
+// the serving buffers (serving_layout.h) and its CPU check (tests/native/publish_map_check.cpp) share this one text.
 #pragma once
 #include <stdint.h>
 

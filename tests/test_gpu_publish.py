@@ -240,3 +240,35 @@ def test_refusals(mid, tmp_path):
     m.save_pretrained(0, str(tmp_path / "ckpt"))
     with np.load(tmp_path / "ckpt" / "params_0.npz") as z:
         assert set(z.files) == set(m.params)
+
+
+def test_load_refuses_an_incomplete_checkpoint_and_serves_after_a_complete_one():
+    """hvla_load_weights with one encoder tensor missing names it (HVLA_E_WEIGHTS) and leaves the context without weights
+    (hvla_generate: HVLA_E_STATE); the complete set loaded into the same context afterwards serves, bit for bit, what a model that
+    never saw the failure serves."""
+    _need_gpu()
+    from hypervla import _native
+    from hypervla import synthetic as syn
+    from hypervla.config import MID, hypernet_param_shapes
+    from hypervla.model import HyperVLA
+    s = _inputs(MID, 2)
+    P = syn.synthetic_params(MID)
+    want = _outputs(HyperVLA.from_synthetic(MID, params=P, max_batch=2), s)
+    params = {k: P[k] for k in hypernet_param_shapes(MID)}
+    gone = "encoder_image_encoder_encoder_layer_1_mlp_fc1_bias"
+    assert gone in params
+    ctx = _native.Context(MID, 0, 2)
+    with pytest.raises(_native.NativeError, match="HVLA_E_WEIGHTS") as e:
+        ctx.load_weights({k: v for k, v in params.items() if k != gone})
+    assert f"checkpoint tensor {gone} (absent)" in str(e.value)
+    dev = torch.device("cuda", 0)
+    tok = torch.zeros(1, MID.lang_tokens, MID.lang_dim, device=dev)
+    mask = torch.ones(1, MID.lang_tokens, dtype=torch.int64, device=dev)
+    cls = torch.zeros(1, MID.enc_dim, device=dev)
+    with pytest.raises(_native.NativeError, match="HVLA_E_STATE"):
+        ctx.generate(tok.data_ptr(), mask.data_ptr(), cls.data_ptr(), 1)
+    ctx.load_weights(params)
+    m = HyperVLA.from_synthetic(MID, params=P, max_batch=2)
+    m._ctx.close()
+    m._ctx = ctx                                       # the model now serves from the context whose first load failed
+    _same(_outputs(m, s), want, KEYS)

@@ -1,5 +1,6 @@
-"""CPU: the index maps and roundings of hvla_train_publish (csrc/publish_map.h, csrc/pack.h) against the host packer, the value set
-of the GPU rounding test, and the new symbol."""
+"""CPU: the one layout of the serving buffers (csrc/serving_layout.h, csrc/pack.h) -- the publish tables and the host packer of
+hvla_load_weights against a frozen copy of the earlier loader, the packer's refusals -- the value set of the GPU rounding test, and
+the publish symbol."""
 import ctypes
 import os
 import shutil
@@ -15,7 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_publish_tables_against_the_host_packer_under_asan_ubsan(tmp_path):
     """tests/native/publish_map_check.cpp: at MID and README geometry a training vector of distinct values through the publish
     tables and the shared rounding functions (what the kernels do) equals, byte for byte, pack::pack_wcat / pack::pack_matrix_t and
-    a transcription of hvla_load_weights' ordering fed the same leaves; every destination element is written exactly once."""
+    a transcription of the ordering hvla_load_weights had before serving_layout.h, fed the same leaves; every destination element
+    is written exactly once.  The real host packer (serving::pack_serving, what hvla_load_weights runs), fed the same leaves by
+    checkpoint name, gives the same bytes; the offsets it returns are where the transcription holds each tensor and tile every
+    buffer.  At MID geometry a checkpoint with a tensor absent or off by one element is refused with that name and its suffix,
+    nothing is written, and of two such tensors the first of the enumeration is named."""
     exe = tmp_path / "publish_map_check"
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
@@ -27,6 +32,7 @@ def test_publish_tables_against_the_host_packer_under_asan_ubsan(tmp_path):
     assert run.returncode == 0, run.stdout + run.stderr
     assert run.stdout.strip().endswith("OK"), run.stdout
     assert "README geometry" in run.stdout and "MID geometry (bf16)" in run.stdout, run.stdout
+    assert "the packer names the first absent or wrong-sized tensor and writes nothing" in run.stdout, run.stdout
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
 
 

@@ -3,7 +3,8 @@
   device  FineTuner.publish(host_copy=False): hvla_train_publish packs the flat training vector into the serving buffers in place;
           timed with events on the stream, one event pair per repetition.
   host    what there was before: ft.params.cpu() -> unpack_params -> Context.load_weights on the context that already exists
-          (device -> host copy, single-thread packing in csrc/pack.h, upload); wall clock around the synchronous calls.
+          (device -> host copy, the single-thread host packer of csrc/serving_layout.h + pack.h, upload); wall clock around the
+          synchronous calls, and around hvla_load_weights alone.
 
 Next to each time: the bytes the device route moves (the vector read once, every serving buffer written once) divided by the
 time, against this process's device-to-device copy rate (a torch copy of a buffer of the vector's size, read + write counted) and
@@ -79,11 +80,16 @@ def main():
         flat = ft.params.cpu().numpy()
         params = dict(m._params)
         params.update(unpack_params(g, flat, True))
+        t1 = time.perf_counter()
         m._ctx.load_weights({k: params[k] for k in hypernet_param_shapes(g)})
         torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3
+        t2 = time.perf_counter()
+        load.append((t2 - t1) * 1e3)
+        return (t2 - t0) * 1e3
 
+    load = []
     host_route()
+    del load[:]
     host = [host_route() for _ in range(a.reps)]
 
     d, h = float(np.median(device)), float(np.median(host))
@@ -94,8 +100,9 @@ def main():
     say(f"              median {d:.3f} ms = {moved / (d * 1e-3) / 1e12:.2f} TB/s = {100 * moved / (d * 1e-3) / 1e12 / copy_rate:.0f} % of the copy rate")
     say("host route    params.cpu() -> unpack_params -> load_weights, ms per repetition: " + " ".join(f"{x:.0f}" for x in host))
     say(f"              median {h:.0f} ms = {moved / (h * 1e-3) / 1e9:.2f} GB/s")
+    say("              of which hvla_load_weights (host packer + upload), ms: " + " ".join(f"{x:.0f}" for x in load) + f"; median {np.median(load):.0f}")
     say(f"device route is {h / d:.0f} x faster")
-    res = dict(geometry="README", train_encoder=True, reps=a.reps, device_ms=round(d, 4), host_ms=round(h, 1), speedup=round(h / d, 1),
+    res = dict(geometry="README", train_encoder=True, reps=a.reps, device_ms=round(d, 4), host_ms=round(h, 1), load_ms=round(float(np.median(load)), 1), speedup=round(h / d, 1),
                bytes_moved=int(moved), device_TBps=round(moved / (d * 1e-3) / 1e12, 3), copy_TBps=round(copy_rate, 3),
                clock_mhz=round(clock), mfma_tflops=round(tflops, 1))
     say(json.dumps(res))
