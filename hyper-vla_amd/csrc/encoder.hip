@@ -10,8 +10,10 @@
 //                      four phases per K-tile, persistent.  A 256-row tile is exactly the 256 patch rows of ONE image
 //                      (rows b*257 + 1 .. b*257 + 256; the B CLS rows go to gemm64_kernel with a row stride): no ragged
 //                      tile rows, and everything that is per image (the bias row below, column sums) is per tile.
-//   gemm64_kernel      64x64 tiles for small row counts (B <= 7, and the CLS rows);  gemm_kernel: 128x128 tiles for
-//                      widths that are not multiples of 256 (DINOv2-small).  Fused epilogues:
+//   gemm64_kernel      64x64 tiles for small row counts (up to 2047 rows, and the CLS rows);  gemm64c_kernel / gemm64c32_kernel:
+//                      the same for a small batch with the per-image bias rows computed inside (64 x 32 tiles while the grid
+//                      fills less than half of the chip; FOLD: the mean rows added up from the LayerNorm's partials);
+//                      gemm_kernel: 128x128 tiles for images that are not 256 patches.  Fused epilogues:
 //                        PATCH  + bias + position embedding  -> f32 residual stream (row remap b*P+p -> b*S+1+p)
 //                        QKV    + bias, q * 1/sqrt(hd)        -> 16-bit
 //                        GELU   + bias, exact erf GELU        -> 16-bit
@@ -19,16 +21,20 @@
 //   mean rows / corr   first-order compensation of the WEIGHT rounding: A W = A W16 + A dW with
 //                      dW = W - W16; A dW is replaced by (per-image mean row of A) dW, a [B, N] table (gemm64_kernel's
 //                      second problem) that the epilogues add instead of the bias.  The mean rows come out of the kernels
-//                      that write A: layernorm_img_kernel, attention_kernel, the GELU epilogue.  Rounding a shared weight perturbs every token of an image the same way,
+//                      that write A: the LayerNorm (layernorm_group_kernel + layernorm_mean_kernel, or the tail of a residual
+//                      GEMM), attention_kernel, the GELU epilogue.  Rounding a shared weight perturbs every token of an image the same way,
 //                      which the generated policy (it pools the 256 tokens) feels about sqrt(257) times more than the
 //                      independent rounding of activations; the mean row carries most of that coherent part.
-//   layernorm_kernel   f32 rows -> 16-bit rows (eps 1e-6), one wavefront per row; final variant drops the
-//                      CLS row and writes the f32 patch tokens the policy consumes
+//   layernorm_group_kernel  norm1 / norm2 where no residual GEMM runs them in its epilogue (gemm256p_kernel<..., LNX>): f32 rows ->
+//                      16-bit rows (eps 1e-6) + partial column sums, which layernorm_mean_kernel or the consumer GEMM adds up
+//   layernorm_kernel   the final norm: drops the CLS row and writes the f32 patch tokens the policy consumes
 //   attention_kernel   S = 257, head_dim 64: one workgroup per (image, head), one wavefront per 32-query
 //                      block; K and V resident in LDS (V consumed through ds_read_b64_tr_b16); transposed scores (keys on accumulator rows,
 //                      query on the lane) so softmax is in-lane and P feeds the PV MFMA from registers.
 //
 // Residual stream, LayerNorm statistics, softmax and GELU are f32; only MFMA operands are 16-bit.
+// Which of these runs for a product, with which grid and LDS size, is decided in plan.h from the sizes alone; the host side at the
+// end of this file holds the kernel tables and launches what the plan says.
 #include <cstring>
 #include <type_traits>
 
@@ -79,8 +85,7 @@ __global__ void im2col_kernel(const uint8_t* __restrict__ img, typename Op::elem
 }
 
 // ------------------------------------------------------------------------------------------------
-enum { EPI_PATCH = 0, EPI_QKV = 1, EPI_GELU = 2, EPI_RES = 3, EPI_CORR = 4 };   // CORR: out f32 = bias + acc / 4096 (gemm64_kernel's second problem)
-
+// (the epilogues EPI_PATCH .. EPI_CORR, and every tile / stage constant the host sizes a launch with, are defined in plan.h)
 struct GemmArgs {
   const void* A;   // 16-bit; logical row m lives at global row row0 + m * row_step, K contiguous
   const void* W;   // [N][K] 16-bit
@@ -133,7 +138,7 @@ struct GemmArgs {
   // rows_xcd = images per XCD label, rcp = ceil(65536 / nbn)
   int lnx_G = 0, lnx_rows_aligned = 0, lnx_rounds_div = 0, lnx_rows_xcd = 0, lnx_rcp = 0;
   // gemm64c_kernel<..., FOLD = true> (the GEMM behind a LayerNorm at a small batch): the mean rows are not read from abar2 but
-  // added up by every workgroup from layernorm_split_kernel's partial column sums [image][half][LNW][K] f32, with
+  // added up by every workgroup from layernorm_group_kernel's partial column sums [image][LNG][K] f32, with
   // layernorm_mean_kernel's arithmetic -- that launch (two per layer, 4.5 us + a kernel boundary each at B = 1) is gone
   const float* ln_partial = nullptr;
 };
@@ -308,7 +313,6 @@ __device__ __forceinline__ void gemm_epilogue_rows(const f32x4 (&acc)[4][MT], co
 // ------------------------------------------------------------------------------------------------
 // gemm_kernel -- 128x128x64 tiles, 4 waves x (64x64), LDS double-buffered through registers with 144-B padded rows.
 // Serves widths that are not multiples of 256 (DINOv2-small) and geometries whose images are not 256 patches.
-constexpr int GBM = 128, GBN = 128, GBK = 64, GLD = 72;   // GLD: padded LDS row (halves) = 144 B
 
 template <typename Op, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
@@ -398,7 +402,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmArgs g) {
 // Four waves, wave w owns rows [16 w, +16) x all 64 columns: 10 ds_read_b128 and 8 MFMAs per K-tile.  LDS image, swizzle,
 // W-row permutation, MFMA and k order are those of gemm256p_kernel, so a row gets the same bits whichever kernel
 // computes it.
-constexpr int SBM = 64, SBN = 64, SNS = 6;
 // NS stages of 16 KB: 6 (5 K-tiles in flight, one workgroup per CU) or 4 (64 KB: two workgroups per CU, for the launches
 // with more blocks than CUs -- the QKV and fc1 shapes -- which otherwise run as two rounds).  Same bits either way.
 template <typename Op, int EPI, int NS = SNS>
@@ -510,15 +513,10 @@ __global__ __launch_bounds__(256) void gemm64_kernel(GemmArgs g) {
 // beside A and W (dW 8 KB, mean rows 4 KB per stage).  The accumulators go through corr_value() into a 16 x 64 table in LDS
 // that the epilogue reads instead of a table in memory: the separate table launch in front of every GEMM (48 per step,
 // 12 us each at B = 1) is gone.  Same operands, same MFMA, same k order as gemm64_body<EPI_CORR> => the same bias rows.
-constexpr int SNSC = 5, SSTC = 28672;   // stages x (A 8 KB | W 8 KB | dW 8 KB | mean rows 4 KB)
-constexpr int LNW = 16;                 // waves of a LayerNorm workgroup
-constexpr int LNG = 8;                  // row groups per image of layernorm_group_kernel = partial column sums per image: [half][fq]
 // abar[(image, half)] = ((p0 + p1) + (p2 + p3)) / (P / 2): the four partials of a half (layernorm_group_kernel), n4 float4 apart
 __device__ __forceinline__ f32x4 ln_half_sum(const f32x4* p, int n4) { return (p[0] + p[n4]) + (p[2 * n4] + p[3 * n4]); }
 // FOLD: the mean rows of ALL K-tiles sit in a table behind the stages ([K-tile][16 rows][128 B], a stage's mean-row image), written
 // once in the prologue from the LayerNorm's partial sums (GemmArgs::ln_partial); a stage is then A | W | dW = 24 KB, six pieces.
-constexpr int SSTF = 24576;
-constexpr size_t gemm64c_fold_lds(int K) { return (size_t)SNSC * SSTF + (size_t)(K / 64) * 2048; }
 template <typename Op, int EPI, bool FOLD = false>
 __global__ __launch_bounds__(256) void gemm64c_kernel(GemmArgs g) {
   constexpr int SST = FOLD ? SSTF : SSTC, PCS = FOLD ? 6 : 7;        // stage stride, LDS-DMA pieces per wave and K-tile
@@ -688,7 +686,6 @@ __global__ __launch_bounds__(256) void gemm64c_kernel(GemmArgs g) {
 // 2 c + nt: lane (fr, fq) owns the two adjacent columns n0 + 2 fr + {0, 1} of its four rows.  Same operands, same MFMA,
 // same k order per accumulator, the same epilogue arithmetic (acc + bias row, then fma with the layer scale into x) as
 // gemm_epilogue_rows_impl<EPI_RES>: the same bits as every other path (the batch-invariance tests cross them).
-constexpr int SNS32 = 7, SST32 = 20480;
 template <typename Op>
 __global__ __launch_bounds__(256) void gemm64c32_kernel(GemmArgs g) {
   using T = typename Op::elem;
@@ -1035,7 +1032,6 @@ __global__ __launch_bounds__(256) void layernorm_mean_kernel(const float* __rest
 // PERSIST: gridDim.x workgroups walk the tiles v, v + gridDim.x, ...; the prologue DMA of the next tile (K-tile 0 and the
 // A halves of K-tile 1 = PRO_DMA instructions per wave) is issued BEFORE this tile's epilogue, so its latency and the
 // workgroup launch disappear under the epilogue's VALU work and stores.
-constexpr int HBM_ = 256, HBN_ = 256;
 constexpr int PRO_DMA = 12, PRO_DMA_KT0 = 8;        // LDS-DMA instructions per wave in that prologue / of them K-tile 0
 // vector-memory instructions every wave issues in a FULL tile's epilogue, all of them behind the prologue DMA (vmcnt counts
 // loads, stores and DMA together and retires in order): MT = 8 m-tiles x 4 rows of stores, plus as many residual loads.
@@ -1795,8 +1791,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // ------------------------------------------------------------------------------------------------
 // Attention, head_dim 64.  qkv [B*S][3E] 16-bit (q already scaled by log2(e)/sqrt(64)); out o [B*S][E].
 constexpr int AKLD = 72;          // K row stride in LDS (halves): 144 B
-constexpr int APS = 68;           // floats per partial of the last query: max, sum, 2 unused, O[64] (16-byte aligned)
-constexpr int AVLD = 64;          // V row stride (halves): 128 B, 64-B halves swapped on rows with bit 1 set
 // K rows are 128 B = half of the 64 banks, so a row's bank half is its row parity, and the 16-B chunk swizzle (chunk ^ key & 7)
 // alone leaves every ds_read_b128 lane group ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}: guide, LDS table) with two keys
 // per 4-bank slot (SQ_LDS_BANK_CONFLICT was 27 % of the LDS cycles of this kernel).  Storing key k in row kperm(k) -- bits 0
@@ -2409,6 +2403,34 @@ __global__ __launch_bounds__(256) void absmax_kernel(const T* __restrict__ p, si
 }
 
 // ------------------------------------------------------------------------------------------------
+// The host side.  plan.h decides every launch from the sizes alone; here are the tables its kernel ids index -- the ONE place that
+// names the instantiations -- and run_encoder, which fills pointers and launches what the plan says.
+template <typename Op>
+struct EncKernels {
+  typedef void (*Gemm)(GemmArgs);
+  typedef decltype(&attention_kernel<Op, false>) Attn;
+  static const Gemm* gemm() {           // [GemmKernel]
+    static const Gemm t[NUM_GEMM_KERNELS] = {
+#define HVLA_X(id, ...) __VA_ARGS__,
+        HVLA_GEMM_KERNELS(HVLA_X)
+#undef HVLA_X
+    };
+    return t;
+  }
+  static const Attn* attn() {           // [AttnKernel]
+    static const Attn t[NUM_ATTN_KERNELS] = {attention_kernel<Op, false>, attention_kernel<Op, false, 8>, attention_kernel<Op, true>};
+    return t;
+  }
+  static auto ln_group() { return layernorm_group_kernel<Op>; }
+  static hipError_t raise_lds_limit() { // every kernel that is launched with dynamic LDS
+    auto raise = [](auto kern) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT); };
+    hipError_t e = raise(ln_group());
+    for (int k = 0; k < NUM_GEMM_KERNELS && e == hipSuccess; ++k) e = raise(gemm()[k]);
+    for (int k = 0; k < NUM_ATTN_KERNELS && e == hipSuccess; ++k) e = raise(attn()[k]);
+    return e;
+  }
+};
+
 namespace {
 struct DeviceInfo {       // per device: a second HyperVLA on another GPU of the same process needs its own
   bool attr[2] = {false, false};
@@ -2416,6 +2438,24 @@ struct DeviceInfo {       // per device: a second HyperVLA on another GPU of the
 };
 DeviceInfo g_dev[64];
 }  // namespace
+// the current device's CU count; the first call per device and operand type raises the kernels' LDS limits
+template <typename Op>
+static hipError_t device_setup(int& ncu) {
+  constexpr int opi = std::is_same<Op, OpBF16>::value ? 1 : 0;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  DeviceInfo& di = g_dev[dev];
+  if (!di.attr[opi]) {
+    if ((e = EncKernels<Op>::raise_lds_limit()) != hipSuccess) return e;
+    di.attr[opi] = true;
+  }
+  if (!di.ncu && (hipDeviceGetAttribute(&di.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || di.ncu <= 0)) di.ncu = 256;
+  ncu = di.ncu;
+  return hipSuccess;
+}
+static dim3 grid_of(const Launch& l) { return dim3(l.grid, l.grid_y); }
 
 // every launch of an encoder call is counted (Profiler::nlaunch; hvla_launches): bench.py reports launches per step from here
 #define HVLA_LAUNCH(...) do { ++pf.nlaunch; hipLaunchKernelGGL(__VA_ARGS__); } while (0)
@@ -2425,260 +2465,96 @@ static hipError_t run_encoder(const Geom& g, const EncWeights& w, const EncWorks
   Profiler none;
   Profiler& pf = prof ? *prof : none;
   using T = typename Op::elem;
-  constexpr int opi = std::is_same<Op, OpBF16>::value ? 1 : 0;
-  const int P = g.P(), S = g.S(), E = g.E, F = g.enc_mlp, H = g.enc_heads;
-  const int Kp = 2 * ((g.patch * g.patch * 3 + 63) / 64 * 64);   // [a | a] x [W_hi | W_lo]
-  const int M = B * S;
-  // the GEMM epilogues address their outputs with 32-bit element offsets
-  if ((size_t)M * (size_t)(F > 3 * E ? F : 3 * E) >= (1ull << 32)) return hipErrorInvalidValue;
-  const size_t gsm = (size_t)2 * (GBM + GBN) * GLD * sizeof(T);
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-  DeviceInfo& di = g_dev[dev];
-  if (!di.attr[opi]) {
-#define SETA(K) \
-  if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-    SETA((gemm_kernel<Op, EPI_PATCH>)) SETA((gemm_kernel<Op, EPI_QKV>)) SETA((gemm_kernel<Op, EPI_GELU>))
-    SETA((gemm_kernel<Op, EPI_RES>)) SETA((attention_kernel<Op, false>)) SETA((attention_kernel<Op, true>)) SETA((attention_kernel<Op, false, 8>))
-    SETA((gemm256p_kernel<Op, EPI_PATCH, false>)) SETA((gemm256p_kernel<Op, EPI_QKV, false>))
-    SETA((gemm256p_kernel<Op, EPI_GELU, false>)) SETA((gemm256p_kernel<Op, EPI_RES, false>))
-    SETA((gemm256p_kernel<Op, EPI_PATCH, true>)) SETA((gemm256p_kernel<Op, EPI_QKV, true>))
-    SETA((gemm256p_kernel<Op, EPI_GELU, true>)) SETA((gemm256p_kernel<Op, EPI_RES, true>))
-    SETA((gemm256p_kernel<Op, EPI_PATCH, false, true>)) SETA((gemm256p_kernel<Op, EPI_RES, false, true>))
-    SETA((gemm256p_kernel<Op, EPI_PATCH, true, true>)) SETA((gemm256p_kernel<Op, EPI_RES, true, true>))
-    SETA((gemm256p_kernel<Op, EPI_RES, false, true, true>)) SETA((gemm256p_kernel<Op, EPI_RES, true, true, true>))
-    SETA((gemm64_kernel<Op, EPI_PATCH>)) SETA((gemm64_kernel<Op, EPI_QKV>)) SETA((gemm64_kernel<Op, EPI_GELU>))
-    SETA((gemm64_kernel<Op, EPI_RES>)) SETA((gemm64_kernel<Op, EPI_CORR>))
-    SETA((gemm64_kernel<Op, EPI_QKV, 4>)) SETA((gemm64_kernel<Op, EPI_GELU, 4>)) SETA((gemm64_kernel<Op, EPI_RES, 4>))
-    SETA((gemm64c_kernel<Op, EPI_QKV>)) SETA((gemm64c_kernel<Op, EPI_GELU>)) SETA((gemm64c_kernel<Op, EPI_RES>)) SETA((gemm64c32_kernel<Op>))
-    SETA((gemm64c_kernel<Op, EPI_QKV, true>)) SETA((gemm64c_kernel<Op, EPI_GELU, true>)) SETA((layernorm_group_kernel<Op>))
-    SETA((gemm256p_kernel<Op, EPI_QKV, false, false, true>)) SETA((gemm256p_kernel<Op, EPI_GELU, false, false, true>))
-    SETA((gemm256p_kernel<Op, EPI_QKV, true, false, true>)) SETA((gemm256p_kernel<Op, EPI_GELU, true, false, true>))
-    SETA((gemm256p_kernel<Op, EPI_RES, false, false, true>)) SETA((gemm256p_kernel<Op, EPI_RES, true, false, true>))
-#undef SETA
-    di.attr[opi] = true;
-  }
-  if (!di.ncu && (hipDeviceGetAttribute(&di.ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || di.ncu <= 0)) di.ncu = 256;
-  const int ncu = di.ncu;
-  constexpr int G64_MAXM = 2047;       // rows up to which a GEMM is cut into 64x64 tiles (pure latency below that)
-  constexpr int CAT_COMP = 8;          // HVLA_PROF_COMP
+  using Kern = EncKernels<Op>;
+  const int P = g.P(), S = g.S(), E = g.E, F = g.enc_mlp, H = g.enc_heads, M = B * S;
   const bool comp = w.layer[0].dqkv != nullptr && ws.corr && ws.abar;
+  EncSizes z{B, P, S, E, F, H, g.patch, g.enc_layers, 0, sizeof(T), comp, ws.ln_cnt != nullptr && ws.ln_part != nullptr, ws.amap != nullptr};
+  const CallPlan call = plan_call(z);
+  if (!call.ok) return hipErrorInvalidValue;
+  hipError_t e = device_setup<Op>(z.ncu);
+  if (e != hipSuccess) return e;
   const int hsplit = 1 + P / 2;        // tokens [1, hsplit) | [hsplit, S): the two wave rows of an image-aligned tile; the CLS row takes the plain bias
-  // ---- one GEMM of the encoder: activations [B*S rows][K] -> [B*S rows][N], with the per-image bias rows that compensate
-  // the rounding of W (dW = the rounding residue x 4096; the mean row of the activation operand is in ws.abar, written by
-  // the kernel that produced the operand)
-  //  * images of 256 patches, batch >= 8, N % 256 == 0: ONE gemm64_kernel launch for the 2 B latency-bound rows (the B CLS
-  //    rows, stride S, plain bias; the B mean rows against dW -> ws.corr), then gemm256p_kernel over image-aligned tiles
-  //    (tile row b = rows b*S + 1 .. b*S + 256 = the patch rows of image b) with ws.corr as its bias rows;
-  //  * otherwise a corr-only gemm64_kernel launch, then gemm64_kernel (<= 2047 rows) or gemm_kernel (128x128 tiles) over all rows, bias row
-  //    looked up per row.
-  // Returns whether the image-aligned form ran (then a GELU epilogue writes the mean row of its output itself).
-  // ln_s / ln_b (RES only): scale and bias of the LayerNorm that follows this GEMM; the image-aligned form runs it inside its
-  // epilogue (GemmArgs::ln_*, gemm256p_kernel<..., LNX>) and sets ln_fused, otherwise the caller launches it.
-  bool ln_fused = false;
-  uint32_t ln_launch = 0;              // LNX launches of this call so far: the count an image's word reaches is launch number x nbn
-  // small batch: does the GEMM [M][K] x [N][K] run as gemm64c_kernel (bias rows computed inside)?  ...and may it also add up the
-  // mean rows from the LayerNorm's partials (FOLD)?  ln_partial: set by layernorm() when it left the mean rows to its consumer.
-  auto small_fused = [&](int N, int K) {
-    return comp && M <= G64_MAXM && (size_t)M * K < (1ull << 31) && (size_t)N * K < (1ull << 31) && N % SBN == 0 && K % 64 == 0 && S >= 9;
-  };
-  const float* ln_partial = nullptr;
-  const bool can_fuse_ln = ws.ln_cnt != nullptr && ws.ln_part != nullptr && (size_t)M * E * 4 < (1ull << 32) && E <= 1024;
-  // the persistent form of an LNX launch keeps the nbn column tiles of an image in one round (tile_origin_x): the counts must divide
-  auto lnx_persistent = [&](int nbm_, int nbn_) {
-    const int nt = nbm_ * nbn_;
-    if (ncu % 8 || nt % ncu || nbm_ % 8) return false;
-    const int Wx = ncu / 8, odd = Wx % nbn_, R = nt / ncu;
-    return Wx >= nbn_ && (odd == 0 || R % nbn_ == 0);
-  };
-  auto lnx_args = [&](GemmArgs& a, const float* ln_s, const float* ln_b, int nbn_) {
-    a.ln_out = ws.h; a.ln_scale = ln_s; a.ln_bias = ln_b; a.ln_abar = comp ? ws.abar : nullptr; a.ln_cnt = ws.ln_cnt; a.ln_part = ws.ln_part;
-    a.out_bytes = (uint32_t)((size_t)M * E * 4);
-    a.part_bytes = (uint32_t)((size_t)B * nbn_ * 256 * 16);
-    a.ln_tag = ++ln_launch;
-    a.ln_target = ln_launch * (uint32_t)nbn_;
-    a.ln_spin = ws.ln_spin;
-    if (lnx_persistent((int)a.nbm, nbn_)) {
-      const int Wx = ncu / 8, R = a.nbm * nbn_ / ncu;
-      a.lnx_G = Wx / nbn_; a.lnx_rows_aligned = R * a.lnx_G; a.lnx_rounds_div = R / nbn_; a.lnx_rows_xcd = a.nbm / 8;
-      a.lnx_rcp = (65536 + nbn_ - 1) / nbn_;
+  bool ln_fused = false;               // the last GEMM ran the LayerNorm behind it in its epilogue
+  uint32_t ln_launch = 0;              // such launches of this call so far: the count an image's word reaches is launch number x nbn
+  const float* ln_partial = nullptr;   // the last LayerNorm left adding up the mean rows to its consumer GEMM (plan_norm's fold)
+  // ---- one dense product as plan_gemm lays it out.  a: A, W, M, N, K, bias, aux, out, qcols of the product; dW = the rounding
+  // residue of W x 4096 (the mean rows of the activation operand are in ws.abar, written by the kernel that produced the operand);
+  // ln_s / ln_b: scale and bias of the LayerNorm that reads the output next, or null.  Returns whether the epilogue wrote the mean
+  // rows of the output (`colmean`, GELU on image-aligned tiles).
+  auto gemm = [&](int epi, GemmArgs a, const void* dW, int cat, const float* ln_s = nullptr, const float* ln_b = nullptr, void* colmean = nullptr) -> bool {
+    const GemmPlan p = plan_gemm(z, epi, a.N, a.K, cat, ln_s != nullptr, ln_partial != nullptr);
+    if (p.small) {
+      GemmArgs c = a;                                  // the B CLS rows (+ the 2 B mean rows -> ws.corr)
+      if (p.aligned) {
+        c.M = B; c.row0 = 0; c.row_step = S;
+        if (comp) { c.abar2 = ws.abar; c.dW2 = dW; c.corr2 = ws.corr; c.M2 = 2 * B; }
+      } else {
+        c = GemmArgs{ws.abar, dW, 2 * B, a.N, a.K, a.bias, nullptr, ws.corr, P, S, 0, 1.f};   // the table alone
+      }
+      pf.begin(p.small.cat, st);
+      HVLA_LAUNCH(Kern::gemm()[p.small.kernel], grid_of(p.small), dim3(p.small.block), p.small.lds, st, c);
+      pf.end(p.small.cat, st);
     }
+    if (p.aligned) {
+      a.nbm = p.nbm; a.tile_row0 = p.tile_row0; a.tile_stride = p.tile_stride; a.colmean = colmean;
+      if (epi != EPI_PATCH) a.corr = comp ? ws.corr : nullptr;
+    } else if (p.fused_bias) {                         // the bias rows are computed inside the GEMM
+      a.abar2 = ws.abar; a.dW2 = dW; a.M2 = 2 * B;
+      if (p.fold) { a.ln_partial = ln_partial; ln_partial = nullptr; }
+    } else if (p.small) {
+      a.corr = ws.corr;
+    }
+    if (p.ln_fused) {
+      a.hsplit = hsplit;
+      a.ln_out = ws.h; a.ln_scale = ln_s; a.ln_bias = ln_b; a.ln_abar = comp ? ws.abar : nullptr; a.ln_cnt = ws.ln_cnt; a.ln_part = ws.ln_part;
+      a.out_bytes = (uint32_t)((size_t)M * E * 4);
+      a.part_bytes = (uint32_t)((size_t)B * p.nbn * 256 * 16);
+      a.ln_tag = ++ln_launch;
+      a.ln_target = ln_launch * (uint32_t)p.nbn;
+      a.ln_spin = ws.ln_spin;
+      a.lnx_G = p.lnx_G; a.lnx_rows_aligned = p.lnx_rows_aligned; a.lnx_rounds_div = p.lnx_rounds_div; a.lnx_rows_xcd = p.lnx_rows_xcd; a.lnx_rcp = p.lnx_rcp;
+    }
+    ln_fused = p.ln_fused;
+    const int bracket = epi == EPI_PATCH ? -1 : p.main.cat;   // (the patch product is timed together with im2col, by the caller)
+    pf.begin(bracket, st);
+    HVLA_LAUNCH(Kern::gemm()[p.main.kernel], grid_of(p.main), dim3(p.main.block), p.main.lds, st, a);
+    pf.end(bracket, st);
+    return p.aligned;
   };
-  auto gemm = [&](auto epic, const void* A, const void* Wt, const void* dW, int N, int K, const float* bias, const float* aux,
-                  void* out, int qcols, int cat, void* colmean = nullptr, const float* ln_s = nullptr, const float* ln_b = nullptr) -> bool {
-    constexpr int EPI = decltype(epic)::value;
-    ln_fused = false;
+  auto layer_gemm = [&](const void* A, const void* Wt, int N, int K, const float* bias, const float* aux, void* out, int qcols) {
     GemmArgs a{A, Wt, M, N, K, bias, aux, out, P, S, qcols, qcols ? 0.125f * 1.4426950408889634f : 1.f / 256.f};   // q: 1/sqrt(64) and exp -> exp2
     a.hsplit = hsplit;
-    const bool fits32 = (size_t)M * K < (1ull << 31) && (size_t)N * K < (1ull << 31);
-    // N % 256 != 0 (DINOv2-small: 384, 1152): the last tile column is 64, 128 or 192 wide, the rest of its MFMAs wasted (33 % at
-    // N = 384) -- still twice as fast as the 128 x 128 register-staged kernel
-    const bool aligned = P == HBM_ && N % SBN == 0 && N >= HBN_ && M > G64_MAXM && K >= 128 && K % 64 == 0 && fits32;
-    if (aligned) {
-      pf.begin(CAT_COMP, st);
-      GemmArgs c = a;                                  // the B CLS rows (+ the B mean rows -> ws.corr)
-      c.M = B; c.row0 = 0; c.row_step = S;
-      int nblocks = ((B + SBM - 1) / SBM) * (N / SBN);
-      if (comp) { c.abar2 = ws.abar; c.dW2 = dW; c.corr2 = ws.corr; c.M2 = 2 * B; nblocks += ((2 * B + SBM - 1) / SBM) * (N / SBN); }   // two mean rows per image
-      if constexpr (EPI != EPI_PATCH) {
-        // (a three-stage form, three workgroups per CU for the launches above 512 blocks, was tried: run-to-run different
-        // tokens in ~4 % of the episodes of a 1024-episode batch, whichever order the reads and the DMA issue are in, while
-        // the four- and six-stage forms are clean -- not understood, not used: profiles/r3_experiments_not_kept.txt)
-        if (nblocks > ncu) HVLA_LAUNCH((gemm64_kernel<Op, EPI, 4>), dim3(nblocks), dim3(256), 4 * 16384, st, c);   // two workgroups per CU
-        else HVLA_LAUNCH((gemm64_kernel<Op, EPI>), dim3(nblocks), dim3(256), SNS * 16384, st, c);
-      } else {
-        HVLA_LAUNCH((gemm64_kernel<Op, EPI>), dim3(nblocks), dim3(256), SNS * 16384, st, c);
-      }
-      pf.end(CAT_COMP, st);
-      const int nbn = (N + HBN_ - 1) / HBN_;
-      a.corr = comp ? ws.corr : nullptr;
-      a.nbm = B; a.tile_row0 = 1; a.tile_stride = S; a.colmean = colmean;
-      const size_t lds = 131072;
-      pf.begin(cat, st);
-      if constexpr (EPI == EPI_RES) {
-        if (ln_s && can_fuse_ln) {                     // the LayerNorm behind this GEMM inside its epilogue
-          lnx_args(a, ln_s, ln_b, nbn);
-          const bool nt = big_output(M, N, sizeof(float));      // a big batch: the residual rows are read past L2 (below)
-          if (lnx_persistent(B, nbn)) {
-            if (nt) HVLA_LAUNCH((gemm256p_kernel<Op, EPI, true, true, true>), dim3(ncu), dim3(512), lds, st, a);
-            else HVLA_LAUNCH((gemm256p_kernel<Op, EPI, true, true>), dim3(ncu), dim3(512), lds, st, a);
-          } else {
-            if (nt) HVLA_LAUNCH((gemm256p_kernel<Op, EPI, false, true, true>), dim3(B * nbn), dim3(512), lds, st, a);
-            else HVLA_LAUNCH((gemm256p_kernel<Op, EPI, false, true>), dim3(B * nbn), dim3(512), lds, st, a);
-          }
-          pf.end(cat, st);
-          ln_fused = true;
-          return true;
-        }
-      }
-      if constexpr (EPI != EPI_PATCH) {
-        // a big batch: the 16-bit output goes past L2, the f32 residual rows are read past it (see the epilogue)
-        // (the 16-bit NT stores carry 32-bit BYTE offsets: an output of 4 GiB or more takes the plain form -- ADVICE r5)
-        if (big_output(M, N, EPI == EPI_RES ? sizeof(float) : sizeof(T)) && (EPI == EPI_RES || nt16_addressable(M, N, sizeof(T)))) {
-          if ((B * nbn) % ncu == 0) HVLA_LAUNCH((gemm256p_kernel<Op, EPI, true, false, true>), dim3(ncu), dim3(512), lds, st, a);
-          else HVLA_LAUNCH((gemm256p_kernel<Op, EPI, false, false, true>), dim3(B * nbn), dim3(512), lds, st, a);
-          pf.end(cat, st);
-          return true;
-        }
-      }
-      if ((B * nbn) % ncu == 0) HVLA_LAUNCH((gemm256p_kernel<Op, EPI, true>), dim3(ncu), dim3(512), lds, st, a);
-      else HVLA_LAUNCH((gemm256p_kernel<Op, EPI, false>), dim3(B * nbn), dim3(512), lds, st, a);
-      pf.end(cat, st);
-      return true;
-    }
-    if constexpr (EPI != EPI_PATCH) {
-      // (S >= 9: a block's 64 rows then belong to at most 8 images = the 16 rows of the kernels' bias-row tile)
-      if (small_fused(N, K)) {                           // small batch: the bias rows are computed inside the GEMM
-        a.abar2 = ws.abar; a.dW2 = dW; a.M2 = 2 * B;
-        pf.begin(cat, st);                               // (no launch of its own for the bias rows: nothing is timed as HVLA_PROF_COMP)
-        const int nb64 = ((M + SBM - 1) / SBM) * (N / SBN);
-        if constexpr (EPI != EPI_RES) {
-          if (ln_partial) {                              // the LayerNorm in front left the mean rows to this launch
-            a.ln_partial = ln_partial;
-            ln_partial = nullptr;
-            HVLA_LAUNCH((gemm64c_kernel<Op, EPI, true>), dim3(nb64), dim3(256), gemm64c_fold_lds(K), st, a);
-            pf.end(cat, st);
-            return false;
-          }
-        }
-        if constexpr (EPI == EPI_RES) {
-          if (2 * nb64 <= ncu) {                     // less than half of the chip: 64 x 32 tiles on twice as many CUs
-            HVLA_LAUNCH((gemm64c32_kernel<Op>), dim3(2 * nb64), dim3(256), SNS32 * SST32, st, a);
-            pf.end(cat, st);
-            return false;
-          }
-        }
-        HVLA_LAUNCH((gemm64c_kernel<Op, EPI>), dim3(nb64), dim3(256), SNSC * SSTC, st, a);
-        pf.end(cat, st);
-        return false;
-      }
-    }
-    if (comp) {                                        // the same gemm64_body<EPI_CORR> arithmetic as the fused launch above
-      pf.begin(CAT_COMP, st);
-      GemmArgs c{ws.abar, dW, 2 * B, N, K, bias, nullptr, ws.corr, P, S, 0, 1.f};
-      HVLA_LAUNCH((gemm64_kernel<Op, EPI_CORR>), dim3(((2 * B + SBM - 1) / SBM) * (N / SBN)), dim3(256), SNS * 16384, st, c);
-      a.corr = ws.corr;
-      pf.end(CAT_COMP, st);
-    }
-    pf.begin(cat, st);
-    if (M <= G64_MAXM && fits32 && N % SBN == 0 && K % 64 == 0)
-      HVLA_LAUNCH((gemm64_kernel<Op, EPI>), dim3(((M + SBM - 1) / SBM) * (N / SBN)), dim3(256), SNS * 16384, st, a);
-    else
-      HVLA_LAUNCH((gemm_kernel<Op, EPI>), dim3(((M + GBM - 1) / GBM) * (N / GBN)), dim3(256), gsm, st, a);
-    pf.end(cat, st);
-    return false;
+    return a;
   };
-  // Nnext: width of the GEMM that reads the output.  scratch / scratch_cols: a 16-bit [M][scratch_cols] workspace buffer that is free
-  // from this launch until its consumer GEMM has ENDED (norm1: ws.g, QKV writes ws.qkv; norm2: ws.qkv, fc1 writes ws.g), for the
-  // partial column sums [B][LNG][E] f32
-  auto layernorm = [&](const float* sc, const float* bi, int Nnext, void* scratch, int scratch_cols) {   // norm1 / norm2 (+ the column sums of the output)
-    const bool room = (size_t)LNG * E * sizeof(float) <= (size_t)S * scratch_cols * sizeof(T);
-    float* partial = comp && room ? reinterpret_cast<float*>(scratch) : nullptr;
-    HVLA_LAUNCH((layernorm_group_kernel<Op>), dim3(LNG, B), dim3(LNW * 64), (size_t)(P / 8) * E * sizeof(float), st, ws.x,
-                       reinterpret_cast<T*>(ws.h), sc, bi, partial, S, P, E);
-    if (!partial) return;
-    // (one launch with the image's last workgroup to arrive -- ticket by atomicAdd behind a __threadfence -- adding the
-    // partials was tried: 14.0 us against 5.2 + 4.7 for the two launches, profiles/r3_experiments_not_kept.txt)
-    // B = 1: every workgroup of the consumer GEMM adds the partials up itself (gemm64c_kernel, FOLD) -- while that GEMM is ONE round
-    // of workgroups (round 4, same box: B = 1 1.250 against 1.270 ms per step with the separate launch; B = 4 1.93 against 1.85).
-    if (small_fused(Nnext, E) && gemm64c_fold_lds(E) <= 160 * 1024 && ((M + SBM - 1) / SBM) * (Nnext / SBN) <= ncu) {
-      ln_partial = partial;
-      return;
-    }
-    HVLA_LAUNCH((layernorm_mean_kernel<Op>), dim3(2 * B), dim3(256), 0, st, partial, reinterpret_cast<T*>(ws.abar), P, E);
-  };
-  auto colmean_of = [&](const void* act, int K) {      // mean row of a GEMM output whose epilogue did not write it (no image-aligned tiles)
-    if (!comp) return;
-    HVLA_LAUNCH((colmean_kernel<T>), dim3((K + 255) / 256, B), dim3(256), 0, st, reinterpret_cast<const T*>(act),
-                       reinterpret_cast<T*>(ws.abar), S, P, K);
+  // norm1 / norm2 as a launch of their own (+ the column sums of the output).  Nnext: width of the GEMM that reads the output.
+  // scratch / scratch_cols: a 16-bit [M][scratch_cols] workspace buffer that is free from this launch until its consumer GEMM has
+  // ENDED (norm1: ws.g, QKV writes ws.qkv; norm2: ws.qkv, fc1 writes ws.g), for the partial column sums [B][LNG][E] f32
+  auto layernorm = [&](const float* sc, const float* bi, int Nnext, void* scratch, int scratch_cols) {
+    const NormPlan n = plan_norm(z, Nnext, scratch_cols);
+    float* partial = n.partial ? reinterpret_cast<float*>(scratch) : nullptr;
+    pf.begin(n.group.cat, st);
+    HVLA_LAUNCH(Kern::ln_group(), grid_of(n.group), dim3(n.group.block), n.group.lds, st, ws.x, reinterpret_cast<T*>(ws.h), sc, bi, partial, S, P, E);
+    if (n.fold) ln_partial = partial;
+    else if (n.mean) HVLA_LAUNCH((layernorm_mean_kernel<Op>), grid_of(n.mean), dim3(n.mean.block), 0, st, partial, reinterpret_cast<T*>(ws.abar), P, E);
+    pf.end(n.group.cat, st);
   };
   auto audit_of = [&](const void* buf, size_t n, int site) {      // site: 0 LayerNorm out, 1 q/k/v, 2 attention out, 3 GELU out
     if (!audit) return;
     HVLA_LAUNCH((absmax_kernel<T>), dim3(1024), dim3(256), 0, st, reinterpret_cast<const T*>(buf), n / 8, audit + 2 * site);
   };
   // the images' arrival words of the fused LayerNorms: zero before the first launch of every call (a memset node when the call is captured)
-  if (can_fuse_ln && P == HBM_ && M > G64_MAXM) {
-    if ((e = hipMemsetAsync(ws.ln_cnt, 0, (size_t)((B * 4 + 15) / 16 * 16), st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(ws.ln_part, 0, (size_t)B * ((E + HBN_ - 1) / HBN_) * 256 * 16, st)) != hipSuccess) return e;   // the entries' tags
+  if (call.cnt_bytes) {
+    if ((e = hipMemsetAsync(ws.ln_cnt, 0, call.cnt_bytes, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(ws.ln_part, 0, call.part_bytes, st)) != hipSuccess) return e;   // the entries' tags
     pf.nlaunch += 2;
   }
-  using EQ = std::integral_constant<int, EPI_QKV>;
-  using EG = std::integral_constant<int, EPI_GELU>;
-  using ER = std::integral_constant<int, EPI_RES>;
-  // patch embedding
-  pf.begin(0, st);
-  {
-    const size_t total = (size_t)B * P * (Kp / 16);
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    HVLA_LAUNCH(im2col_kernel<Op>, dim3(blocks), dim3(256), 0, st, images, reinterpret_cast<T*>(ws.g), B,
-                       g.image_size, g.patch, g.grid(), Kp, ws.x, w.pos, S, E);
-    const int Mp = B * P;
-    GemmArgs a{ws.g, w.w_patch, Mp, E, Kp, w.b_patch, w.pos, ws.x, P, S, 0, 1.f / 256.f};
-    const bool fits32 = (size_t)Mp * Kp < (1ull << 31);
-    if (Mp % HBM_ == 0 && E % SBN == 0 && E >= HBN_ && Mp > G64_MAXM && fits32) {
-      a.nbm = Mp / HBM_; a.tile_row0 = 0; a.tile_stride = HBM_;
-      const int nbn = (E + HBN_ - 1) / HBN_;
-      if (P == HBM_ && can_fuse_ln && g.enc_layers > 0) {   // a tile row is an image: norm1 of layer 0 inside the epilogue (the CLS rows are written above)
-        a.hsplit = hsplit;
-        lnx_args(a, w.layer[0].ln1_s, w.layer[0].ln1_b, nbn);
-        if (lnx_persistent(a.nbm, nbn)) HVLA_LAUNCH((gemm256p_kernel<Op, EPI_PATCH, true, true>), dim3(ncu), dim3(512), 131072, st, a);
-        else HVLA_LAUNCH((gemm256p_kernel<Op, EPI_PATCH, false, true>), dim3(a.nbm * nbn), dim3(512), 131072, st, a);
-        ln_fused = true;
-      } else if ((a.nbm * nbn) % ncu == 0) HVLA_LAUNCH((gemm256p_kernel<Op, EPI_PATCH, true>), dim3(ncu), dim3(512), 131072, st, a);
-      else HVLA_LAUNCH((gemm256p_kernel<Op, EPI_PATCH, false>), dim3(a.nbm * nbn), dim3(512), 131072, st, a);
-    } else if (Mp <= G64_MAXM && fits32 && E % SBN == 0) {
-      HVLA_LAUNCH((gemm64_kernel<Op, EPI_PATCH>), dim3(((Mp + SBM - 1) / SBM) * (E / SBN)), dim3(256), SNS * 16384, st, a);
-    } else {
-      HVLA_LAUNCH((gemm_kernel<Op, EPI_PATCH>), dim3(((Mp + GBM - 1) / GBM) * (E / GBN)), dim3(256), gsm, st, a);
-    }
-  }
-  pf.end(0, st);
-  const int KT = (S + 31) / 32;     // S = 32 * (KT - 1) + 1
-  const size_t asm_bytes = (size_t)KT * 32 * 2 * AVLD * sizeof(T) + (size_t)KT * APS * sizeof(float) + 64 * sizeof(T) +
-                           (size_t)(KT - 1) * 64 * sizeof(float);
+  // patch embedding (a tile row that is an image: norm1 of layer 0 inside the epilogue; the CLS rows are written by im2col)
+  pf.begin(call.im2col.cat, st);
+  HVLA_LAUNCH(im2col_kernel<Op>, grid_of(call.im2col), dim3(call.im2col.block), 0, st, images, reinterpret_cast<T*>(ws.g), B,
+              g.image_size, g.patch, g.grid(), call.Kp, ws.x, w.pos, S, E);
+  gemm(EPI_PATCH, GemmArgs{ws.g, w.w_patch, B * P, E, call.Kp, w.b_patch, w.pos, ws.x, P, S, 0, 1.f / 256.f}, nullptr, call.im2col.cat,
+       g.enc_layers > 0 ? w.layer[0].ln1_s : nullptr, g.enc_layers > 0 ? w.layer[0].ln1_b : nullptr);
+  pf.end(call.im2col.cat, st);
 #ifdef HVLA_BENCH_HOOKS
   int products = 0;
 #define HVLA_STOP_HERE() do { if (ws.stop_after > 0 && ++products == ws.stop_after) return hipGetLastError(); } while (0)
@@ -2687,56 +2563,42 @@ static hipError_t run_encoder(const Geom& g, const EncWeights& w, const EncWorks
 #endif
   for (int l = 0; l < g.enc_layers; ++l) {
     const EncLayerW& L = w.layer[l];
-    if (!ln_fused) {                    // norm1: otherwise done as the tail of the previous layer's fc2 / of the patch embedding
-      pf.begin(1, st);
-      layernorm(L.ln1_s, L.ln1_b, 3 * E, ws.g, F);
-      pf.end(1, st);
-    }
+    if (!ln_fused) layernorm(L.ln1_s, L.ln1_b, 3 * E, ws.g, F);   // norm1: otherwise done as the tail of the previous layer's fc2 / of the patch embedding
     audit_of(ws.h, (size_t)M * E, 0);
-    gemm(EQ{}, ws.h, L.wqkv, L.dqkv, 3 * E, E, L.bqkv, nullptr, ws.qkv, E, 2);                       // the LayerNorm wrote the mean row itself
+    gemm(EPI_QKV, layer_gemm(ws.h, L.wqkv, 3 * E, E, L.bqkv, nullptr, ws.qkv, E), L.dqkv, 2);        // the LayerNorm wrote the mean row itself
     audit_of(ws.qkv, (size_t)M * 3 * E, 1);
     HVLA_STOP_HERE();
-    pf.begin(3, st);
-    const bool att_unrolled = KT == 9;
-    auto attn = [&](auto kern, size_t lds) {
-      HVLA_LAUNCH(kern, dim3(B * H), dim3((KT - 1) * 64), lds, st, reinterpret_cast<const T*>(ws.qkv), reinterpret_cast<T*>(ws.h), S, E, H,
-                  comp ? reinterpret_cast<T*>(ws.abar) : nullptr, ws.amap ? ws.amap + (size_t)l * H * (S - 1) : nullptr, g.enc_layers * H * (S - 1)
+    pf.begin(call.attention.cat, st);
+    HVLA_LAUNCH(Kern::attn()[call.attention.kernel], grid_of(call.attention), dim3(call.attention.block), call.attention.lds, st,
+                reinterpret_cast<const T*>(ws.qkv), reinterpret_cast<T*>(ws.h), S, E, H, comp ? reinterpret_cast<T*>(ws.abar) : nullptr,
+                ws.amap ? ws.amap + (size_t)l * H * (S - 1) : nullptr, g.enc_layers * H * (S - 1)
 #ifdef HVLA_BENCH_HOOKS
-                  , (unsigned long long*)nullptr, 0     // (default arguments do not travel through a function pointer)
+                , (unsigned long long*)nullptr, 0     // (default arguments do not travel through a function pointer)
 #endif
-                  );
-    };
-    if (ws.amap) {                     // (unrolled, the attention-map instantiation spills: it stays rolled)
-      attn(attention_kernel<Op, true>, asm_bytes + (size_t)(KT * 32 + 32) * sizeof(float));
-    } else {
-      if (att_unrolled) attn(attention_kernel<Op, false, 8>, asm_bytes);
-      else attn(attention_kernel<Op, false>, asm_bytes);
-    }
-    pf.end(3, st);
+                );
+    pf.end(call.attention.cat, st);
     audit_of(ws.h, (size_t)M * E, 2);
-    gemm(ER{}, ws.h, L.wo, L.dwo, E, E, L.bo, L.ls1, ws.x, 0, 4, nullptr, L.ln2_s, L.ln2_b);   // the attention kernel wrote the mean row itself; norm2 as the tail
-    if (!ln_fused) {
-      pf.begin(1, st);
-      layernorm(L.ln2_s, L.ln2_b, F, ws.qkv, 3 * E);
-      pf.end(1, st);
-    }
+    gemm(EPI_RES, layer_gemm(ws.h, L.wo, E, E, L.bo, L.ls1, ws.x, 0), L.dwo, 4, L.ln2_s, L.ln2_b);   // the attention kernel wrote the mean row itself; norm2 as the tail
+    if (!ln_fused) layernorm(L.ln2_s, L.ln2_b, F, ws.qkv, 3 * E);
     HVLA_STOP_HERE();
     audit_of(ws.h, (size_t)M * E, 0);
-    const bool summed = gemm(EG{}, ws.h, L.w1, L.dw1, F, E, L.b1, nullptr, ws.g, 0, 5, comp ? ws.abar : nullptr);
+    const bool summed = gemm(EPI_GELU, layer_gemm(ws.h, L.w1, F, E, L.b1, nullptr, ws.g, 0), L.dw1, 5, nullptr, nullptr, comp ? ws.abar : nullptr);
     audit_of(ws.g, (size_t)M * F, 3);
-    if (!summed) colmean_of(ws.g, F);                                                 // aligned tiles: the GELU epilogue wrote the mean row
+    if (!summed && call.colmean)        // no image-aligned tiles: the GELU epilogue did not write the mean row of its output
+      HVLA_LAUNCH((colmean_kernel<T>), grid_of(call.colmean), dim3(call.colmean.block), 0, st, reinterpret_cast<const T*>(ws.g),
+                  reinterpret_cast<T*>(ws.abar), S, P, F);
     HVLA_STOP_HERE();
-    if (l + 1 < g.enc_layers) gemm(ER{}, ws.g, L.w2, L.dw2, E, F, L.b2, L.ls2, ws.x, 0, 6, nullptr, w.layer[l + 1].ln1_s, w.layer[l + 1].ln1_b);   // the next layer's norm1 as the tail
-    else gemm(ER{}, ws.g, L.w2, L.dw2, E, F, L.b2, L.ls2, ws.x, 0, 6);
+    const EncLayerW* next = l + 1 < g.enc_layers ? &w.layer[l + 1] : nullptr;                         // the next layer's norm1 as the tail
+    gemm(EPI_RES, layer_gemm(ws.g, L.w2, E, F, L.b2, L.ls2, ws.x, 0), L.dw2, 6, next ? next->ln1_s : nullptr, next ? next->ln1_b : nullptr);
     HVLA_STOP_HERE();
   }
 #undef HVLA_STOP_HERE
-  pf.begin(1, st);
+  pf.begin(call.final_norm.cat, st);
   if (keep_cls)
-    HVLA_LAUNCH((layernorm_kernel<Op, 2>), dim3((M + 3) / 4), dim3(256), 0, st, ws.x, tokens, w.lnf_s, w.lnf_b, M, E, S);
+    HVLA_LAUNCH((layernorm_kernel<Op, 2>), grid_of(call.final_norm), dim3(call.final_norm.block), 0, st, ws.x, tokens, w.lnf_s, w.lnf_b, M, E, S);
   else
-    HVLA_LAUNCH((layernorm_kernel<Op, 1>), dim3((M + 3) / 4), dim3(256), 0, st, ws.x, tokens, w.lnf_s, w.lnf_b, M, E, S);
-  pf.end(1, st);
+    HVLA_LAUNCH((layernorm_kernel<Op, 1>), grid_of(call.final_norm), dim3(call.final_norm.block), 0, st, ws.x, tokens, w.lnf_s, w.lnf_b, M, E, S);
+  pf.end(call.final_norm.cat, st);
   return hipGetLastError();
 }
 
@@ -2760,31 +2622,15 @@ hipError_t debug_gemm(const void* A, const void* W, const float* bias, const flo
   GemmArgs a{A, W, M, N, K, bias, aux, out, 256, 257, epi == EPI_QKV ? N / 3 : 0, 0.125f};
   a.nbm = M / HBM_; a.tile_row0 = 0; a.tile_stride = HBM_;
   if (epi < EPI_QKV || epi > EPI_RES || variant < 0 || variant > 3 || N % HBN_ || K % 64 || (variant >= 2 && a.nbm < 1)) return hipErrorInvalidValue;
-  int dev = 0, ncu = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const size_t gsm = (size_t)2 * (GBM + GBN) * GLD * 2;
-  auto launch_e = [&](auto epic) {
-    constexpr int EPI = decltype(epic)::value;
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<Op, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm64_kernel<Op, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256p_kernel<Op, EPI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm256p_kernel<Op, EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
-    const int nt = a.nbm * (N / HBN_);
-    if (variant == 0) hipLaunchKernelGGL((gemm_kernel<Op, EPI>), dim3(((M + GBM - 1) / GBM) * (N / GBN)), dim3(256), gsm, st, a);
-    else if (variant == 1) hipLaunchKernelGGL((gemm64_kernel<Op, EPI>), dim3(((M + SBM - 1) / SBM) * (N / SBN)), dim3(256), SNS * 16384, st, a);
-    else if (variant == 2) hipLaunchKernelGGL((gemm256p_kernel<Op, EPI, false>), dim3(nt), dim3(512), 131072, st, a);
-    else hipLaunchKernelGGL((gemm256p_kernel<Op, EPI, true>), dim3(nt < ncu ? nt : ncu), dim3(512), 131072, st, a);
-  };
-  auto launch = [&]() {
-    if (epi == EPI_QKV) launch_e(std::integral_constant<int, EPI_QKV>{});
-    else if (epi == EPI_GELU) launch_e(std::integral_constant<int, EPI_GELU>{});
-    else launch_e(std::integral_constant<int, EPI_RES>{});
-  };
+  int ncu = 256;
+  (void)device_setup<Op>(ncu);
+  const int nt = a.nbm * (N / HBN_);
+  const Launch forms[4] = {{G128_PATCH + epi, (unsigned)(((M + GBM - 1) / GBM) * (N / GBN)), 1, 256, (size_t)2 * (GBM + GBN) * GLD * 2},
+                           {G64_PATCH + epi, (unsigned)(((M + SBM - 1) / SBM) * (N / SBN)), 1, 256, (size_t)SNS * SST},
+                           {G256_PATCH + 2 * epi, (unsigned)nt, 1, 512, P256_LDS},
+                           {G256_PATCH + 2 * epi + 1, (unsigned)(nt < ncu ? nt : ncu), 1, 512, P256_LDS}};
+  const Launch& f = forms[variant];
+  auto launch = [&]() { hipLaunchKernelGGL(EncKernels<Op>::gemm()[f.kernel], grid_of(f), dim3(f.block), f.lds, st, a); };
   hipEvent_t e0, e1;
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
@@ -2799,21 +2645,17 @@ hipError_t debug_gemm(const void* A, const void* W, const float* bias, const flo
   (void)hipEventDestroy(e1);
   return hipGetLastError();
 }
-// phase stamps of attention_kernel (tools/attention_timeline.py): one launch over B * H workgroups on workspace-shaped buffers
+// phase stamps of attention_kernel (tools/attention_timeline.py): one launch over B * H workgroups on workspace-shaped buffers, the
+// instantiation and LDS size the step launches at this S
 hipError_t debug_attention_stamps(const void* qkv, void* o, void* omean, int B, int S, int E, int H, int wg, unsigned long long* stamps,
                                   hipStream_t st) {
   using Op = OpF16;
   using T = Op::elem;
-  const int KT = (S + 31) / 32;
-  const size_t asm_bytes = (size_t)KT * 32 * 2 * AVLD * sizeof(T) + (size_t)KT * APS * sizeof(float) + 64 * sizeof(T) +
-                           (size_t)(KT - 1) * 64 * sizeof(float);
-  auto go = [&](auto kern) {           // the instantiation the step launches at this S (run_encoder)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(B * H), dim3((KT - 1) * 64), asm_bytes, st, reinterpret_cast<const T*>(qkv),
-                       reinterpret_cast<T*>(o), S, E, H, reinterpret_cast<T*>(omean), (float*)nullptr, 0, stamps, wg);
-  };
-  if (KT == 9) go(attention_kernel<Op, false, 8>);
-  else go(attention_kernel<Op, false>);
+  int ncu = 256;
+  (void)device_setup<Op>(ncu);
+  const Launch at = plan_attention(B, S, H, sizeof(T), false);
+  hipLaunchKernelGGL(EncKernels<Op>::attn()[at.kernel], grid_of(at), dim3(at.block), at.lds, st, reinterpret_cast<const T*>(qkv),
+                     reinterpret_cast<T*>(o), S, E, H, reinterpret_cast<T*>(omean), (float*)nullptr, 0, stamps, wg);
   return hipGetLastError();
 }
 #endif  // HVLA_BENCH_HOOKS

@@ -1,6 +1,9 @@
-// CPU-only check of csrc/plan.h (the arithmetic-only launch decisions of run_encoder and the XCD tile order of the small GEMM
-// kernels).  Built and run by tests/test_host_sanitizers.py with g++ -fsanitize=address,undefined.
+// CPU-only check of csrc/plan.h (the launch plan of run_encoder and the XCD tile order of the small GEMM kernels).  Built and run
+// by tests/test_host_sanitizers.py with g++ -fsanitize=address,undefined; argv[1] = tests/native/encoder_plan_trace.txt, the
+// launches of the dispatch that plan.h replaced (recorded on the CPU from run_encoder with its launch macro turned into a logger).
 #include <cstdio>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "plan.h"
@@ -9,7 +12,120 @@ using namespace hvla;
 
 #define REQUIRE(c, ...) do { if (!(c)) { printf("FAILED %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); return 1; } } while (0)
 
-int main() {
+static const char* kernel_name(int k) {
+  static const char* const gemm[] = {
+#define HVLA_X(id, ...) #id,
+      HVLA_GEMM_KERNELS(HVLA_X)
+#undef HVLA_X
+  };
+  static const char* const other[] = {"IM2COL", "LN_GROUP", "LN_MEAN", "COLMEAN", "LN_FINAL"};
+  return k >= IM2COL ? other[k - IM2COL] : gemm[k];
+}
+static const char* const attn_name[NUM_ATTN_KERNELS] = {"ATT", "ATT_U", "ATT_MAP"};
+
+// One encode as run_encoder issues it: a line per launch (kernel id, grid, block, LDS bytes, category; the lnx_* numbers of a
+// persistent fused-LayerNorm launch).  Returns the number of launches (the two memsets count), -1 when the call is refused;
+// `bad` counts launches whose LDS size or kernel id is out of range.
+struct Walk {
+  std::string out;
+  int n = 0, bad = 0;
+  void line(const Launch& l, const char* name, const GemmPlan* g = nullptr) {
+    char buf[160];
+    int k = snprintf(buf, sizeof buf, "%s %u", name, l.grid);
+    if (l.grid_y != 1) k += snprintf(buf + k, sizeof buf - k, "x%u", l.grid_y);
+    k += snprintf(buf + k, sizeof buf - k, " %u %zu %d", l.block, l.lds, l.cat);
+    if (g && g->lnx_G) k += snprintf(buf + k, sizeof buf - k, " lnx %d %d %d %d %d", g->lnx_G, g->lnx_rows_aligned, g->lnx_rounds_div, g->lnx_rows_xcd, g->lnx_rcp);
+    out += buf;
+    out += '\n';
+    ++n;
+    if (l.lds > LDS_LIMIT || l.grid == 0 || l.block == 0 || l.block > 1024) ++bad;
+  }
+  void other(const Launch& l) { line(l, kernel_name(l.kernel)); }
+  void gemm(const GemmPlan& g) {
+    for (const Launch* l : {&g.small, &g.main}) {
+      if (!*l) continue;
+      if (l->kernel >= NUM_GEMM_KERNELS) ++bad;
+      line(*l, kernel_name(l->kernel), l == &g.main ? &g : nullptr);
+    }
+    if (!g.main) ++bad;
+  }
+  bool norm(const EncSizes& z, int Nnext, int scratch_cols) {
+    const NormPlan n = plan_norm(z, Nnext, scratch_cols);
+    other(n.group);
+    if (n.mean) other(n.mean);
+    return n.fold;
+  }
+  int encode(const EncSizes& z) {
+    const CallPlan c = plan_call(z);
+    if (!c.ok) { out += "REFUSED\n"; return -1; }
+    const int E = z.E, F = z.F;
+    if (c.cnt_bytes) {
+      out += "MEMSET " + std::to_string(c.cnt_bytes) + "\nMEMSET " + std::to_string(c.part_bytes) + "\n";
+      n += 2;
+    }
+    other(c.im2col);
+    GemmPlan g = plan_gemm(z, EPI_PATCH, E, c.Kp, 0, z.layers > 0, false);
+    gemm(g);
+    bool ln_fused = g.ln_fused;
+    for (int l = 0; l < z.layers; ++l) {
+      bool fold = !ln_fused && norm(z, 3 * E, F);
+      gemm(plan_gemm(z, EPI_QKV, 3 * E, E, 2, false, fold));
+      if (c.attention.kernel < 0 || c.attention.kernel >= NUM_ATTN_KERNELS) ++bad;
+      line(c.attention, attn_name[c.attention.kernel]);
+      g = plan_gemm(z, EPI_RES, E, E, 4, true, false);
+      gemm(g);
+      fold = !g.ln_fused && norm(z, F, 3 * E);
+      g = plan_gemm(z, EPI_GELU, F, E, 5, false, fold);
+      gemm(g);
+      if (!g.aligned && c.colmean) other(c.colmean);
+      g = plan_gemm(z, EPI_RES, E, F, 6, l + 1 < z.layers, false);
+      gemm(g);
+      ln_fused = g.ln_fused;
+    }
+    other(c.final_norm);
+    return n;
+  }
+};
+static int launches(const EncSizes& z) { Walk w; const int n = w.encode(z); return w.bad ? -2 : n; }
+
+struct Geo { const char* name; int image, patch, E, F, H; };
+static const Geo README = {"readme", 224, 14, 768, 3072, 12}, DINOV2S = {"dinov2s", 224, 14, 384, 1536, 6};
+static EncSizes sizes(const Geo& g, int B, int layers, int ncu = 256, bool comp = true, bool ln_ws = true) {
+  const int grid = g.image / g.patch, P = grid * grid;
+  return EncSizes{B, P, P + 1, g.E, g.F, g.H, g.patch, layers, ncu, 2, comp, ln_ws, false};
+}
+
+// gemm256p_kernel's tile_origin_x restated: with the plan's five lnx_* numbers, the ncu workgroups of a persistent fused-LayerNorm
+// launch cover every tile once in nbm * nbn / ncu rounds, and the nbn column tiles of an image either run in ONE round (on nbn
+// workgroups of one XCD label) or one after the other on one workgroup (all but the last `later`)
+static bool lnx_covers(const GemmPlan& p, int ncu) {
+  const int nbm = p.nbm, nbn = p.nbn, R = nbm * nbn / ncu;
+  if (nbm * nbn % ncu || ncu % 8) return false;
+  std::vector<int> round_of(nbm * nbn, -1), wg_of(nbm * nbn, -1);
+  for (int b = 0; b < ncu; ++b)
+    for (int rnd = 0; rnd < R; ++rnd) {
+      const int xcd = b & 7, w = b >> 3, wq = (w * p.lnx_rcp) >> 16, rq = (rnd * p.lnx_rcp) >> 16;
+      int row, col;
+      if (wq < p.lnx_G) { row = rnd * p.lnx_G + wq; col = w - wq * nbn; }
+      else { row = p.lnx_rows_aligned + (w - p.lnx_G * nbn) * p.lnx_rounds_div + rq; col = rnd - rq * nbn; }
+      const int tm = xcd * p.lnx_rows_xcd + row;
+      if (tm < 0 || tm >= nbm || col < 0 || col >= nbn || round_of[tm * nbn + col] >= 0) return false;
+      round_of[tm * nbn + col] = rnd;
+      wg_of[tm * nbn + col] = b;
+    }
+  for (int tm = 0; tm < nbm; ++tm) {
+    bool one_round = true, one_wg = true;
+    for (int c = 0; c < nbn; ++c) {
+      if (round_of[tm * nbn + c] < 0) return false;
+      one_round &= round_of[tm * nbn + c] == round_of[tm * nbn] && (wg_of[tm * nbn + c] & 7) == (wg_of[tm * nbn] & 7);
+      one_wg &= wg_of[tm * nbn + c] == wg_of[tm * nbn] && round_of[tm * nbn + c] == round_of[tm * nbn] + c;
+    }
+    if (!one_round && !one_wg) return false;
+  }
+  return true;
+}
+
+int main(int argc, char** argv) {
   // xcd_run: a bijection of [0, nwg) for every grid size, XCD x (= block id % 8) owning ONE contiguous run of tile indices
   for (int nwg = 1; nwg <= 4100; ++nwg) {
     std::vector<int> seen(nwg, 0), lo(8, nwg), hi(8, -1), cnt(8, 0);
@@ -49,6 +165,88 @@ int main() {
   REQUIRE(!nt16_addressable(2721 * S, F, 2), "B = 2721: %zu bytes wrap a 32-bit byte offset", 2721 * S * F * 2);
   REQUIRE(!nt16_addressable((size_t)1 << 16, (size_t)1 << 15, 2), "exactly 4 GiB");
   REQUIRE(nt16_addressable(((size_t)1 << 16) - 1, (size_t)1 << 15, 2), "one row below 4 GiB");
+  // ---- the launch counts the committed profiles pin (README geometry, 12 layers, compensation on, 256 CUs; the recorded totals
+  // are one higher: the policy's launch)
+  REQUIRE(launches(sizes(README, 1, 12)) == 99, "B = 1: %d launches (profiles/r6_bench_b1.json: 100 per step)", launches(sizes(README, 1, 12)));
+  REQUIRE(launches(sizes(README, 4, 12)) == 123, "B = 4: %d launches (r6_bench_b4.json: 124)", launches(sizes(README, 4, 12)));
+  for (int B : {8, 256, 1024}) REQUIRE(launches(sizes(README, B, 12)) == 113, "B = %d: %d launches (r6_bench_b256.json, r6_bench_b1024.json: 114)", B, launches(sizes(README, B, 12)));
+  REQUIRE(launches(sizes(DINOV2S, 256, 12)) == 113, "DINOv2-small, B = 256: %d launches (r6_bench_b256_dinov2_small.json: 114)", launches(sizes(DINOV2S, 256, 12)));
+  // ---- form boundaries
+  const int E = README.E, Fm = README.F;
+  {
+    const GemmPlan lo = plan_gemm(sizes(README, 7, 12), EPI_QKV, 3 * E, E, 2, false, false), hi = plan_gemm(sizes(README, 8, 12), EPI_QKV, 3 * E, E, 2, false, false);
+    REQUIRE(!lo.aligned && lo.fused_bias && lo.main.kernel == G64C_QKV && !lo.small, "2047 rows: 64 x 64 tiles, bias rows inside");
+    REQUIRE(hi.aligned && !hi.fused_bias && hi.main.kernel == G256_QKV && hi.small.kernel == G64_QKV && hi.nbm == 8 && hi.tile_row0 == 1 && hi.tile_stride == 257,
+            "2048 rows: image-aligned tiles behind the CLS / mean-row launch");
+    REQUIRE(plan_norm(sizes(README, 1, 12), 3 * E, Fm).fold && plan_gemm(sizes(README, 1, 12), EPI_QKV, 3 * E, E, 2, false, true).main.kernel == G64CF_QKV, "B = 1: QKV folds the LayerNorm's partials");
+    const NormPlan n2 = plan_norm(sizes(README, 2, 12), 3 * E, Fm);
+    REQUIRE(n2.partial && !n2.fold && n2.mean.kernel == LN_MEAN, "B = 2: QKV is more than one round, the mean rows get their launch");
+  }
+  const int ncus[4] = {256, 304, 64, 250};
+  for (int ncu : ncus)
+    for (int B = 1; B <= 7; ++B) {
+      const GemmPlan p = plan_gemm(sizes(README, B, 12, ncu), EPI_RES, E, E, 4, true, false);
+      const int nb64 = (B * 257 + 63) / 64 * (E / 64);
+      REQUIRE((p.main.kernel == G64C32) == (2 * nb64 <= ncu) && (int)p.main.grid == (2 * nb64 <= ncu ? 2 * nb64 : nb64), "B = %d, %d CUs: 64 x 32 tiles exactly below half of the chip", B, ncu);
+    }
+  for (int ncu : ncus) {
+    int persistent = 0;
+    for (int B = 8; B <= 2432; ++B) {
+      const GemmPlan p = plan_gemm(sizes(README, B, 12, ncu), EPI_RES, E, E, 4, true, false);
+      REQUIRE(p.ln_fused && p.nbn == 3 && p.nbm == B, "B = %d: the out-projection runs norm2 in its epilogue", B);
+      if (p.main.kernel == G256LN_RES_P || p.main.kernel == G256LNNT_RES_P) {
+        ++persistent;
+        REQUIRE((int)p.main.grid == ncu && lnx_covers(p, ncu), "B = %d, %d CUs: persistent, yet an image's column tiles do not share a round", B, ncu);
+      } else {
+        REQUIRE((int)p.main.grid == B * 3 && p.lnx_G == 0, "B = %d, %d CUs: one workgroup per tile", B, ncu);
+      }
+    }
+    // (three column tiles, 32 / 38 / 8 workgroups per XCD label: two left over, so the rounds must be a multiple of three)
+    REQUIRE(persistent == (ncu % 8 ? 0 : 2432 / ncu), "%d CUs: %d persistent batches", ncu, persistent);
+  }
+  {
+    const GemmPlan p = plan_gemm(sizes(README, 1024, 12), EPI_RES, E, E, 4, true, false);   // 3072 tiles on 256 CUs: 12 rounds
+    REQUIRE(p.main.kernel == G256LNNT_RES_P && p.lnx_G == 10 && p.lnx_rows_aligned == 120 && p.lnx_rounds_div == 4 && p.lnx_rows_xcd == 128 && p.lnx_rcp == 21846, "B = 1024: lnx numbers");
+    REQUIRE(p.lnx_rows_aligned + (256 / 8 - p.lnx_G * 3) * p.lnx_rounds_div == p.lnx_rows_xcd, "B = 1024: the groups' and the left-over workgroups' images add up");
+  }
+  REQUIRE(plan_gemm(sizes(README, 2720, 12), EPI_GELU, Fm, E, 5, false, false).main.kernel == G256NT_GELU, "B = 2720: fc1 stores non-temporally");
+  REQUIRE(plan_gemm(sizes(README, 2721, 12), EPI_GELU, Fm, E, 5, false, false).main.kernel == G256_GELU, "B = 2721: fc1's output is 4 GiB, the plain form");
+  {
+    int B = 1;
+    while ((size_t)B * 257 * Fm < ((size_t)1 << 32)) ++B;                        // 5441
+    REQUIRE(B == 5441 && plan_call(sizes(README, B - 1, 12)).ok && !plan_call(sizes(README, B, 12)).ok && launches(sizes(README, B, 12)) == -1, "refused from B = %d on", B);
+  }
+  // ---- the sweep: every planned LDS size within the limit, every kernel id inside its table, and the launches those of the recorded trace
+  std::string want;
+  if (argc > 1) {
+    FILE* f = fopen(argv[1], "rb");
+    REQUIRE(f != nullptr, "cannot open %s", argv[1]);
+    char buf[65536];
+    for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) want.append(buf, k);
+    fclose(f);
+  }
+  const Geo geos[4] = {README, DINOV2S, {"mid", 112, 14, 128, 512, 2}, {"wide64", 112, 14, 768, 3072, 12}};
+  const int Bs[14] = {1, 2, 4, 7, 8, 9, 64, 255, 256, 257, 1024, 2048, 2720, 2721};
+  size_t at = 0;
+  for (const Geo& g : geos)
+    for (int B : Bs)
+      for (int ncu : ncus)
+        for (int comp = 1; comp >= 0; --comp)
+          for (int lnws = 1; lnws >= 0; --lnws) {
+            if (ncu != 256 && !(comp && lnws)) continue;       // the other CU counts with everything on only: keeps the file small
+            Walk w;
+            char head[96];
+            snprintf(head, sizeof head, "# %s B %d ncu %d comp %d lnws %d\n", g.name, B, ncu, comp, lnws);
+            w.out = head;
+            const int n = w.encode(sizes(g, B, 2, ncu, comp != 0, lnws != 0));
+            REQUIRE(w.bad == 0, "%s: %d launches out of range", head, w.bad);
+            if (n >= 0) w.out += "= " + std::to_string(n) + "\n";
+            if (argc > 1) {
+              REQUIRE(want.compare(at, w.out.size(), w.out) == 0, "%sthe plan:\n%srecorded (from byte %zu):\n%s", head, w.out.c_str(), at, want.substr(at, w.out.size()).c_str());
+              at += w.out.size();
+            }
+          }
+  REQUIRE(argc > 1 && at == want.size() && at > 0, "usage: plan_check encoder_plan_trace.txt (%zu of %zu bytes matched)", at, want.size());
   printf("OK\n");
   return 0;
 }

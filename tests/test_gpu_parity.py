@@ -1097,6 +1097,23 @@ def test_tokens_are_the_same_whichever_gemm_kernel_computes_them():
     assert torch.equal(pair[1], ref[0]) and torch.equal(pair[0], last[0])
 
 
+@pytest.mark.gpu
+def test_launches_per_step_are_those_of_the_launch_plan(full):
+    """One sample_actions step enqueues what csrc/plan.h plans for the encoder (tests/native/plan_check.cpp counts the same plan on
+    the CPU: 99 / 123 / 113) plus the policy's one launch, in each of the three regimes: B = 1 (every small-batch form, the
+    LayerNorm's partials folded into its consumer), B = 4 (small batch, mean rows by their own launch) and B = 8 (image-aligned
+    tiles, fused LayerNorms, the two memsets).  100 and 124 are the recorded values of profiles/r6_bench_b1.json / r6_bench_b4.json,
+    114 that of r6_bench_b256.json / r6_bench_b1024.json."""
+    from hypervla import synthetic as syn
+    m, g = full["model"], full["g"]
+    for B, want in ((1, 100), (4, 124), (8, 114)):
+        ins, st = syn.synthetic_instructions(B, g), syn.synthetic_initial_state(B, g)
+        w, tasks, _ = m.create_tasks(instruction_dict=ins, initial_state=st)
+        m._ctx.launches()                                   # (reads and clears the count)
+        m.sample_actions(syn.synthetic_images(B, g), ins, tasks, np.ones((B, 1)), w)
+        assert m._ctx.launches() == want, B
+
+
 def _encode_in_a_fresh_process(code, flavour=None):
     import os, subprocess, sys
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

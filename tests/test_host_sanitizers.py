@@ -39,13 +39,15 @@ def test_layout_and_packing_under_asan_ubsan(tmp_path):
 def test_launch_plan_arithmetic_under_asan_ubsan(tmp_path):
     """csrc/plan.h: the XCD tile order of the small GEMM kernels is a bijection with one contiguous run per XCD at every grid size
     (a 64-column slice of W / dW on at most two XCDs at the B = 256 launch shapes), and the non-temporal 16-bit epilogue, whose
-    stores carry 32-bit BYTE offsets, is only chosen for outputs below 4 GiB (fc1 from B = 2721 on would wrap)."""
+    stores carry 32-bit BYTE offsets, is only chosen for outputs below 4 GiB (fc1 from B = 2721 on would wrap).  The
+    launch plan of an encoder call: the launch counts the committed profiles record, the boundaries between its forms, and, launch
+    for launch over a sweep of geometries, batches and CU counts, the trace recorded from the dispatch it replaced."""
     exe = tmp_path / "plan_check"
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
          "-Werror", "-I", os.path.join(ROOT, "hyper-vla_amd", "csrc"), os.path.join(ROOT, "tests", "native", "plan_check.cpp"),
          "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    run = subprocess.run([str(exe), os.path.join(ROOT, "tests", "native", "encoder_plan_trace.txt")], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
