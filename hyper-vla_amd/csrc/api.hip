@@ -84,6 +84,8 @@ struct hvla_ctx {
   std::vector<hvla_weights*> arena_pool;
   std::mutex pool_mu;                        // hvla_weights_free can arrive from another thread (Python's GC) than hvla_generate
   static constexpr size_t ARENA_POOL_MAX = 4;
+  int pos_n = 0;                 // hvla_train_position_source: side of the position table's source grid (0: the baked table is the parameter)
+  const float* pos_w = nullptr;  //   its [n, grid] resize weights (device, the caller's)
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
   ~hvla_ctx() {
@@ -701,14 +703,63 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* logits, const fl
   return HVLA_OK;
 }
 
+static PosSource pos_source(const hvla_ctx* ctx, bool train_encoder);
+
 int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[4]) {
   if (!ctx || !out) return HVLA_E_STATE;
   if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
   const TrainLayout L = make_train_layout(ctx->g);
-  out[0] = L.total + (train_encoder ? L.enc_total : 0); out[1] = L.G;
+  out[0] = L.total + (train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0); out[1] = L.G;
   out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0); out[3] = L.total;
+  return HVLA_OK;
+}
+
+// the position-table source as the training entries see it: off unless the encoder is trained
+static PosSource pos_source(const hvla_ctx* ctx, bool train_encoder) {
+  PosSource ps;
+  if (train_encoder && ctx->pos_n > 0) { ps.n = ctx->pos_n; ps.w = ctx->pos_w; ps.grid = ctx->g.image_size / ctx->g.patch; ps.E = ctx->g.E; }
+  return ps;
+}
+
+static int position_args(hvla_ctx* ctx, const void* a, int32_t n, const void* w, const void* b) {
+  if (!a || !w || !b) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  if (n < 2 || n > 1024) FAIL(ctx, HVLA_E_SHAPE, "source grid %d outside [2, 1024]", n);
+  if (((uintptr_t)a | (uintptr_t)b) % 16 != 0) FAIL(ctx, HVLA_E_SHAPE, "tables must be 16-byte aligned");
+  const int grid = ctx->g.image_size / ctx->g.patch;
+  if (grid * grid != ctx->g.P() || ctx->g.E % 4 != 0) FAIL(ctx, HVLA_E_SHAPE, "the context's patch grid is not square");
+  return HVLA_OK;
+}
+
+int hvla_position_interp(hvla_ctx* ctx, const float* src, int32_t n, const float* w, float* dst, void* stream) {
+  if (!ctx) return HVLA_E_STATE;
+  if (int rc = position_args(ctx, src, n, w, dst)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, launch_position_interp(src, n, w, dst, ctx->g.image_size / ctx->g.patch, ctx->g.E, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+int hvla_position_interp_adjoint(hvla_ctx* ctx, const float* ddst, int32_t n, const float* w, float* dsrc, void* stream) {
+  if (!ctx) return HVLA_E_STATE;
+  if (int rc = position_args(ctx, ddst, n, w, dsrc)) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, launch_position_adjoint(ddst, n, w, dsrc, ctx->g.image_size / ctx->g.patch, ctx->g.E, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
+int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w) {
+  if (!ctx) return HVLA_E_STATE;
+  if (n == 0) { ctx->pos_n = 0; ctx->pos_w = nullptr; return HVLA_OK; }
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
+  if (!w) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  if (n < 2 || n > 1024) FAIL(ctx, HVLA_E_SHAPE, "source grid %d outside [2, 1024]", n);
+  const TrainLayout L = make_train_layout(ctx->g);
+  // the kernels move 16 bytes at a time: the slot and the tail must start on a multiple of 4 elements of the flat vector
+  if ((L.total + L.e_pos) % 4 != 0 || (L.total + L.enc_total) % 4 != 0 || ctx->g.E % 4 != 0)
+    FAIL(ctx, HVLA_E_SHAPE, "the position table is not 16-byte aligned in this geometry's training vector");
+  ctx->pos_n = n;
+  ctx->pos_w = w;
   return HVLA_OK;
 }
 
@@ -739,7 +790,8 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
   const TrainHyper hp = to_hp(hy);
   for (hipEvent_t& e : ctx->ev_bucket)
     if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIPCHK(ctx, train_step(ctx->g, L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : ctx->ev_bucket));
+  HIPCHK(ctx, train_step(ctx->g, L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : ctx->ev_bucket,
+                         pos_source(ctx, images != nullptr)));
   // ONE pending backward per ctx: the bucket events belong to the last hvla_train_step that ran a backward pass, and
   // hvla_train_wait_bucket refers to that step.  A forward-only step (evaluation between a step and its apply) records
   // nothing and leaves the pending step's events alone.
@@ -754,7 +806,7 @@ int hvla_train_bucket_ranges(hvla_ctx* ctx, int32_t train_encoder, int64_t out[6
   if (!ctx || !out) return HVLA_E_STATE;
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
-  out[0] = L.total; out[1] = train_encoder ? L.enc_total : 0;     // the shared DINOv2 leaves
+  out[0] = L.total; out[1] = train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0;     // the shared DINOv2 leaves (+ the position source)
   out[2] = L.wcat; out[3] = L.total - L.wcat;                     // the output heads (W_cat, b_cat)
   out[4] = 0; out[5] = L.wcat;                                    // the context encoder
   return HVLA_OK;
@@ -793,7 +845,8 @@ int hvla_train_apply(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_tr
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
-  HIPCHK(ctx, train_apply(L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream)));
+  HIPCHK(ctx, train_apply(L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
+                          pos_source(ctx, hy->train_encoder != 0)));
   return HVLA_OK;
 }
 
@@ -804,7 +857,8 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
-  HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream)));
+  HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
+                               pos_source(ctx, hy->train_encoder != 0)));
   return HVLA_OK;
 }
 
@@ -816,8 +870,11 @@ int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int
   if (!params) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   const Geom& g = ctx->g;
   const TrainLayout L = make_train_layout(g);
-  const int64_t want = L.total + (train_encoder ? L.enc_total : 0);
+  const PosSource ps = pos_source(ctx, train_encoder != 0);
+  const int64_t want = L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
   if (n_params != want) FAIL(ctx, HVLA_E_SHAPE, "n_params %lld, the training vector has %lld", (long long)n_params, (long long)want);
+  if (ps.n > 0 && (serving::enc_map(g, L).f_pos % 4 != 0 || (uintptr_t)params % 16 != 0))
+    FAIL(ctx, HVLA_E_SHAPE, "the position table is not 16-byte aligned");
   // (the transposing kernel's whole 64 x 64 tiles: hvla_create admits encoder widths in multiples of 128 only)
   const PolicyLayout& pl = ctx->lay.pl;
   const int Gtot = pl.Gm + pl.Gv;
@@ -827,6 +884,11 @@ int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int
                 ctx->cfg.enc_dtype == HVLA_ENC_BF16, train_encoder != 0};
   ctx->prof.nlaunch += train_encoder ? 6 : 2;
   HIPCHK(ctx, launch_publish(a, reinterpret_cast<hipStream_t>(stream)));
+  if (ps.n > 0) {      // the served table is the resize of the vector's SOURCE table, by the kernel the step resizes with
+    ctx->prof.nlaunch += 2;
+    HIPCHK(ctx, launch_position_serve(params + L.total + L.enc_total, ps.n, ps.w, params + L.total + L.e_cls,
+                                      ctx->encf32.as<float>() + serving::enc_map(g, L).f_pos, ps.grid, ps.E, reinterpret_cast<hipStream_t>(stream)));
+  }
   return HVLA_OK;
 }
 

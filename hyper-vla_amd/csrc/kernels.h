@@ -204,6 +204,14 @@ struct PublishArgs {
 };
 hipError_t launch_publish(const PublishArgs& a, hipStream_t st);
 
+// ---------------------------------------------------------------- position table (position.hip, include/hvla.h hvla_position_*)
+// src [1 + n n, E] -> dst [1 + grid grid, E] through the resize whose per-axis weight matrix is w [n, grid] (device), and the
+// adjoint ddst -> dsrc of that map.  E % 4 == 0, every pointer 16-byte aligned.
+hipError_t launch_position_interp(const float* src, int n, const float* w, float* dst, int grid, int E, hipStream_t st);
+// the serving buffer's table: `table` [1 + grid grid, E] = resize of src, then the class token added into row 0 as the loader does
+hipError_t launch_position_serve(const float* src, int n, const float* w, const float* cls, float* table, int grid, int E, hipStream_t st);
+hipError_t launch_position_adjoint(const float* ddst, int n, const float* w, float* dsrc, int grid, int E, hipStream_t st);
+
 // ---------------------------------------------------------------- self test
 hipError_t launch_selftest(int* fail_flags, hipStream_t st);
 hipError_t run_box_probe(float* sink, unsigned long long* ticks, float out[3], hipStream_t st);   // selftest.hip: sustained clock / MFMA rate of this box

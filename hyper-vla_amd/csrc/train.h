@@ -56,7 +56,7 @@ struct TrainBuffers {        // all device memory, owned by the caller
   float* sqsum;              // [1]
   const uint8_t* wd_mask;    // [total (+ enc_total)] 1 where decoupled weight decay applies: built by the host from the
                              //     selected weight_decay_strategy (hypervla/train.py), flat parameter order
-  const float* params0;      // [enc_total] pretrained encoder weights for the delta decay (train.py:465-471) or null
+  const float* params0;      // [enc_total (+ source tail)] pretrained encoder weights for the delta decay (train.py:465-471) or null
 };
 struct TrainInputs {
   const float* tok;          // [B, T, lang_dim]
@@ -73,14 +73,26 @@ struct TrainHyper {
   int step, forward_only;
   float base_lr, base_weight_decay;      // optimizer group of the shared (DINOv2) leaves, train_utils.py:411-419
 };
+// The DINOv2 position table trained through its interpolation (hvla_train_position_source; position.hip).  n == 0: off, and every
+// entry below launches exactly what it launches without this struct.  On (trained encoder only): the flat vector is
+// [hypernetwork | encoder leaves | source table (1 + n n) E]; the baked table's slot among the encoder leaves (TrainLayout::e_pos)
+// stays where it is as a derived quantity -- resized from the tail before the encoder reads it, its gradient carried to the tail
+// by the adjoint and then zeroed.
+struct PosSource {
+  int n = 0;                 // side of the source grid
+  const float* w = nullptr;  // [n, grid] per-axis resize weights (device, owned by the caller)
+  int grid = 0, E = 0;       // the context's
+  long tail() const { return n ? (long)(1 + (long)n * n) * E : 0; }
+};
 // bucket_done (nullable, [3]): events recorded on `st` when a contiguous range of `grads` is final -- [0] the shared DINOv2
 // leaves [total, total + enc_total) after the image encoder's backward (trained encoder only), [1] the output heads
 // [wcat, total) after the weight-generation backward, [2] the context encoder [0, wcat) at the end -- so that the caller's
 // all-reduce of a bucket runs under the rest of the backward pass.
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr);
-hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st);
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr, const PosSource& ps = PosSource());
+hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
+                       const PosSource& ps = PosSource());
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st);
+                            bool train_encoder, hipStream_t st, const PosSource& ps = PosSource());
 
 }  // namespace hvla

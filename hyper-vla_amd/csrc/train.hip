@@ -1340,7 +1340,7 @@ size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
 }
 
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done) {
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps) {
   const int S = g.S(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
   const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
@@ -1356,7 +1356,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   float* Gm = tb.grads;
   const float* Pe = Pm + L.total;          // shared DINOv2 leaves (only touched when enc)
   float* Ge = Gm + L.total;
-  (void)hipMemsetAsync(Gm, 0, (size_t)(L.total + (enc ? L.enc_total : 0)) * 4, st);
+  const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
+  (void)hipMemsetAsync(Gm, 0, (size_t)(L.total + (enc ? L.enc_total : 0) + (src_on ? ps.tail() : 0)) * 4, st);
   (void)hipMemsetAsync(tb.dtheta, 0, (size_t)B * G * 4, st);
   const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0}, enc_opt{2, nullptr, 1};
 
@@ -1367,6 +1368,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   long tok_stride = (long)P * E;
   if (enc) {
     float* ex0 = eb.empty() ? pl.ex_fin : eb[0].x_in;
+    if (src_on) (void)launch_position_interp(Pe + L.enc_total, ps.n, ps.w, tb.params + L.total + L.e_pos, ps.grid, E, st);     // tail -> slot
     KL(im2col_f32_kernel, g1((long)B * P * Kp), dim3(256), in.images, pl.patches, B, g.image_size, g.patch);
     bgemm(st, false, false, BG{pl.patches, Pe + L.e_pk, ex0 + E, Pe + L.e_pb, P, E, Kp, Kp, E, E, (long)P * Kp, 0, 0, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
     KL(enc_x0_kernel, g1((long)B * Se * E), dim3(256), ex0, Pe + L.e_cls, Pe + L.e_pos, B, Se, E);
@@ -1430,6 +1432,10 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     (void)hipMemcpyAsync(Ge + L.e_cls, Ge + L.e_pos, (size_t)E * 4, hipMemcpyDeviceToDevice, st);                          // dcls = dpos[0]
     KL(colsum_kernel, dim3((E + 63) / 64, 1, (P + 63) / 64), dim3(64), Ge + L.e_pos + E, Ge + L.e_pb, 0, P, P, E, 1);     // dbias = sum_{t>=1} dpos[t]
     bgemm(st, true, false, BG{pl.patches, edx + E, Ge + L.e_pk, nullptr, Kp, E, P, Kp, E, E, (long)P * Kp, 0, (long)Se * E, 0, 0, 0, 0, 1, 1.f, 2}, B);
+    if (src_on) {                                                        // dsource = A^T dslot; the slot is no parameter: its gradient is zero
+      (void)launch_position_adjoint(Ge + L.e_pos, ps.n, ps.w, Ge + L.enc_total, ps.grid, E, st);
+      (void)hipMemsetAsync(Ge + L.e_pos, 0, (size_t)Se * E * 4, st);
+    }
     if (bucket_done) (void)hipEventRecord(bucket_done[0], st);           // the shared DINOv2 leaves are final
   }
   // =============================== weight generation backward ===============================
@@ -1452,8 +1458,10 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   return hipGetLastError();
 }
 
-hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st) {
-  const long n = L.total + (train_encoder ? L.enc_total : 0);
+hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
+                       const PosSource& ps) {
+  const long tail = train_encoder ? ps.tail() : 0;           // the position table's source (shared group; the slot's gradient is zero)
+  const long n = L.total + (train_encoder ? L.enc_total : 0) + tail;
   (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
   KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);          // one global norm over both optimizer groups
   const float t = (float)(hp.step + 1);
@@ -1462,14 +1470,19 @@ hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const Train
      hp.clip, hp.lr, hp.b1, hp.b2, hp.eps, hp.weight_decay, tb.wd_mask, bc1, bc2, hp.ema_decay);
   if (train_encoder)
     KL(adamw_shared_kernel, dim3(2048), dim3(256), tb.params + L.total, tb.grads + L.total, tb.mu + L.total, tb.nu + L.total,
-       hp.ema_decay > 0.f ? tb.ema + L.total : nullptr, L.enc_total, tb.sqsum, hp.clip, hp.base_lr, hp.b1, hp.b2, hp.eps,
+       hp.ema_decay > 0.f ? tb.ema + L.total : nullptr, L.enc_total + tail, tb.sqsum, hp.clip, hp.base_lr, hp.b1, hp.b2, hp.eps,
        hp.base_weight_decay, tb.wd_mask ? tb.wd_mask + L.total : nullptr, tb.params0, bc1, bc2, hp.ema_decay);
+  if (tail) {                                                 // the derived slots follow their tails
+    const long slot = L.total + L.e_pos, src = L.total + L.enc_total;
+    (void)launch_position_interp(tb.params + src, ps.n, ps.w, tb.params + slot, ps.grid, ps.E, st);
+    if (hp.ema_decay > 0.f && tb.ema) (void)launch_position_interp(tb.ema + src, ps.n, ps.w, tb.ema + slot, ps.grid, ps.E, st);
+  }
   return hipGetLastError();
 }
 
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st) {
-  const long n = L.total + (train_encoder ? L.enc_total : 0);
+                            bool train_encoder, hipStream_t st, const PosSource& ps) {
+  const long n = L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
   (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
   KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);
   KL(accumulate_kernel, dim3(2048), dim3(256), acc, tb.grads, n, tb.sqsum, hp.clip, inv_k);

@@ -25,7 +25,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
-           "hvla_create_with", "hvla_train_publish"]
+           "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
+           "hvla_train_position_source"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -147,6 +148,12 @@ def load_library():
     lib.hvla_train_accumulate.restype = C.c_int
     lib.hvla_train_publish.argtypes = [vp, vp, i64, i32, vp]
     lib.hvla_train_publish.restype = C.c_int
+    lib.hvla_position_interp.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.hvla_position_interp.restype = C.c_int
+    lib.hvla_position_interp_adjoint.argtypes = [vp, vp, i32, vp, vp, vp]
+    lib.hvla_position_interp_adjoint.restype = C.c_int
+    lib.hvla_train_position_source.argtypes = [vp, i32, vp]
+    lib.hvla_train_position_source.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -377,6 +384,21 @@ class Context:
         """Pack the flat training vector at `params_ptr` (device f32 [n_params]) into this context's serving buffers, in place."""
         self._check(self.lib.hvla_train_publish(self.h, C.c_void_p(params_ptr or None), int(n_params), int(bool(train_encoder)),
                                                 C.c_void_p(stream)), "hvla_train_publish")
+
+    def position_interp(self, src_ptr, n, w_ptr, dst_ptr, stream=0):
+        """dst [1 + P, E] = the resize of the source position table src [1 + n n, E] with the weights w [n, grid] (device pointers)."""
+        self._check(self.lib.hvla_position_interp(self.h, C.c_void_p(src_ptr or None), int(n), C.c_void_p(w_ptr or None),
+                                                  C.c_void_p(dst_ptr or None), C.c_void_p(stream)), "hvla_position_interp")
+
+    def position_interp_adjoint(self, ddst_ptr, n, w_ptr, dsrc_ptr, stream=0):
+        """dsrc [1 + n n, E] = the transpose of `position_interp` applied to ddst [1 + P, E]."""
+        self._check(self.lib.hvla_position_interp_adjoint(self.h, C.c_void_p(ddst_ptr or None), int(n), C.c_void_p(w_ptr or None),
+                                                          C.c_void_p(dsrc_ptr or None), C.c_void_p(stream)),
+                    "hvla_position_interp_adjoint")
+
+    def train_position_source(self, n, w_ptr=0):
+        """Train the position table through its interpolation from an n x n source (n = 0: off); `w_ptr` stays the caller's."""
+        self._check(self.lib.hvla_train_position_source(self.h, int(n), C.c_void_p(w_ptr or None)), "hvla_train_position_source")
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

@@ -173,10 +173,15 @@ def flatten_tree(tree: Mapping, sep: str = "/") -> Dict[str, np.ndarray]:
     return out
 
 
-def params_from_tree(tree: Mapping, g: Geometry) -> Dict[str, np.ndarray]:
+POSITION_SOURCE_KEY = "position_table_source"       # the un-resized DINOv2 position table beside the parameters in params_<step>.npz
+
+
+def params_from_tree(tree: Mapping, g: Geometry, return_source: bool = False):
     """Hypernetwork parameter tree (SURVEY.md §5.4 naming) -> the flat float32 dict `HyperVLA(params=...)` takes.
     Every tensor the built path needs must be present with the expected shape; tensors the path does not use are
-    reported, not silently dropped."""
+    reported, not silently dropped.  With `return_source` the result is (params, source): the position table as the tree
+    carries it, float32 [1, 1 + n*n, E], when it had to be baked to the run-time grid -- the leaf the reference trains
+    (`HyperVLA(position_table_source=...)`) -- and None when the tree's table already is at that grid."""
     flat = flatten_tree(tree)
     if flat and all(k.startswith("params/") for k in flat):             # a variables dict {"params": ...}
         flat = {k[len("params/"):]: v for k, v in flat.items()}
@@ -188,16 +193,17 @@ def params_from_tree(tree: Mapping, g: Geometry) -> Dict[str, np.ndarray]:
     if extra:
         raise ValueError(f"{len(extra)} tensors of the checkpoint are outside the built path (other generation strategy / "
                          f"encoder?), e.g. {extra[:4]}")
-    out = {}
+    out, source = {}, None
     for k, shp in shapes.items():
         v = np.asarray(flat[k], np.float32)
         if k.endswith("embeddings_position_embeddings") and v.size != int(np.prod(shp)):
             # the checkpoint carries HF's 37 x 37 table; the reference resizes it inside every forward pass
-            v = bake_position_embeddings(v.reshape(1, -1, g.enc_dim), g.image_size // g.patch)
+            source = v.reshape(1, -1, g.enc_dim).copy()
+            v = bake_position_embeddings(source, g.image_size // g.patch)
         if int(np.prod(v.shape)) != int(np.prod(shp)):
             raise ValueError(f"{k}: checkpoint shape {v.shape} != expected {tuple(shp)}")
         out[k] = v.reshape(shp)
-    return out
+    return (out, source) if return_source else out
 
 
 # ------------------------------------------------------------------------------------------------ DINOv2 position table
@@ -223,6 +229,30 @@ def _scale_and_translate_weights(in_size: int, out_size: int, scale: float, tran
     return np.where(inside[None, :], w, 0.0).astype(np.float32)
 
 
+def position_interp_weights(n: int, grid: int) -> np.ndarray:
+    """float32 [n, grid]: the per-axis weight matrix `bake_position_embeddings` resizes an n x n table to grid x grid with --
+    what `hvla_position_interp` takes as `w` (the device resizes with these numbers; it restates no formula)."""
+    return _scale_and_translate_weights(n, grid, np.float32((grid + 0.1) / n))
+
+
+def position_table_adjoint(dtable: np.ndarray, n: int) -> np.ndarray:
+    """The transpose of `bake_position_embeddings` as a linear map, in float64: the gradient of the baked table
+    [1, 1 + grid*grid, E] -> the gradient of the n x n source table [1, 1 + n*n, E] (what jax.grad gives the reference's leaf
+    through interpolate_pos_encoding).  The class row passes through; n == grid is the identity."""
+    d = np.asarray(dtable, np.float64)
+    if d.ndim == 2:
+        d = d[None]
+    g2, E = d.shape[1] - 1, d.shape[2]
+    grid = int(round(np.sqrt(g2)))
+    if grid * grid != g2:
+        raise ValueError(f"baked table has {g2} patch rows, not a square")
+    if n == grid:
+        return d.copy()
+    w = position_interp_weights(n, grid).astype(np.float64)
+    out = np.einsum("ije,hi,wj->hwe", d[0, 1:].reshape(grid, grid, E), w, w)
+    return np.concatenate([d[:, :1], out.reshape(1, n * n, E)], axis=1)
+
+
 def bake_position_embeddings(table: np.ndarray, grid: int) -> np.ndarray:
     """HF ``embeddings.position_embeddings`` [1, 1 + n*n, E] -> [1, 1 + grid*grid, E] as
     ``FlaxDinov2Embeddings.interpolate_pos_encoding`` produces it for a (14*grid)^2 image: the patch part is resized
@@ -244,15 +274,18 @@ def bake_position_embeddings(table: np.ndarray, grid: int) -> np.ndarray:
     return np.concatenate([table[:, :1], out.reshape(1, grid * grid, E)], axis=1)
 
 
-def tree_from_params(params: Mapping[str, np.ndarray]) -> Dict[str, Any]:
+def tree_from_params(params: Mapping[str, np.ndarray], position_table_source: Optional[np.ndarray] = None) -> Dict[str, Any]:
     """Inverse of :func:`params_from_tree`: the flat '/'-named dict -> the nested hypernetwork parameter tree of the
     reference (`HyperVLA.params`, hypervla/model.py:330-346): modules nest by '/', the shared image-encoder leaves are flat
     vectors under their one-level names `encoder_image_encoder_<path>`.  Values keep their shapes (the shared leaves are
     ravelled); reshape against the target tree's leaves where the reference's shapes are at hand
-    (tools/make_reference_fixtures.py does)."""
+    (tools/make_reference_fixtures.py does).  With `position_table_source` (`model.position_table_source`) the un-resized
+    position table takes the place of the baked one: the tree then has the reference's own shapes, leaf for leaf."""
     tree: Dict[str, Any] = {}
     for name, v in params.items():
         v = np.asarray(v, np.float32)
+        if position_table_source is not None and name.endswith("embeddings_position_embeddings"):
+            v = np.asarray(position_table_source, np.float32)
         if name.startswith("encoder_image_encoder_"):
             v = v.reshape(-1)
         node = tree
@@ -366,10 +399,11 @@ def convert_checkpoint(src_dir: str, dst_dir: str, step: int, ema: Optional[floa
         if ema is None:
             raise ValueError("pass the restored parameter tree, or ema=<coefficient> to read EMA_params.pkl")
         tree = load_ema_pickle(os.path.join(src_dir, str(step), "EMA_params.pkl"), ema)
-    params = params_from_tree(tree, g)
+    params, source = params_from_tree(tree, g, return_source=True)
     os.makedirs(dst_dir, exist_ok=True)
     out = os.path.join(dst_dir, f"params_{step}.npz")
-    np.savez(out, **params)
+    # the un-resized position table rides beside the parameters: FineTuner(train_encoder=True) trains it, as the reference does
+    np.savez(out, **params, **({POSITION_SOURCE_KEY: source} if source is not None else {}))
     for name in ("dataset_statistics.json", "example_batch.msgpack"):
         sp = os.path.join(src_dir, name)
         if os.path.exists(sp):

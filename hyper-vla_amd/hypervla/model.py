@@ -84,10 +84,13 @@ class GeneratedWeights:
 class HyperVLA:
     def __init__(self, config: Dict, params: Dict[str, np.ndarray], example_batch: Optional[Dict] = None,
                  dataset_statistics: Optional[Dict] = None, device: int = 0, max_batch: int = 256,
-                 enc_dtype: str = "f16", streams: int = 1, _shared_ctx=None):
+                 enc_dtype: str = "f16", streams: int = 1, _shared_ctx=None, *, position_table_source=None):
         torch = _torch()
         self.config = config
         self.params = params
+        # the un-resized DINOv2 position table of a converted checkpoint (float32 [1, 1 + n*n, E]; hypervla/convert.py): not a
+        # parameter of the serving path, which reads the baked table in `params`, but the leaf FineTuner(train_encoder=True) trains
+        self.position_table_source = position_table_source
         self.example_batch = example_batch
         self.dataset_statistics = dataset_statistics
         self.geometry: Geometry = geometry_from_config(config)
@@ -103,6 +106,20 @@ class HyperVLA:
         if missing:
             raise ValueError(f"checkpoint is missing {len(missing)} tensors, e.g. {missing[:3]}")
         self._ctx.load_weights({k: params[k] for k in want})
+
+    @property
+    def position_table_source(self) -> Optional[np.ndarray]:
+        return self._position_table_source
+
+    @position_table_source.setter
+    def position_table_source(self, value) -> None:
+        if value is not None:
+            value = np.ascontiguousarray(np.asarray(value, np.float32))
+            E = geometry_from_config(self.config).enc_dim
+            n = int(round(np.sqrt(max(value.shape[1] - 1, 0)))) if value.ndim == 3 else 0
+            if value.ndim != 3 or value.shape[0] != 1 or value.shape[2] != E or n < 2 or 1 + n * n != value.shape[1]:
+                raise ValueError(f"position_table_source must be float32 [1, 1 + n*n, {E}], got {value.shape}")
+        self._position_table_source = value
 
     @property
     def params(self) -> Dict[str, np.ndarray]:
@@ -151,10 +168,9 @@ class HyperVLA:
             cands = [p for p in cands if p == f"params_{step}.npz"]
         if not cands:
             raise FileNotFoundError(f"no params*.npz under {checkpoint_path} (step={step})")
-        with np.load(os.path.join(checkpoint_path, cands[-1])) as z:
-            params = {k: z[k] for k in z.files}
         from .convert import load_example_batch
-        model = cls(config, params, load_example_batch(checkpoint_path), stats, **kw)
+        params, source = read_params_file(os.path.join(checkpoint_path, cands[-1]))
+        model = cls(config, params, load_example_batch(checkpoint_path), stats, position_table_source=source, **kw)
         if audit in ("raise", "warn"):         # a real checkpoint's activations must fit the 16-bit operand type
             import warnings
             try:
@@ -206,7 +222,10 @@ class HyperVLA:
 
     def save_pretrained(self, step: int, checkpoint_path: str):
         os.makedirs(checkpoint_path, exist_ok=True)
-        np.savez(os.path.join(checkpoint_path, f"params_{step}.npz"), **self.params)
+        from .convert import POSITION_SOURCE_KEY
+        src = self.position_table_source
+        np.savez(os.path.join(checkpoint_path, f"params_{step}.npz"), **self.params,
+                 **({POSITION_SOURCE_KEY: src} if src is not None else {}))
         cp = os.path.join(checkpoint_path, "config.json")
         if not os.path.exists(cp):
             with open(cp, "w") as f:
@@ -222,21 +241,43 @@ class HyperVLA:
                 f.write(msgpack_serialize(self.example_batch))
 
     @classmethod
-    def from_synthetic(cls, geometry: Geometry = FULL, params: Optional[Dict[str, np.ndarray]] = None, **kw) -> "HyperVLA":
+    def from_synthetic(cls, geometry: Geometry = FULL, params: Optional[Dict[str, np.ndarray]] = None, *,
+                       position_table_source=None, **kw) -> "HyperVLA":
+        """`position_table_source` (e.g. `synthetic.synthetic_position_table_hub(g, n)`): the model is what the converter makes of a
+        checkpoint with that table -- the served table is its baking, the config carries the marker, the source rides along."""
         from . import synthetic
-        return cls(default_config(geometry), synthetic.synthetic_params(geometry) if params is None else params, None,
-                   synthetic.synthetic_dataset_statistics(geometry), **kw)
+        config = default_config(geometry)
+        params = synthetic.synthetic_params(geometry) if params is None else params
+        if position_table_source is not None:
+            from .convert import bake_position_embeddings
+            src = np.asarray(position_table_source, np.float32)
+            n = int(round(np.sqrt(src.shape[1] - 1)))
+            params = dict(params)
+            key = next(k for k in params if k.endswith("embeddings_position_embeddings"))
+            params[key] = bake_position_embeddings(src, geometry.image_size // geometry.patch).reshape(params[key].shape)
+            config["position_embeddings_baked_from"] = [n, n]
+        return cls(config, params, None, synthetic.synthetic_dataset_statistics(geometry),
+                   position_table_source=position_table_source, **kw)
 
     def replace(self, **changes) -> "HyperVLA":
         """flax ``struct.dataclass.replace``: the evaluators swap in EMA params this way
         (data/simpler/evaluate.py:440-444)."""
-        if set(changes) - {"params", "config", "dataset_statistics", "example_batch"}:
+        if set(changes) - {"params", "config", "dataset_statistics", "example_batch", "position_table_source"}:
             raise TypeError(f"cannot replace {set(changes)}")
         if "params" in changes or "config" in changes:
+            # the source table goes along while it still is the source of the served table: parameters that bring another
+            # position table leave it behind unless theirs is passed too
+            source = changes.get("position_table_source", self.position_table_source)
+            if "position_table_source" not in changes and source is not None and "params" in changes:
+                key = next(k for k in self.params if k.endswith("embeddings_position_embeddings"))
+                if key not in changes["params"] or not np.array_equal(np.asarray(changes["params"][key]).reshape(-1),
+                                                                     np.asarray(self.params[key]).reshape(-1)):
+                    source = None
             return HyperVLA(changes.get("config", self.config), changes.get("params", self.params),
                             changes.get("example_batch", self.example_batch),
                             changes.get("dataset_statistics", self.dataset_statistics),
-                            self.device.index or 0, self.max_batch, self.enc_dtype, self.streams)
+                            self.device.index or 0, self.max_batch, self.enc_dtype, self.streams,
+                            position_table_source=source)
         import copy
         other = copy.copy(self)
         for k, v in changes.items():
@@ -505,6 +546,15 @@ class HyperVLA:
         self._ctx.loss(act.data_ptr(), lg.data_ptr(), tgt.data_ptr(), tm.data_ptr(), am.data_ptr(), out.data_ptr(), B,
                        self._stream())
         return out, out.mean()
+
+
+def read_params_file(path: str):
+    """params_<step>.npz -> (parameters, position_table_source or None): the un-resized position table a converted checkpoint
+    carries beside its parameters (hypervla/convert.py) is not one of them."""
+    from .convert import POSITION_SOURCE_KEY
+    with np.load(path) as z:
+        params = {k: z[k] for k in z.files}
+    return params, params.pop(POSITION_SOURCE_KEY, None)
 
 
 HyperVLAModel = HyperVLA        # the name BASELINE.json's north_star uses

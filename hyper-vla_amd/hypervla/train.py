@@ -18,10 +18,17 @@ from . import _native
 from .config import Geometry, encoder_leaves, generated_leaves, shared_name
 
 
-def train_param_layout(g: Geometry, train_encoder: bool = False) -> Tuple[List[Tuple[str, int, Tuple[int, ...]]], int]:
+POSITION_SOURCE = "position_table_source"      # the layout's name of the tail: no checkpoint tensor (model.position_table_source)
+POSITION_LEAF = "encoder_image_encoder_embeddings_position_embeddings"
+
+
+def train_param_layout(g: Geometry, train_encoder: bool = False,
+                       position_source: int = 0) -> Tuple[List[Tuple[str, int, Tuple[int, ...]]], int]:
     """[(name, offset, shape)] of the flat trainable-parameter vector == make_train_layout() in csrc/train.hip.
     The 73 output heads are the fused entries "W_cat" [C, G] and "b_cat" [G] (columns in pytree leaf order); with
-    `train_encoder` the shared DINOv2 leaves follow as flat vectors under their checkpoint names."""
+    `train_encoder` the shared DINOv2 leaves follow as flat vectors under their checkpoint names.  `position_source` = n
+    (hvla_train_position_source, trained encoder only): the n x n source of the position table follows them as the tail
+    "position_table_source" [1, 1 + n*n, E]; the baked table keeps its slot among the leaves as a derived quantity."""
     C, F = g.ctx_dim, g.ctx_mlp
     out, off = [], 0
 
@@ -51,16 +58,18 @@ def train_param_layout(g: Geometry, train_encoder: bool = False) -> Tuple[List[T
     if train_encoder:
         for path, shape in encoder_leaves(g):
             add(shared_name(path), (int(np.prod(shape)),))
+        if position_source:
+            add(POSITION_SOURCE, (1, 1 + int(position_source) ** 2, g.enc_dim))
     return out, off
 
 
-def gradient_buckets(g: Geometry, train_encoder: bool = False) -> List[Tuple[str, int, int]]:
+def gradient_buckets(g: Geometry, train_encoder: bool = False, position_source: int = 0) -> List[Tuple[str, int, int]]:
     """[(name, offset, length)] of the flat gradient in the order hvla_train_step finishes them (include/hvla.h,
     hvla_train_bucket_ranges): the shared DINOv2 leaves after the image encoder's backward, the output heads (W_cat,
     b_cat) after the weight-generation backward, the context encoder at the end of the step.  Contiguous, disjoint, and
     together the whole vector -- what `pmean(grads)` (scripts/train.py:460) is cut into so that each all-reduce runs
-    under the rest of the backward pass."""
-    layout, total = train_param_layout(g, train_encoder)
+    under the rest of the backward pass.  The position table's source (`position_source`) is the tail of the encoder's bucket."""
+    layout, total = train_param_layout(g, train_encoder, position_source)
     at = {name: off for name, off, _ in layout}
     wcat = at["W_cat"]
     n_hyper = at["b_cat"] + generated_leaves(g)[-1].offset + generated_leaves(g)[-1].size
@@ -72,8 +81,14 @@ def gradient_buckets(g: Geometry, train_encoder: bool = False) -> List[Tuple[str
     return out
 
 
-def pack_params(g: Geometry, params: Dict[str, np.ndarray], train_encoder: bool = False) -> np.ndarray:
-    layout, total = train_param_layout(g, train_encoder)
+def _source_side(position_source) -> int:
+    """n of a source table [1, 1 + n*n, E] (None: 0)."""
+    return 0 if position_source is None else int(round(np.sqrt(np.shape(position_source)[1] - 1)))
+
+
+def pack_params(g: Geometry, params: Dict[str, np.ndarray], train_encoder: bool = False, position_source=None) -> np.ndarray:
+    """`position_source`: the source table itself (float32 [1, 1 + n*n, E]), packed as the tail."""
+    layout, total = train_param_layout(g, train_encoder, _source_side(position_source) if train_encoder else 0)
     flat = np.zeros(total, np.float32)
     leaves = generated_leaves(g)
     for name, off, shape in layout:
@@ -83,16 +98,20 @@ def pack_params(g: Geometry, params: Dict[str, np.ndarray], train_encoder: bool 
             flat[off:off + n] = w.reshape(-1)
         elif name == "b_cat":
             flat[off:off + n] = np.concatenate([np.asarray(params[l.head_name + "/bias"], np.float32).reshape(-1) for l in leaves])
+        elif name == POSITION_SOURCE:
+            flat[off:off + n] = np.asarray(position_source, np.float32).reshape(-1)
         else:
             flat[off:off + n] = np.asarray(params[name], np.float32).reshape(-1)
     return flat
 
 
-def unpack_params(g: Geometry, flat: np.ndarray, train_encoder: bool = False) -> Dict[str, np.ndarray]:
-    """flat vector (parameters or gradients) -> reference-named tensors."""
-    layout, _ = train_param_layout(g, train_encoder)
+def unpack_params(g: Geometry, flat: np.ndarray, train_encoder: bool = False, position_source: int = 0):
+    """flat vector (parameters or gradients) -> reference-named tensors.  With `position_source` = n the result is
+    (tensors, source [1, 1 + n*n, E]): the tail is no checkpoint tensor and stays out of the dict."""
+    layout, _ = train_param_layout(g, train_encoder, position_source)
     leaves = generated_leaves(g)
     out: Dict[str, np.ndarray] = {}
+    source = None
     for name, off, shape in layout:
         v = np.asarray(flat[off:off + int(np.prod(shape))]).reshape(shape)
         if name == "W_cat":
@@ -101,9 +120,11 @@ def unpack_params(g: Geometry, flat: np.ndarray, train_encoder: bool = False) ->
         elif name == "b_cat":
             for l in leaves:
                 out[l.head_name + "/bias"] = v[l.offset:l.offset + l.size].copy()
+        elif name == POSITION_SOURCE:
+            source = v.copy()
         else:
             out[name] = v.copy()
-    return out
+    return (out, source) if (train_encoder and position_source) else out
 
 
 def lr_rsqrt(step: int, peak: float, warmup: int = 2000, timescale: int = 10000, init: float = 0.0) -> float:
@@ -114,7 +135,7 @@ def lr_rsqrt(step: int, peak: float, warmup: int = 2000, timescale: int = 10000,
     return peak / float(np.sqrt((s + timescale) / timescale))
 
 
-def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False) -> np.ndarray:
+def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False, position_source: int = 0) -> np.ndarray:
     """uint8 [n_params]: where `create_optimizer`'s decoupled weight decay applies (octo/utils/train_utils.py:325-382).
     The reference tests `jax.tree_util.keystr(path)` of every leaf of the hypernetwork's parameter tree; an output head is
     the module `output_head_<flat base-net leaf name>` (hypervla/model.py:342) with leaves `kernel` and `bias`, so the
@@ -127,10 +148,15 @@ def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False) -
     "v3" (:335-350): output heads that generate *kernel* leaves (kernel and bias), every leaf of the shared image
     encoder, and the remaining *kernel* leaves (context encoder, projections).
     "v5" (the README run, README.md:29; :354-363): as v3 without the context-encoder kernels.
-    "v4" adds a second backward pass through a weight-decay loss (scripts/train.py:473-480) and is not built."""
+    "v4" adds a second backward pass through a weight-decay loss (scripts/train.py:473-480) and is not built.
+    With `position_source` the tail IS the reference's leaf `encoder_image_encoder_embeddings_position_embeddings` and gets that
+    leaf's value; the baked slot is no parameter and gets 0."""
     if strategy not in ("v1", "v2", "v3", "v5"):
         raise ValueError(f"weight_decay_strategy {strategy!r}: 'v1', 'v2', 'v3' and 'v5' are built (v4 is not)")
-    layout, total = train_param_layout(g, train_encoder)
+    layout, total = train_param_layout(g, train_encoder, position_source)
+    if train_encoder and position_source:          # the tail under the leaf's name, the slot under one that no rule matches
+        layout = [(POSITION_LEAF if name == POSITION_SOURCE else "" if name == POSITION_LEAF else name, off, shape)
+                  for name, off, shape in layout]
     leaves = generated_leaves(g)
     G = leaves[-1].offset + leaves[-1].size
     mask = np.zeros(total, np.uint8)
@@ -140,6 +166,8 @@ def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False) -
             cols[l.offset:l.offset + l.size] = 1
     for name, off, shape in layout:
         n = int(np.prod(shape))
+        if name == "":                            # the baked position table's slot (a derived quantity)
+            continue
         if name == "W_cat":                       # [C, G]: the kernels of the 73 output heads
             mask[off:off + n] = 1 if strategy in ("v1", "v2") else np.tile(cols, shape[0])
         elif name == "b_cat":                     # their biases: `output_head_<..._kernel>/bias` contains "kernel"
@@ -177,19 +205,32 @@ class FineTuner:
         self.torch, self.model, self.g, self.B = torch, model, model.geometry, batch
         self.train_encoder = bool(train_encoder)
         baked = (model.config or {}).get("position_embeddings_baked_from")
-        if self.train_encoder and baked and not accept_baked_position_table:
+        source = getattr(model, "position_table_source", None)
+        # the reference's leaf is the un-resized table: with it at hand it is the parameter, the baked table a derived quantity
+        self.position_source = source if self.train_encoder and not accept_baked_position_table else None
+        self.source_n = _source_side(self.position_source)
+        self._drops_source = self.train_encoder and accept_baked_position_table and source is not None
+        if self.train_encoder and baked and source is None and not accept_baked_position_table:
             raise ValueError(
                 f"this checkpoint's DINOv2 position table was baked from {baked} to the run-time grid at conversion time "
                 "(hypervla/convert.py); the reference trains the ORIGINAL table through interpolate_pos_encoding, so its "
                 "gradient and Adam state differ and the result cannot be exported back into a reference-shaped "
-                "checkpoint.  Pass accept_baked_position_table=True to train the baked table anyway (INTEGRATION.md).")
+                "checkpoint.  This model has no position_table_source (checkpoints converted before the converter kept it): convert "
+                "again, or pass accept_baked_position_table=True to train the baked table anyway (INTEGRATION.md).")
         dev = model.device
+        self.interp_w = None
+        if self.source_n:
+            from .convert import position_interp_weights
+            self.interp_w = torch.as_tensor(position_interp_weights(self.source_n, self.g.grid)).to(dev).contiguous()
+        self._select_source()
         n, G, work, n_hyper = model._ctx.train_sizes(batch, self.train_encoder)
-        layout, total = train_param_layout(self.g, self.train_encoder)
+        layout, total = train_param_layout(self.g, self.train_encoder, self.source_n)
         assert n == total, (n, total)
         self.n, self.G, self.n_hyper = n, G, n_hyper
         f32 = dict(dtype=torch.float32, device=dev)
-        self.params = torch.as_tensor(pack_params(self.g, model.params, self.train_encoder)).to(dev)
+        self.params = torch.as_tensor(pack_params(self.g, model.params, self.train_encoder, self.position_source)).to(dev)
+        if self.source_n:
+            self._derive_slot(layout)
         self.grads = torch.zeros(n, **f32)
         self.mu = torch.zeros(n, dtype=torch.bfloat16, device=dev)
         self.nu = torch.zeros(n, **f32)
@@ -202,7 +243,7 @@ class FineTuner:
         self.logits = torch.zeros(batch, self.g.horizon, **f32)
         self.sqsum = torch.zeros(1, **f32)
         self.weight_decay_strategy = weight_decay_strategy
-        self.wd_mask = torch.as_tensor(weight_decay_mask(self.g, weight_decay_strategy, self.train_encoder)).to(dev)
+        self.wd_mask = torch.as_tensor(weight_decay_mask(self.g, weight_decay_strategy, self.train_encoder, self.source_n)).to(dev)
         # the pull towards the pretrained encoder only exists for base_weight_decay > 0 (scripts/train.py:469)
         self.params0 = self.params[n_hyper:].clone() if self.train_encoder and base_weight_decay > 0 else None
         self.accum_k = int(grad_accumulation_steps)
@@ -218,8 +259,34 @@ class FineTuner:
         self.ema_start_step = int(ema_start_step)
         self._bucket_setup()
 
+    def _select_source(self):
+        """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this
+        one trains (hvla_train_position_source; a host-side setting, nothing is launched)."""
+        self.model._ctx.train_position_source(self.source_n, self.interp_w.data_ptr() if self.source_n else 0)
+
+    def _derive_slot(self, layout):
+        """The baked slot of `params` becomes the device's own resize of the tail (bitwise what every later step and apply
+        re-derives), after a check that the source really is the source of the table being served: the two may differ by the
+        rounding of two four-tap float32 contractions evaluated in another order, not by more."""
+        torch, g = self.torch, self.g
+        at = {name: (off, int(np.prod(shape))) for name, off, shape in layout}
+        (so, sn), (to, tn) = at[POSITION_LEAF], at[POSITION_SOURCE]
+        self.slot, self.tail = slice(so, so + sn), slice(to, to + tn)
+        served = self.params[self.slot].clone()
+        self.model._ctx.position_interp(self.params[self.tail].data_ptr(), self.source_n, self.interp_w.data_ptr(),
+                                        self.params[self.slot].data_ptr(), self.model._stream())
+        w1 = float(self.interp_w.abs().sum(dim=0).max())
+        bound = 2 * 14 * 2.0 ** -24 * w1 * w1 * float(self.params[self.tail].abs().max())
+        worst = float((self.params[self.slot] - served).abs().max())
+        if not worst <= bound:
+            raise ValueError(
+                f"model.position_table_source ({self.source_n} x {self.source_n}) is not the source of the served table "
+                f"{POSITION_LEAF}: resized to {g.grid} x {g.grid} it differs from it by {worst:.3e}, the resize's own rounding "
+                f"allows {bound:.3e}.  Pass the source these parameters were baked from, or accept_baked_position_table=True "
+                "to train the served table itself (INTEGRATION.md)")
+
     def _bucket_setup(self):
-        self.buckets = gradient_buckets(self.g, self.train_encoder)
+        self.buckets = gradient_buckets(self.g, self.train_encoder, self.source_n)
         ranges = self.model._ctx.train_bucket_ranges(self.train_encoder)
         self._bucket_id = [ranges.index((off, n)) for _, off, n in self.buckets]   # the library's numbering (0 encoder, 1 heads, 2 context)
         self._comm = None
@@ -265,6 +332,7 @@ class FineTuner:
         assert tok.shape[0] == self.B
         self._keep = (tok, msk, cls, obs, tgt, am, tm)
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
+        self._select_source()
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
         return self.loss
 
@@ -299,6 +367,7 @@ class FineTuner:
         on every k-th call only (optax.MultiSteps, octo/utils/train_utils.py:420-421); returns True when they moved."""
         self.all_reduce_gradient()
         ctx, st = self.model._ctx, self.model._stream()
+        self._select_source()
         if self.accum_k > 1:
             if self.micro == 0:
                 self.acc.zero_()
@@ -337,14 +406,26 @@ class FineTuner:
         `host_copy=True` also replaces `model.params` by the published tensors (encoder leaves that were not trained are
         kept), so that `save_pretrained` writes what is being served.  With `host_copy=False` nothing leaves the device and
         `model.params` / `save_pretrained` raise until a later `publish(host_copy=True)`.
+        When the position table is trained through its interpolation (the model has a `position_table_source`), the served table is
+        baked on the device from the published vector's source, and `host_copy=True` updates `model.position_table_source` too;
+        after training the baked table itself (`accept_baked_position_table=True`) it sets it to None.
         `audit=True` runs `model.audit_operand_range()` afterwards: a trained encoder is where fp16 operands can leave their
         range; it returns that audit's result, otherwise None."""
         m = self.model
         vec = self.ema if ema else self.params
+        self._select_source()
+        if self.source_n:                          # the slot the host copy reads is the resize of the tail being published, whatever
+            m._ctx.position_interp(vec[self.tail].data_ptr(), self.source_n, self.interp_w.data_ptr(),     # was done to the vector
+                                   vec[self.slot].data_ptr(), m._stream())
         m._ctx.train_publish(vec.data_ptr(), self.n, self.train_encoder, m._stream())
         if host_copy:
             new = dict(m._params)
-            new.update(unpack_params(self.g, vec.cpu().numpy(), self.train_encoder))
+            got = unpack_params(self.g, vec.cpu().numpy(), self.train_encoder, self.source_n)
+            if self.source_n:                      # the trained source goes with the table that was baked from it
+                got, m.position_table_source = got
+            elif self._drops_source:               # the baked table was trained on its own: the source is stale
+                m.position_table_source = None
+            new.update(got)
             m.params = new
         else:
             m._params_stale = True

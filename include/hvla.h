@@ -337,6 +337,30 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
  * params, or a use_language_token geometry -> HVLA_E_SHAPE.                                                                 */
 int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int32_t train_encoder, void* stream);
 
+/* Replaces: FlaxDinov2Embeddings.interpolate_pos_encoding, which resizes HF's n x n DINOv2 position table to
+ * the run-time grid inside every forward pass, and its transpose under jax.grad: the reference trains the n x n table.
+ * hvla_position_interp: src f32 [1 + n n, E] -> dst f32 [1 + P, E], the context's grid and width (dst has no other geometry).  Row 0
+ * is copied.  w f32 [n, grid] is the per-axis weight matrix of hypervla.convert._scale_and_translate_weights(n, grid,
+ * (grid + 0.1) / n), computed on the host by that function and uploaded by the caller: the library restates no formula.  Height
+ * axis first, then width, each in f32 with ascending taps, as convert.bake_position_embeddings; n == grid copies the table.
+ * hvla_position_interp_adjoint: dsrc f32 [1 + n n, E] = A^T ddst f32 [1 + P, E] as a gather in ascending (i, j): no atomics,
+ * bit-reproducible.  All pointers DEVICE, 16-byte aligned.  HVLA_E_SHAPE: a NULL or misaligned pointer, n < 2.                */
+int hvla_position_interp(hvla_ctx* ctx, const float* src, int32_t n, const float* w, float* dst, void* stream);
+int hvla_position_interp_adjoint(hvla_ctx* ctx, const float* ddst, int32_t n, const float* w, float* dsrc, void* stream);
+/* Train the position table through its interpolation (n >= 2; n == 0 turns it off again, the state of a new context).  w as
+ * above, kept by POINTER and owned by the caller for as long as the source is on.  Off, or with train_encoder == 0, every
+ * hvla_train_* entry does exactly what it did.  On, with train_encoder != 0:
+ *   - the flat vector is [hypernetwork | encoder leaves | source table (1 + n n) E]: hvla_train_sizes reports it, bucket 0 of
+ *     hvla_train_bucket_ranges grows by the tail, params0 and wd_mask cover it.  The baked table's slot among the encoder leaves
+ *     stays where it is, as a derived quantity;
+ *   - hvla_train_step resizes tail -> slot in `params` before the encoder runs, carries the slot's gradient to the tail with the
+ *     adjoint after the encoder's backward and zeroes the slot's gradient, all before bucket 0's event;
+ *   - hvla_train_apply / hvla_train_accumulate take the norm and the shared group's AdamW over the tail too, then re-derive
+ *     the slot of `params` (and of `ema` when the EMA is on) from its tail;
+ *   - hvla_train_publish bakes the served position table from the tail of the vector it is given, with the same kernel (the
+ *     vector's own slot is not read for it and, like the rest of the vector, not written).                                  */
+int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w);
+
 /* Replaces: InferenceWrapper._resize_image (data/utils/hypervla_interface.py:89-121): optionally
  * tf.image.resize_with_pad(image, 256, 320) (bilinear, zero padding; `padded_resize`), then
  * tf.image.resize(lanczos3, antialias=True) to image_size x image_size, optionally the centred sqrt(0.9)
