@@ -86,6 +86,10 @@ struct hvla_ctx {
   static constexpr size_t ARENA_POOL_MAX = 4;
   int pos_n = 0;                 // hvla_train_position_source: side of the position table's source grid (0: the baked table is the parameter)
   const float* pos_w = nullptr;  //   its [n, grid] resize weights (device, the caller's)
+  const uint8_t* frozen = nullptr;   // hvla_train_frozen: device mask [frozen_n] of create_optimizer's frozen_keys (the caller's), or off
+  int64_t frozen_n = 0;              //   its length, one of the two of hvla_train_sizes when it was set ...
+  bool frozen_enc = false;           //   ... namely the one of this train_encoder value
+  int frozen_buckets = 0;            //   gradient buckets the caller declared wholly frozen (bits 0..2)
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
   ~hvla_ctx() {
@@ -763,6 +767,33 @@ int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w) {
   return HVLA_OK;
 }
 
+int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, int32_t frozen_buckets) {
+  if (!ctx) return HVLA_E_STATE;
+  if (!frozen) { ctx->frozen = nullptr; ctx->frozen_n = 0; ctx->frozen_enc = false; ctx->frozen_buckets = 0; return HVLA_OK; }
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
+  const TrainLayout L = make_train_layout(ctx->g);
+  const int64_t n_hyper = L.total, n_enc = L.total + L.enc_total + pos_source(ctx, true).tail();
+  if (n_params != n_hyper && n_params != n_enc)
+    FAIL(ctx, HVLA_E_SHAPE, "frozen mask of %lld elements: the training vector has %lld (frozen encoder) or %lld (trained encoder)",
+         (long long)n_params, (long long)n_hyper, (long long)n_enc);
+  const bool enc = n_params == n_enc;
+  if (frozen_buckets & ~7) FAIL(ctx, HVLA_E_SHAPE, "frozen_buckets 0x%x: buckets are 0, 1, 2", (unsigned)frozen_buckets);
+  if (enc && (frozen_buckets & 1)) FAIL(ctx, HVLA_E_SHAPE, "the whole image encoder frozen is train_encoder == 0");
+  ctx->frozen = frozen; ctx->frozen_n = n_params; ctx->frozen_enc = enc; ctx->frozen_buckets = frozen_buckets;
+  return HVLA_OK;
+}
+
+// the mask set by hvla_train_frozen must be the one of this call's train_encoder value and of the vector's present length (the
+// position source may have changed since): checked before anything is launched, so that no kernel indexes it past its end
+static int frozen_fits(hvla_ctx* ctx, const TrainLayout& L, bool train_encoder) {
+  if (!ctx->frozen) return HVLA_OK;
+  const int64_t n = L.total + (train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0);
+  if (ctx->frozen_enc != train_encoder || ctx->frozen_n != n)
+    FAIL(ctx, HVLA_E_STATE, "the frozen mask was set for train_encoder = %d and %lld elements, this call has train_encoder = %d and %lld: "
+         "call hvla_train_frozen first", (int)ctx->frozen_enc, (long long)ctx->frozen_n, (int)train_encoder, (long long)n);
+  return HVLA_OK;
+}
+
 static TrainBuffers to_tb(const hvla_train_buffers* b) {
   return TrainBuffers{b->params, b->grads, reinterpret_cast<__bf16*>(b->mu), b->nu, b->ema, b->theta, b->dtheta, b->work,
                       b->loss, b->actions, b->logits, b->sqsum, b->wd_mask, b->params0};
@@ -786,12 +817,13 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
   if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const TrainLayout L = make_train_layout(ctx->g);
+  if (int rc = frozen_fits(ctx, L, images != nullptr)) return rc;
   TrainInputs in{tok, mask, cls, tokens, images, target, tmask, amask};
   const TrainHyper hp = to_hp(hy);
   for (hipEvent_t& e : ctx->ev_bucket)
     if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIPCHK(ctx, train_step(ctx->g, L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : ctx->ev_bucket,
-                         pos_source(ctx, images != nullptr)));
+                         pos_source(ctx, images != nullptr), ctx->frozen ? ctx->frozen_buckets : 0));
   // ONE pending backward per ctx: the bucket events belong to the last hvla_train_step that ran a backward pass, and
   // hvla_train_wait_bucket refers to that step.  A forward-only step (evaluation between a step and its apply) records
   // nothing and leaves the pending step's events alone.
@@ -845,8 +877,9 @@ int hvla_train_apply(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_tr
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
+  if (int rc = frozen_fits(ctx, L, hy->train_encoder != 0)) return rc;
   HIPCHK(ctx, train_apply(L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
-                          pos_source(ctx, hy->train_encoder != 0)));
+                          pos_source(ctx, hy->train_encoder != 0), ctx->frozen));
   return HVLA_OK;
 }
 
@@ -857,8 +890,9 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const TrainLayout L = make_train_layout(ctx->g);
+  if (int rc = frozen_fits(ctx, L, hy->train_encoder != 0)) return rc;
   HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
-                               pos_source(ctx, hy->train_encoder != 0)));
+                               pos_source(ctx, hy->train_encoder != 0), ctx->frozen));
   return HVLA_OK;
 }
 

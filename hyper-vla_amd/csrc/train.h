@@ -88,11 +88,15 @@ struct PosSource {
 // leaves [total, total + enc_total) after the image encoder's backward (trained encoder only), [1] the output heads
 // [wcat, total) after the weight-generation backward, [2] the context encoder [0, wcat) at the end -- so that the caller's
 // all-reduce of a bucket runs under the rest of the backward pass.
+// frozen_buckets / frozen (hvla_train_frozen; 0 / nullptr: off, and exactly the launches without them): bit 1 leaves out dW_cat and
+// db_cat, bit 2 dctx and the context encoder's backward -- the skipped ranges of `grads` stay zero, all three events are still
+// recorded; `frozen` [n] (device, 1 = frozen) takes its elements out of the global norm and out of AdamW's loads and stores.
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr, const PosSource& ps = PosSource());
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr, const PosSource& ps = PosSource(),
+                      int frozen_buckets = 0);
 hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
-                       const PosSource& ps = PosSource());
+                       const PosSource& ps = PosSource(), const uint8_t* frozen = nullptr);
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st, const PosSource& ps = PosSource());
+                            bool train_encoder, hipStream_t st, const PosSource& ps = PosSource(), const uint8_t* frozen = nullptr);
 
 }  // namespace hvla

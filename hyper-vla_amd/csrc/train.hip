@@ -1075,6 +1075,48 @@ __global__ void adamw_shared_kernel(float* __restrict__ p, const float* __restri
   }
 }
 
+// ---- optimizer under create_optimizer(frozen_keys=...) (octo/utils/train_utils.py:242-292: multi_transform{trainable: the whole
+// chain, frozen: set_to_zero} by fnmatch over the leaf names; the host resolves the names into `frozen` [n], hvla_train_frozen).
+// The clip sits inside the trainable transform, so the global norm is taken over trainable elements only; a frozen element of
+// params / mu / nu / ema is neither loaded nor stored, and neither are its g and p0: the mask byte is all it costs.
+__global__ void sqsum_frozen_kernel(const float* __restrict__ g, const uint8_t* __restrict__ frozen, long n, float* __restrict__ out) {
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    if (!frozen[i]) { const float gi = g[i]; s += gi * gi; }
+  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) unsafeAtomicAdd(out, s);
+}
+// adamw_kernel (SHARED = false: p0 unused) / adamw_shared_kernel (SHARED = true) on the trainable elements
+template <bool SHARED>
+__global__ void adamw_frozen_kernel(float* __restrict__ p, const float* __restrict__ g, __bf16* __restrict__ mu,
+                                    float* __restrict__ nu, float* __restrict__ ema, const uint8_t* __restrict__ frozen, long n,
+                                    const float* __restrict__ sq, float clip, float lr, float b1, float b2, float eps, float wd,
+                                    const uint8_t* __restrict__ mask, const float* __restrict__ p0, float bc1, float bc2,
+                                    float ema_decay) {
+  const float norm = sqrtf(sq[0]);
+  const float sc = norm < clip ? 1.f : clip / norm;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    if (frozen[i]) continue;
+    const float gi = g[i] * sc;
+    const float m = b1 * (float)mu[i] + (1.f - b1) * gi;
+    const float v = b2 * nu[i] + (1.f - b2) * gi * gi;
+    mu[i] = (__bf16)m;
+    nu[i] = v;
+    float upd = (m / bc1) / (sqrtf(v / bc2) + eps);
+    if (SHARED) {
+      if (wd > 0.f) {
+        if (mask && mask[i]) upd += wd * p[i];
+        if (p0) upd -= wd * p0[i];
+      }
+    } else {
+      if (mask && mask[i]) upd += wd * p[i];
+    }
+    const float pn = p[i] - lr * upd;
+    p[i] = pn;
+    if (ema) ema[i] = ema_decay * ema[i] + (1.f - ema_decay) * pn;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host sequencing
 // ------------------------------------------------------------------------------------------------
@@ -1340,7 +1382,7 @@ size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
 }
 
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps) {
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps, int frozen_buckets) {
   const int S = g.S(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
   const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
@@ -1439,39 +1481,58 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     if (bucket_done) (void)hipEventRecord(bucket_done[0], st);           // the shared DINOv2 leaves are final
   }
   // =============================== weight generation backward ===============================
-  bgemm(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1}, 1);   // dW_cat = ctx^T dtheta
-  KL(colsum_kernel, dim3((unsigned)((G + 63) / 64), 1, (B + 63) / 64), dim3(64), tb.dtheta, Gm + L.bcat, 0, B, B, (int)G, 1);                  // db_cat
-  (void)hipMemsetAsync(dctx, 0, (size_t)B * C * 4, st);
-  // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
-  bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
+  // hvla_train_frozen: a bucket declared frozen is not computed -- its range of `grads` stays the zeros of the memset above, its
+  // event is recorded where it always is.  dtheta is complete here whatever is frozen.
+  const bool heads_on = !(frozen_buckets & 2), ctx_on = !(frozen_buckets & 4);
+  if (heads_on) {
+    bgemm(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1}, 1);   // dW_cat = ctx^T dtheta
+    KL(colsum_kernel, dim3((unsigned)((G + 63) / 64), 1, (B + 63) / 64), dim3(64), tb.dtheta, Gm + L.bcat, 0, B, B, (int)G, 1);                  // db_cat
+  }
+  if (ctx_on) {
+    (void)hipMemsetAsync(dctx, 0, (size_t)B * C * 4, st);
+    // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
+    bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
+  }
   if (bucket_done) (void)hipEventRecord(bucket_done[1], st);             // W_cat, b_cat are final
   // =============================== context encoder backward ===============================
-  (void)hipMemsetAsync(cdx, 0, (size_t)B * Sc * C * 4, st);
-  KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
-  for (int l = g.ctx_layers - 1; l >= 0; --l)
-    block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, cw(l), cg(l), cb[l], cdx, t, ctx_opt);
-  // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
-  KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
-  bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
-  bgemm(st, true, false, BG{in.cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
+  if (ctx_on) {
+    (void)hipMemsetAsync(cdx, 0, (size_t)B * Sc * C * 4, st);
+    KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+    for (int l = g.ctx_layers - 1; l >= 0; --l)
+      block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, cw(l), cg(l), cb[l], cdx, t, ctx_opt);
+    // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
+    KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
+    bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
+    bgemm(st, true, false, BG{in.cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
+  }
   if (bucket_done) (void)hipEventRecord(bucket_done[2], st);             // the context encoder's leaves: everything is final
   return hipGetLastError();
 }
 
 hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
-                       const PosSource& ps) {
+                       const PosSource& ps, const uint8_t* frozen) {
   const long tail = train_encoder ? ps.tail() : 0;           // the position table's source (shared group; the slot's gradient is zero)
   const long n = L.total + (train_encoder ? L.enc_total : 0) + tail;
   (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
-  KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);          // one global norm over both optimizer groups
   const float t = (float)(hp.step + 1);
   const float bc1 = 1.f - powf(hp.b1, t), bc2 = 1.f - powf(hp.b2, t);
-  KL(adamw_kernel, dim3(2048), dim3(256), tb.params, tb.grads, tb.mu, tb.nu, hp.ema_decay > 0.f ? tb.ema : nullptr, L.total, tb.sqsum,
-     hp.clip, hp.lr, hp.b1, hp.b2, hp.eps, hp.weight_decay, tb.wd_mask, bc1, bc2, hp.ema_decay);
-  if (train_encoder)
-    KL(adamw_shared_kernel, dim3(2048), dim3(256), tb.params + L.total, tb.grads + L.total, tb.mu + L.total, tb.nu + L.total,
-       hp.ema_decay > 0.f ? tb.ema + L.total : nullptr, L.enc_total + tail, tb.sqsum, hp.clip, hp.base_lr, hp.b1, hp.b2, hp.eps,
-       hp.base_weight_decay, tb.wd_mask ? tb.wd_mask + L.total : nullptr, tb.params0, bc1, bc2, hp.ema_decay);
+  if (frozen) {                                               // hvla_train_frozen: the norm and both groups over the trainable elements
+    KL(sqsum_frozen_kernel, dim3(1024), dim3(256), tb.grads, frozen, n, tb.sqsum);
+    KL(adamw_frozen_kernel<false>, dim3(2048), dim3(256), tb.params, tb.grads, tb.mu, tb.nu, hp.ema_decay > 0.f ? tb.ema : nullptr, frozen,
+       L.total, tb.sqsum, hp.clip, hp.lr, hp.b1, hp.b2, hp.eps, hp.weight_decay, tb.wd_mask, (const float*)nullptr, bc1, bc2, hp.ema_decay);
+    if (train_encoder)
+      KL(adamw_frozen_kernel<true>, dim3(2048), dim3(256), tb.params + L.total, tb.grads + L.total, tb.mu + L.total, tb.nu + L.total,
+         hp.ema_decay > 0.f ? tb.ema + L.total : nullptr, frozen + L.total, L.enc_total + tail, tb.sqsum, hp.clip, hp.base_lr, hp.b1, hp.b2,
+         hp.eps, hp.base_weight_decay, tb.wd_mask ? tb.wd_mask + L.total : nullptr, tb.params0, bc1, bc2, hp.ema_decay);
+  } else {
+    KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);          // one global norm over both optimizer groups
+    KL(adamw_kernel, dim3(2048), dim3(256), tb.params, tb.grads, tb.mu, tb.nu, hp.ema_decay > 0.f ? tb.ema : nullptr, L.total, tb.sqsum,
+       hp.clip, hp.lr, hp.b1, hp.b2, hp.eps, hp.weight_decay, tb.wd_mask, bc1, bc2, hp.ema_decay);
+    if (train_encoder)
+      KL(adamw_shared_kernel, dim3(2048), dim3(256), tb.params + L.total, tb.grads + L.total, tb.mu + L.total, tb.nu + L.total,
+         hp.ema_decay > 0.f ? tb.ema + L.total : nullptr, L.enc_total + tail, tb.sqsum, hp.clip, hp.base_lr, hp.b1, hp.b2, hp.eps,
+         hp.base_weight_decay, tb.wd_mask ? tb.wd_mask + L.total : nullptr, tb.params0, bc1, bc2, hp.ema_decay);
+  }
   if (tail) {                                                 // the derived slots follow their tails
     const long slot = L.total + L.e_pos, src = L.total + L.enc_total;
     (void)launch_position_interp(tb.params + src, ps.n, ps.w, tb.params + slot, ps.grid, ps.E, st);
@@ -1481,10 +1542,14 @@ hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const Train
 }
 
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st, const PosSource& ps) {
+                            bool train_encoder, hipStream_t st, const PosSource& ps, const uint8_t* frozen) {
   const long n = L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
   (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
-  KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);
+  if (frozen) {                                               // the clip's norm is over the trainable elements
+    KL(sqsum_frozen_kernel, dim3(1024), dim3(256), tb.grads, frozen, n, tb.sqsum);
+  } else {
+    KL(sqsum_kernel, dim3(1024), dim3(256), tb.grads, n, tb.sqsum);
+  }
   KL(accumulate_kernel, dim3(2048), dim3(256), acc, tb.grads, n, tb.sqsum, hp.clip, inv_k);
   return hipGetLastError();
 }

@@ -26,7 +26,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
            "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
-           "hvla_train_position_source"]
+           "hvla_train_position_source", "hvla_train_frozen"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -154,6 +154,8 @@ def load_library():
     lib.hvla_position_interp_adjoint.restype = C.c_int
     lib.hvla_train_position_source.argtypes = [vp, i32, vp]
     lib.hvla_train_position_source.restype = C.c_int
+    lib.hvla_train_frozen.argtypes = [vp, vp, i64, i32]
+    lib.hvla_train_frozen.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -399,6 +401,12 @@ class Context:
     def train_position_source(self, n, w_ptr=0):
         """Train the position table through its interpolation from an n x n source (n = 0: off); `w_ptr` stays the caller's."""
         self._check(self.lib.hvla_train_position_source(self.h, int(n), C.c_void_p(w_ptr or None)), "hvla_train_position_source")
+
+    def train_frozen(self, frozen_ptr=0, n_params=0, frozen_buckets=0):
+        """create_optimizer's frozen_keys as a device uint8 mask [n_params] (1 = frozen; 0 / None: off) and the gradient buckets
+        that are frozen as a whole (hypervla.train.frozen_plan); the mask stays the caller's."""
+        self._check(self.lib.hvla_train_frozen(self.h, C.c_void_p(frozen_ptr or None), int(n_params), int(frozen_buckets)),
+                    "hvla_train_frozen")
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

@@ -186,18 +186,79 @@ def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False, p
     return mask
 
 
+def frozen_plan(g: Geometry, frozen_keys, train_encoder: bool = False, position_source: int = 0,
+                base_weight_decay: float = 0.0) -> Tuple[np.ndarray, int]:
+    """(mask uint8 [n_params], frozen_buckets): `create_optimizer(frozen_keys=...)` (octo/utils/train_utils.py:242-292, 385,
+    428-439) over the flat vector.  The reference flattens the parameter tree, names a leaf `".".join(path)` and freezes it
+    (`multi_transform({"trainable": tx, "frozen": set_to_zero()})` round the whole chain) iff `fnmatch(name, key)` holds for any
+    key; a leaf's name here is its checkpoint name with "/" replaced by ".":  `Transformer_0.encoderblock_3.MlpBlock_0.Dense_0.kernel`,
+    `task_token_projection.bias`, `output_head_<flat base-net leaf>.kernel` / `.bias`, and the encoder leaves
+    `encoder_image_encoder_<...>`, each a single key without a dot.  Keys that match nothing are accepted silently, as by the
+    reference (its default `("*hf_model*",)` matches nothing in this tree).
+
+    W_cat / b_cat are the 73 heads fused: a frozen head freezes its column range in every row of W_cat (`.kernel`) or its range
+    of b_cat (`.bias`), per element, the way weight_decay_mask builds `cols`.  With `position_source` the tail IS the leaf
+    `encoder_image_encoder_embeddings_position_embeddings` and has its status; so has the baked slot, which is derived from it
+    (re-derived from an unchanged tail it keeps its bits).
+
+    `frozen_buckets` has bit b set iff every element of gradient bucket b (hvla_train_bucket_ranges: 0 encoder, 1 output heads,
+    2 context encoder) is frozen: hvla_train_step then does not compute that bucket.
+
+    ValueError: nothing trainable is left; the whole encoder is frozen with train_encoder=True (that is train_encoder=False);
+    an encoder leaf is frozen while base_weight_decay > 0 -- the reference adds its `delta_change_decay`
+    (scripts/train.py:465-471) after `tx.update`, so there a "frozen" encoder leaf still moves towards the pretrained weights.
+    That is not reproduced: frozen means untouched here."""
+    from fnmatch import fnmatch
+    keys = (frozen_keys,) if isinstance(frozen_keys, str) else tuple(frozen_keys)
+    hit = lambda name: any(fnmatch(name.replace("/", "."), k) for k in keys)
+    layout, total = train_param_layout(g, train_encoder, position_source)
+    leaves = generated_leaves(g)
+    G = leaves[-1].offset + leaves[-1].size
+    wcols, bcols = np.zeros(G, np.uint8), np.zeros(G, np.uint8)
+    for l in leaves:
+        wcols[l.offset:l.offset + l.size] = hit(l.head_name + "/kernel")
+        bcols[l.offset:l.offset + l.size] = hit(l.head_name + "/bias")
+    mask = np.zeros(total, np.uint8)
+    for name, off, shape in layout:
+        n = int(np.prod(shape))
+        if name == "W_cat":
+            mask[off:off + n] = np.tile(wcols, shape[0])
+        elif name == "b_cat":
+            mask[off:off + n] = bcols
+        else:                                     # the tail under the name of the leaf it is
+            mask[off:off + n] = hit(POSITION_LEAF if name == POSITION_SOURCE else name)
+    if mask.all():
+        raise ValueError(f"frozen_keys {keys!r} freeze every parameter: nothing is left to train")
+    flags = 0
+    for name, off, n in gradient_buckets(g, train_encoder, position_source):
+        if mask[off:off + n].all():
+            flags |= 1 << {"image_encoder": 0, "output_heads": 1, "context_encoder": 2}[name]
+    if flags & 1:
+        raise ValueError(f"frozen_keys {keys!r} freeze every leaf of the image encoder: use train_encoder=False, which neither "
+                         "differentiates the encoder nor keeps optimizer state for it")
+    n_hyper = total if not train_encoder else gradient_buckets(g, True, position_source)[0][1]
+    if base_weight_decay > 0 and mask[n_hyper:].any():
+        raise ValueError("frozen_keys freeze image-encoder leaves while base_weight_decay > 0: the reference adds its pull towards "
+                         "the pretrained encoder (delta_change_decay, scripts/train.py:465-471) after the optimizer's update, so "
+                         "its 'frozen' encoder leaves still move.  That is not reproduced here (a frozen element is never "
+                         "written): freeze encoder leaves with base_weight_decay=0, or freeze none of them")
+    return mask, flags
+
+
 class FineTuner:
     """One optimizer state of the fine-tune step.  Defaults are the README run's (README.md:29-31,61 and
     scripts/configs/hypervla_pretrain_config.py:286-321): weight_decay_strategy v5, learning rate 3e-4 (rsqrt) for the
     hypernetwork and 3e-5 for the shared image encoder, base_weight_decay 0, no gradient accumulation, EMA 0.999 started at
     update 5000 (`ema_start_step`; the EMA is a copy of the parameters at that update and an average afterwards,
-    scripts/train.py:681-690)."""
+    scripts/train.py:681-690).  `frozen_keys`: the reference's create_optimizer(frozen_keys=...) -- fnmatch patterns over the dotted
+    leaf names (frozen_plan); matching elements keep their parameters, moments and EMA bit for bit, stay out of the clip's global
+    norm, and a gradient bucket that is frozen as a whole is neither computed nor all-reduced."""
 
     def __init__(self, model, batch: int, peak_lr: float = 3e-4, weight_decay: float = 0.05, clip: float = 1.0,
                  ema_decay: float = 0.999, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
-                 accept_baked_position_table: bool = False):
+                 accept_baked_position_table: bool = False, frozen_keys=()):
         if getattr(model.geometry, "lang_in_policy", False):
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")
@@ -222,7 +283,14 @@ class FineTuner:
         if self.source_n:
             from .convert import position_interp_weights
             self.interp_w = torch.as_tensor(position_interp_weights(self.source_n, self.g.grid)).to(dev).contiguous()
+        # create_optimizer(frozen_keys=...): fnmatch patterns over the dotted leaf names (frozen_plan); no match, no mask
+        self.frozen_keys = (frozen_keys,) if isinstance(frozen_keys, str) else tuple(frozen_keys)
+        plan, self.frozen_buckets = frozen_plan(self.g, self.frozen_keys, self.train_encoder, self.source_n, base_weight_decay)
+        self.frozen_count = int(plan.sum())
+        self.trainable_count = int(plan.size) - self.frozen_count
+        self.frozen = torch.as_tensor(plan).to(dev) if self.frozen_count else None
         self._select_source()
+        self._select_frozen()
         n, G, work, n_hyper = model._ctx.train_sizes(batch, self.train_encoder)
         layout, total = train_param_layout(self.g, self.train_encoder, self.source_n)
         assert n == total, (n, total)
@@ -263,6 +331,14 @@ class FineTuner:
         """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this
         one trains (hvla_train_position_source; a host-side setting, nothing is launched)."""
         self.model._ctx.train_position_source(self.source_n, self.interp_w.data_ptr() if self.source_n else 0)
+
+    def _select_frozen(self):
+        """... and which elements it leaves alone (hvla_train_frozen: the mask by pointer and the buckets frozen_plan found wholly
+        frozen, or NULL; a host-side setting like the one above, after it because the mask's length depends on the source)."""
+        if self.frozen is None:
+            self.model._ctx.train_frozen(0, 0, 0)
+        else:
+            self.model._ctx.train_frozen(self.frozen.data_ptr(), self.frozen.numel(), self.frozen_buckets)
 
     def _derive_slot(self, layout):
         """The baked slot of `params` becomes the device's own resize of the tail (bitwise what every later step and apply
@@ -333,6 +409,7 @@ class FineTuner:
         self._keep = (tok, msk, cls, obs, tgt, am, tm)
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
         self._select_source()
+        self._select_frozen()
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
         return self.loss
 
@@ -354,6 +431,8 @@ class FineTuner:
         works = []
         with torch.cuda.stream(self._comm):
             for i, (_, off, n) in enumerate(self.buckets):
+                if self.frozen_buckets >> self._bucket_id[i] & 1:     # wholly frozen (frozen_keys): not computed, nobody reads it
+                    continue
                 m._ctx.train_wait_bucket(self._bucket_id[i], self._comm.cuda_stream)
                 works.append(dist.all_reduce(self.grads[off:off + n], async_op=True))
             for w in works:
@@ -368,6 +447,7 @@ class FineTuner:
         self.all_reduce_gradient()
         ctx, st = self.model._ctx, self.model._stream()
         self._select_source()
+        self._select_frozen()
         if self.accum_k > 1:
             if self.micro == 0:
                 self.acc.zero_()
@@ -414,6 +494,7 @@ class FineTuner:
         m = self.model
         vec = self.ema if ema else self.params
         self._select_source()
+        self._select_frozen()
         if self.source_n:                          # the slot the host copy reads is the resize of the tail being published, whatever
             m._ctx.position_interp(vec[self.tail].data_ptr(), self.source_n, self.interp_w.data_ptr(),     # was done to the vector
                                    vec[self.slot].data_ptr(), m._stream())

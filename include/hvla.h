@@ -360,6 +360,27 @@ int hvla_position_interp_adjoint(hvla_ctx* ctx, const float* ddst, int32_t n, co
  *   - hvla_train_publish bakes the served position table from the tail of the vector it is given, with the same kernel (the
  *     vector's own slot is not read for it and, like the rest of the vector, not written).                                  */
 int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w);
+/* Replaces: `create_optimizer(frozen_keys=...)` (octo/utils/train_utils.py:242-292 freeze_weights, applied at :428-439): fnmatch
+ * patterns over the parameter tree, wrapped round the whole chain as multi_transform({"trainable": tx, "frozen": set_to_zero()}).
+ * The caller resolves the patterns (hypervla.train.frozen_plan) into `frozen`, DEVICE uint8 [n_params], 1 = frozen, kept by
+ * POINTER and owned by the caller while set; NULL turns it off again (n_params and frozen_buckets are then ignored), the state of
+ * a new context, in which every hvla_train_* entry launches exactly what it launched.  A host-side setting: nothing is launched,
+ * hvla_train_buffers / hvla_train_hyper keep their layout.  Set:
+ *   - hvla_train_apply / hvla_train_accumulate take the global norm over the trainable elements only (the reference's clip sits
+ *     inside the trainable transform); sqsum[0] is that sum.  AdamW, in both groups, neither loads nor stores a frozen element of
+ *     params / mu / nu / ema (nor its grads / params0): they keep their bits;
+ *   - frozen_buckets: bit b = bucket b of hvla_train_bucket_ranges is frozen as a whole, the caller's declaration.  A bucket
+ *     declared frozen is not computed: bit 1 leaves out dW_cat and db_cat, bit 2 everything behind bucket 1's event and the
+ *     product dctx = dtheta W_cat^T before it; its range of `grads` stays zero.  All events are recorded where they always are
+ *     (hvla_train_wait_bucket keeps working).  If the mask disagrees with the declaration, the bucket's elements see zero
+ *     gradients; nothing is read out of bounds either way.  Frozen elements of a computed bucket get their gradients in `grads`;
+ *     the optimizer ignores them.
+ * HVLA_E_SHAPE at set time: n_params is not hvla_train_sizes(...)[0] for one of the two train_encoder values under the current
+ * position source (the value it matches is remembered); bits outside 0..2; bit 0 with the trained encoder's length (that is
+ * train_encoder == 0).  HVLA_E_STATE from hvla_train_step (forward-only too), hvla_train_apply and hvla_train_accumulate, before
+ * any launch, while a mask is set for the other train_encoder value than hyper->train_encoder (or the position source changed
+ * the vector's length since).                                                                                                */
+int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, int32_t frozen_buckets);
 
 /* Replaces: InferenceWrapper._resize_image (data/utils/hypervla_interface.py:89-121): optionally
  * tf.image.resize_with_pad(image, 256, 320) (bilinear, zero padding; `padded_resize`), then
