@@ -90,6 +90,7 @@ struct hvla_ctx {
   int64_t frozen_n = 0;              //   its length, one of the two of hvla_train_sizes when it was set ...
   bool frozen_enc = false;           //   ... namely the one of this train_encoder value
   int frozen_buckets = 0;            //   gradient buckets the caller declared wholly frozen (bits 0..2)
+  AttnAux aux;                       // hvla_train_attention_losses: weights, the reference map and the metric outputs (the caller's), or off
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
   ~hvla_ctx() {
@@ -783,6 +784,18 @@ int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, in
   return HVLA_OK;
 }
 
+int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts) {
+  if (!ctx) return HVLA_E_STATE;
+  if (!opts) { ctx->aux = AttnAux(); return HVLA_OK; }
+  if (opts->struct_size != sizeof(hvla_train_attention)) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_attention.struct_size %u: this library's is %zu", opts->struct_size, sizeof(hvla_train_attention));
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
+  const float we = opts->entropy_weight, wa = opts->alignment_weight;
+  if (!std::isfinite(we) || !std::isfinite(wa) || we < 0.f || wa < 0.f) FAIL(ctx, HVLA_E_SHAPE, "attention loss weights (%g, %g) must be finite and >= 0", (double)we, (double)wa);
+  if (wa > 0.f && !opts->reference_map) FAIL(ctx, HVLA_E_SHAPE, "alignment_weight %g > 0 needs reference_map [B, P]", (double)wa);
+  ctx->aux.w_ent = we; ctx->aux.w_align = wa; ctx->aux.ref = opts->reference_map; ctx->aux.ent = opts->entropy; ctx->aux.align = opts->alignment;
+  return HVLA_OK;
+}
+
 // the mask set by hvla_train_frozen must be the one of this call's train_encoder value and of the vector's present length (the
 // position source may have changed since): checked before anything is launched, so that no kernel indexes it past its end
 static int frozen_fits(hvla_ctx* ctx, const TrainLayout& L, bool train_encoder) {
@@ -823,7 +836,7 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
   for (hipEvent_t& e : ctx->ev_bucket)
     if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIPCHK(ctx, train_step(ctx->g, L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : ctx->ev_bucket,
-                         pos_source(ctx, images != nullptr), ctx->frozen ? ctx->frozen_buckets : 0));
+                         pos_source(ctx, images != nullptr), ctx->frozen ? ctx->frozen_buckets : 0, ctx->aux));
   // ONE pending backward per ctx: the bucket events belong to the last hvla_train_step that ran a backward pass, and
   // hvla_train_wait_bucket refers to that step.  A forward-only step (evaluation between a step and its apply) records
   // nothing and leaves the pending step's events alone.

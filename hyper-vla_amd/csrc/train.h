@@ -91,9 +91,20 @@ struct PosSource {
 // frozen_buckets / frozen (hvla_train_frozen; 0 / nullptr: off, and exactly the launches without them): bit 1 leaves out dW_cat and
 // db_cat, bit 2 dctx and the context encoder's backward -- the skipped ranges of `grads` stay zero, all three events are still
 // recorded; `frozen` [n] (device, 1 = frozen) takes its elements out of the global norm and out of AdamW's loads and stores.
+// The attention terms of the reference's sample_loss_fn (hvla_train_attention_losses; scripts/train.py:348-373), both on the action
+// token's attention row of the last policy layer: loss_b += w_ent ent_b + w_align align_b.  Off (both weights 0, the default):
+// train_step launches exactly what it launches without this struct.  On: attention_aux_kernel once behind head_loss_kernel (also
+// forward-only) and once inside the last policy layer's backward; no workspace.
+struct AttnAux {
+  float w_ent = 0.f, w_align = 0.f;   // w_align: the effective, already annealed weight
+  const float* ref = nullptr;         // [B, P] DINOv2's last-layer CLS attention over the patches, mean over heads (device; read iff w_align > 0)
+  float* ent = nullptr;               // [B] out, nullable: ent_b
+  float* align = nullptr;             // [B] out, nullable: align_b (written iff w_align > 0)
+  bool on() const { return w_ent > 0.f || w_align > 0.f; }
+};
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
                       const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr, const PosSource& ps = PosSource(),
-                      int frozen_buckets = 0);
+                      int frozen_buckets = 0, const AttnAux& aux = AttnAux());
 hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
                        const PosSource& ps = PosSource(), const uint8_t* frozen = nullptr);
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,

@@ -948,6 +948,62 @@ __global__ void head_loss_kernel(HeadP p) {
   p.dxrow[(long)b * p.D + lane] = r * (dxh - s1 / 64.f - xh[lane] * s2 / 64.f);
 }
 
+// The two attention terms of the reference's sample_loss_fn (scripts/train.py:348-373; hvla_train_attention_losses), on the action
+// token's softmax row p[h][k] (query S-1, all S keys: the row is unmasked) of the LAST policy layer, one workgroup per episode:
+//   ent = 1/H sum_h -sum_{k<S} p log(p + 1e-8);  m[k] = 1/H sum_h p[h][k];  align = 1/P sum_{k<P} (m[k] - ref[k])^2
+// dp == null (LOSS): loss[b] += w_ent ent + w_align align, behind head_loss_kernel; the two terms also go to ent[] / align[].
+// dp != null (GRAD): row S-1 of dp[b][h] += gscale d(w_ent ent + w_align align)/dp[h][k], between dp = do v^T and softmax_bwd_kernel;
+// recomputed from p, no workspace.  A thread owns keys k, k + 256, ..: the sums run in a fixed order (lanes by xor-shuffle, waves in
+// ascending order by one thread), no atomics -- the forward loss stays bit-reproducible.
+struct AuxP {
+  const float* p; float* dp;                // [B][H][S][Sp]
+  long sb, sh;                              // episode and head stride of both
+  int S, Sp, H, P;
+  float w_ent, w_align;
+  const float* ref;                         // [B][P], or null (then w_align == 0)
+  float* loss; float* ent; float* align;    // [B]; ent / align nullable
+  float gscale;                             // the seed's factor of d mean_b loss_b: 1 / B (head_loss_kernel's gb)
+};
+__global__ __launch_bounds__(256) void attention_aux_kernel(AuxP a) {
+  __shared__ float red[2][4];
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long o = (long)b * a.sb + (long)(a.S - 1) * a.Sp;
+  const float* row = a.p + o;
+  const float* r = a.ref ? a.ref + (long)b * a.P : nullptr;
+  const float invH = 1.f / (float)a.H, eps = 1e-8f;
+  const float ge = a.gscale * a.w_ent * invH, ga = a.gscale * a.w_align * 2.f * invH / (float)a.P;
+  float es = 0.f, as = 0.f;
+  for (int k = threadIdx.x; k < a.S; k += 256) {
+    float m = 0.f, e = 0.f;
+    for (int h = 0; h < a.H; ++h) {
+      const float pv = row[h * a.sh + k];
+      m += pv;
+      e -= pv * logf(pv + eps);
+    }
+    const float d = r && k < a.P ? m * invH - r[k] : 0.f;       // the action key counts for the entropy only
+    es += e;
+    as += d * d;
+    if (a.dp) {
+      float* drow = a.dp + o;
+      for (int h = 0; h < a.H; ++h) {
+        const float pv = row[h * a.sh + k];
+        drow[h * a.sh + k] += ge * (-logf(pv + eps) - pv / (pv + eps)) + ga * d;
+      }
+    }
+  }
+  if (a.dp) return;
+  for (int s = 32; s; s >>= 1) { es += __shfl_xor(es, s, 64); as += __shfl_xor(as, s, 64); }
+  if (lane == 0) { red[0][wave] = es; red[1][wave] = as; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float ent = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * invH;
+    const float al = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / (float)a.P;
+    a.loss[b] += a.w_ent * ent + a.w_align * al;
+    if (a.ent) a.ent[b] = ent;
+    if (a.align && r) a.align[b] = al;
+  }
+}
+
 // context-token assembly: rows t < T += pos_tok[t]; row T += pos_img; row T+1 = pos_layer (hypernetwork.py:112-145)
 __global__ void ctx_rows_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
                                 const float* __restrict__ pos_layer, int B, int T, int C) {
@@ -1236,8 +1292,9 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
 
 // dx (in/out: gradient wrt the block output on entry, wrt its input on exit).  Weight gradients: per-episode
 // (gs = G) written per b; shared (gs = 0) reduced over the batch by folding it into the GEMM's M/K dimension.
+// aux (nullable; the last policy layer under hvla_train_attention_losses): the attention terms' gradient joins dp in front of the softmax backward.
 static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long ws, long gs, const BlkW& w, const BlkG& gw,
-                      const BlkBuf& a, float* dx, const BlkTmp& t, const BlkOpt& op) {
+                      const BlkBuf& a, float* dx, const BlkTmp& t, const BlkOpt& op, const AuxP* aux = nullptr) {
   const int hd = D / H, rows = nb * S;
   const bool shared = gs == 0;
   auto wgrad = [&](const float* X, int K, const float* dY, int N, float* dW) {   // dW[K][N] (+)= X^T dY
@@ -1305,6 +1362,7 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   auto padded = [](BG g) { g.a_padded = 1; return g; };
   bgemm(st, false, true, BG{t.d, a.v, t.dp, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
   bgemm(st, true, false, padded(BG{a.p, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
+  if (aux) KL(attention_aux_kernel, dim3(nb), dim3(256), *aux);                                                            // dp row S-1 += d aux / dp
   KL(softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dp, nb * H * S, S, Sp);                             // ds
   const float sc = 1.f / sqrtf((float)hd);
   bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);   // dq = ds k / sqrt(hd)
@@ -1382,7 +1440,8 @@ size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
 }
 
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps, int frozen_buckets) {
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps, int frozen_buckets,
+                      const AttnAux& aux) {
   const int S = g.S(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
   const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
@@ -1449,11 +1508,17 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   HeadP hpp{px_fin, (long)S * D, TH, tb.dtheta, G, off.wc, off.bc, off.wd, off.bd, off.ns, off.nb, in.target, in.tmask, in.amask,
             tb.loss, hp.forward_only ? nullptr : dxrow, tb.actions, tb.logits, B, S, D, g.horizon, g.action_dim, g.tanh_scale, g.max_action, g.clip_target};
   KL(head_loss_kernel, dim3(B), dim3(64), hpp);
+  // hvla_train_attention_losses: the last layer's action row, [B][H][S][Sp] like t.dp (block_fwd / block_bwd)
+  const int Sp = (S + 3) & ~3;
+  AuxP auxp{pb[g.L - 1].p, nullptr, (long)H * S * Sp, (long)S * Sp, S, Sp, H, P, aux.w_ent, aux.w_align, aux.w_align > 0.f ? aux.ref : nullptr,
+            tb.loss, aux.ent, aux.align, 1.f / (float)B};
+  if (aux.on()) KL(attention_aux_kernel, dim3(B), dim3(256), auxp);
   if (hp.forward_only) return hipGetLastError();
+  auxp.dp = t.dp;
   KL(add_strided_kernel, g1((long)B * D), dim3(256), pdx + (long)(S - 1) * D, (long)S * D, dxrow, (long)D, B);
   // =============================== policy backward ===============================
   for (int l = g.L - 1; l >= 0; --l)
-    block_bwd(st, B, S, D, H, F, G, G, pw(l, TH), pg(l, tb.dtheta), pb[l], pdx, t, pol_opt);
+    block_bwd(st, B, S, D, H, F, G, G, pw(l, TH), pg(l, tb.dtheta), pb[l], pdx, t, pol_opt, aux.on() && l == g.L - 1 ? &auxp : nullptr);
   // x0 = [tokens Wp + bp ; 0] + pos : dpos = dx0, dbp = sum_{t<P} dx0, dWp = tokens^T dx0[:P]
   KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + off.pos, G, pdx, (long)S * D, B);
   KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx, tb.dtheta + off.bp, G, S, P, D, B);

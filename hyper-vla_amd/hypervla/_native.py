@@ -26,7 +26,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
            "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
-           "hvla_train_position_source", "hvla_train_frozen"]
+           "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -67,6 +67,12 @@ class hvla_train_hyper(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("lr", "b1", "b2", "eps", "weight_decay", "clip", "ema_decay")] + \
                [("step", C.c_int32), ("forward_only", C.c_int32), ("base_lr", C.c_float),
                 ("base_weight_decay", C.c_float), ("train_encoder", C.c_int32)]
+
+
+class hvla_train_attention(C.Structure):
+    """Options of hvla_train_attention_losses (include/hvla.h): struct_size must be sizeof(hvla_train_attention)."""
+    _fields_ = [("struct_size", C.c_uint32), ("entropy_weight", C.c_float), ("alignment_weight", C.c_float),
+                ("reference_map", C.c_void_p), ("entropy", C.c_void_p), ("alignment", C.c_void_p)]
 
 
 class hvla_post_row(C.Structure):
@@ -156,6 +162,8 @@ def load_library():
     lib.hvla_train_position_source.restype = C.c_int
     lib.hvla_train_frozen.argtypes = [vp, vp, i64, i32]
     lib.hvla_train_frozen.restype = C.c_int
+    lib.hvla_train_attention_losses.argtypes = [vp, C.POINTER(hvla_train_attention)]
+    lib.hvla_train_attention_losses.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -407,6 +415,17 @@ class Context:
         that are frozen as a whole (hypervla.train.frozen_plan); the mask stays the caller's."""
         self._check(self.lib.hvla_train_frozen(self.h, C.c_void_p(frozen_ptr or None), int(n_params), int(frozen_buckets)),
                     "hvla_train_frozen")
+
+    def train_attention_losses(self, entropy_weight=0.0, alignment_weight=0.0, reference_ptr=0, entropy_ptr=0, alignment_ptr=0):
+        """The reference's attention entropy / alignment terms for the following train_step calls (both weights 0: off, passed as
+        NULL); `alignment_weight` is the annealed weight, the device pointers (map [B, P] in, the two [B] metric outputs) stay the caller's."""
+        if not (entropy_weight or alignment_weight):
+            rc = self.lib.hvla_train_attention_losses(self.h, None)
+        else:
+            opts = hvla_train_attention(C.sizeof(hvla_train_attention), float(entropy_weight), float(alignment_weight),
+                                        reference_ptr or None, entropy_ptr or None, alignment_ptr or None)
+            rc = self.lib.hvla_train_attention_losses(self.h, C.byref(opts))
+        self._check(rc, "hvla_train_attention_losses")
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

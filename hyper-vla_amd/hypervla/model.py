@@ -501,6 +501,29 @@ class HyperVLA:
         self._ctx.encode(img.data_ptr(), tokens.data_ptr(), B, self._stream())
         return tokens
 
+    def reference_attention_map(self, images):
+        """The alignment term's target of the fine-tune step (`FineTuner(attention_map_alignment=...)`): uint8 frames
+        [B, (1,) H, W, 3] -> f32 [B, P] CUDA tensor, DINOv2's last-layer attention of the CLS query over the patches, mean over
+        heads -- the reference's `DINO_outputs.attentions[-1][:, :, 0, 1:].mean(1)` (scripts/train.py:366-368,432-438).
+        It is the serving encoder's `dino_cls_attention` output (`sample_actions(..., attention_maps=True)`), last layer.  The
+        reference takes this map from the PRETRAINED encoder (`pretrained_image_encoder`, not the copy being fine-tuned): take it
+        before any `publish()` of a trained encoder, or from a second model that keeps the pretrained weights.  The serving encoder
+        computes with 16-bit operands; for a constant target that the loss only pulls towards, that precision is enough."""
+        torch = _torch()
+        g = self.geometry
+        img = self._dev(images, torch.uint8)
+        if img.dim() == 5:
+            img = img[:, 0].contiguous()
+        B = img.shape[0]
+        tokens = torch.empty(B, g.patches, g.enc_dim, dtype=torch.float32, device=self.device)
+        maps = torch.empty(B, g.enc_layers, g.enc_heads, g.patches, dtype=torch.float32, device=self.device)
+        self._ctx.set_attention_outputs(maps.data_ptr(), 0)
+        try:
+            self._ctx.encode(img.data_ptr(), tokens.data_ptr(), B, self._stream())
+        finally:
+            self._ctx.set_attention_outputs(0, 0)
+        return maps[:, -1].mean(1)
+
     def encode_initial_image(self, images):
         """The evaluators' `DINO_encode_image(initial_image).last_hidden_state` on the device
         (data/simpler/evaluate.py:155-163,264-274): uint8 [B, (1,) H, W, 3] -> f32 [B, 1 + P, E] (row 0 = CLS), ready to

@@ -245,6 +245,39 @@ def frozen_plan(g: Geometry, frozen_keys, train_encoder: bool = False, position_
     return mask, flags
 
 
+def attention_loss_plan(attention_entropy: float = 0.0, attention_map_alignment: float = 0.0, num_steps=None):
+    """(entropy coefficient, alignment coefficient, num_steps) of `config.auxiliary_loss.attention_entropy` /
+    `.attention_map_alignment` (scripts/train.py:348-373), checked.  The alignment term is annealed by 1 - step / num_steps
+    (:370-371), so a positive alignment coefficient needs the run's `num_steps`."""
+    ent, ali = float(attention_entropy), float(attention_map_alignment)
+    if not (np.isfinite(ent) and np.isfinite(ali) and ent >= 0.0 and ali >= 0.0):
+        raise ValueError(f"attention_entropy {attention_entropy!r} / attention_map_alignment {attention_map_alignment!r} must be finite and >= 0")
+    if ali > 0.0 and (num_steps is None or int(num_steps) < 1):
+        raise ValueError("attention_map_alignment > 0 needs num_steps >= 1: the reference anneals the term by 1 - step / num_steps "
+                         "(scripts/train.py:370-371)")
+    return ent, ali, None if num_steps is None else int(num_steps)
+
+
+def alignment_weight(attention_map_alignment: float, step: int, num_steps) -> float:
+    """`annealing_factor * attention_map_alignment` of scripts/train.py:370-371 at update `step` (the reference's `state.step`);
+    zero, not negative, past the end of the schedule."""
+    if not attention_map_alignment > 0.0:
+        return 0.0
+    return max(0.0, 1.0 - float(step) / float(num_steps)) * float(attention_map_alignment)
+
+
+def check_reference_attention(attention_map_alignment: float, reference_attention, batch: int, patches: int):
+    """`reference_attention` is needed exactly when the alignment coefficient is positive, as [batch, patches]."""
+    if not attention_map_alignment > 0.0:
+        return
+    if reference_attention is None:
+        raise ValueError("attention_map_alignment > 0 needs reference_attention [B, P]: the pretrained DINOv2's last-layer CLS "
+                         "attention over the patches, mean over heads (HyperVLA.reference_attention_map)")
+    shape = tuple(reference_attention.shape) if hasattr(reference_attention, "shape") else np.shape(reference_attention)
+    if shape != (batch, patches):
+        raise ValueError(f"reference_attention must be [{batch}, {patches}], got {shape}")
+
+
 class FineTuner:
     """One optimizer state of the fine-tune step.  Defaults are the README run's (README.md:29-31,61 and
     scripts/configs/hypervla_pretrain_config.py:286-321): weight_decay_strategy v5, learning rate 3e-4 (rsqrt) for the
@@ -252,13 +285,20 @@ class FineTuner:
     update 5000 (`ema_start_step`; the EMA is a copy of the parameters at that update and an average afterwards,
     scripts/train.py:681-690).  `frozen_keys`: the reference's create_optimizer(frozen_keys=...) -- fnmatch patterns over the dotted
     leaf names (frozen_plan); matching elements keep their parameters, moments and EMA bit for bit, stay out of the clip's global
-    norm, and a gradient bucket that is frozen as a whole is neither computed nor all-reduced."""
+    norm, and a gradient bucket that is frozen as a whole is neither computed nor all-reduced.
+    `attention_entropy`, `attention_map_alignment`: the coefficients of `config.auxiliary_loss` (scripts/train.py:348-373, default 0 =
+    off): the entropy of the action token's attention row in the last policy layer, and its squared distance to `reference_attention`
+    (forward_backward / step; `model.reference_attention_map(images)`), annealed by 1 - step_count / `num_steps`.  Both are added to
+    every sample's loss; `aux_metrics` holds the un-weighted terms of the last step under the reference's metric names."""
 
     def __init__(self, model, batch: int, peak_lr: float = 3e-4, weight_decay: float = 0.05, clip: float = 1.0,
                  ema_decay: float = 0.999, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
-                 accept_baked_position_table: bool = False, frozen_keys=()):
+                 accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
+                 attention_map_alignment: float = 0.0, num_steps=None):
+        self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
+            attention_entropy, attention_map_alignment, num_steps)
         if getattr(model.geometry, "lang_in_policy", False):
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")
@@ -309,6 +349,10 @@ class FineTuner:
         self.loss = torch.zeros(batch, **f32)
         self.actions = torch.zeros(batch, self.g.horizon, self.g.action_dim, **f32)
         self.logits = torch.zeros(batch, self.g.horizon, **f32)
+        # hvla_train_attention_losses' metric outputs: ent_b / align_b of the last step
+        self.aux_entropy = torch.zeros(batch, **f32) if self.attention_entropy > 0 else None
+        self.aux_alignment = torch.zeros(batch, **f32) if self.attention_map_alignment > 0 else None
+        self.aux_metrics: Dict[str, "torch.Tensor"] = {}
         self.sqsum = torch.zeros(1, **f32)
         self.weight_decay_strategy = weight_decay_strategy
         self.wd_mask = torch.as_tensor(weight_decay_mask(self.g, weight_decay_strategy, self.train_encoder, self.source_n)).to(dev)
@@ -339,6 +383,16 @@ class FineTuner:
             self.model._ctx.train_frozen(0, 0, 0)
         else:
             self.model._ctx.train_frozen(self.frozen.data_ptr(), self.frozen.numel(), self.frozen_buckets)
+
+    def _select_attention(self, reference=None):
+        """... and which attention terms its loss has (hvla_train_attention_losses; off for a FineTuner without them).  The alignment
+        weight is annealed with this tuner's count of applied updates, the reference's `state.step`."""
+        wa = alignment_weight(self.attention_map_alignment, self.step_count, self.num_steps)
+        self.model._ctx.train_attention_losses(
+            self.attention_entropy, wa, reference.data_ptr() if wa > 0 else 0,
+            self.aux_entropy.data_ptr() if self.aux_entropy is not None else 0,
+            self.aux_alignment.data_ptr() if wa > 0 else 0)
+        return wa
 
     def _derive_slot(self, layout):
         """The baked slot of `params` becomes the device's own resize of the tail (bitwise what every later step and apply
@@ -379,9 +433,12 @@ class FineTuner:
                                         self.step_count, int(forward_only), lr if base_lr is None else base_lr,
                                         h["base_weight_decay"], int(self.train_encoder))
 
-    def forward_backward(self, instruction_dict, initial_state, tokens_or_images, batch, forward_only=False):
+    def forward_backward(self, instruction_dict, initial_state, tokens_or_images, batch, forward_only=False,
+                         reference_attention=None):
         """loss [B] (device) after writing self.grads = d mean(loss) / d params.  The fourth argument is the frozen
-        encoder's patch tokens f32 [B, P, E], or -- with train_encoder -- the uint8 observations [B, (1,) H, W, 3]."""
+        encoder's patch tokens f32 [B, P, E], or -- with train_encoder -- the uint8 observations [B, (1,) H, W, 3].
+        `reference_attention` (device or host float32 [B, P]; needed iff attention_map_alignment > 0): the alignment term's target."""
+        check_reference_attention(self.attention_map_alignment, reference_attention, self.B, self.g.patches)
         torch, m, g = self.torch, self.model, self.g
         li = instruction_dict["language_instruction"]
         if "token_embedding" not in li:                    # frozen T5 inside the step, as scripts/train.py:407-415
@@ -406,11 +463,19 @@ class FineTuner:
         am = m._dev(np.asarray(batch["action_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
         tm = m._dev(np.asarray(batch["timestep_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
         assert tok.shape[0] == self.B
+        ref = m._dev(reference_attention, torch.float32) if self.attention_map_alignment > 0 else None
         self._keep = (tok, msk, cls, obs, tgt, am, tm)
+        self._keep_reference = ref
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
         self._select_source()
         self._select_frozen()
+        wa = self._select_attention(ref)
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
+        self.aux_metrics = {}
+        if self.attention_entropy > 0:
+            self.aux_metrics["attention_entropy_loss"] = self.aux_entropy
+        if wa > 0:
+            self.aux_metrics["attention_alignment_loss"] = self.aux_alignment
         return self.loss
 
     def all_reduce_gradient(self, single_rank_too: bool = False):
@@ -469,9 +534,10 @@ class FineTuner:
         self.step_count += 1
         return True
 
-    def step(self, instruction_dict, initial_state, images, batch, lr=None, base_lr=None):
+    def step(self, instruction_dict, initial_state, images, batch, lr=None, base_lr=None, reference_attention=None):
+        check_reference_attention(self.attention_map_alignment, reference_attention, self.B, self.g.patches)
         obs = images if self.train_encoder else self.model.encode_images(images)
-        loss = self.forward_backward(instruction_dict, initial_state, obs, batch)
+        loss = self.forward_backward(instruction_dict, initial_state, obs, batch, reference_attention=reference_attention)
         self.apply(lr, base_lr)
         return loss.mean()
 

@@ -381,6 +381,34 @@ int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w);
  * any launch, while a mask is set for the other train_encoder value than hyper->train_encoder (or the position source changed
  * the vector's length since).                                                                                                */
 int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, int32_t frozen_buckets);
+/* Replaces: the two attention terms of `sample_loss_fn` (scripts/train.py:348-373, config.auxiliary_loss.attention_entropy and
+ * .attention_map_alignment), added to every sample's loss after MixActionHead.loss -- so neither the timestep nor the action mask
+ * touches them.  Both read the action token's attention row of the LAST policy layer (transformer.py:248-262 returns that block's
+ * map): p[h][k], the softmax of query S-1 of head h over all S = P + 1 keys (the row is unmasked).  Per sample b:
+ *   ent_b   = 1/H sum_h ( -sum_{k<S} p[h][k] log(p[h][k] + 1e-8) )
+ *   m[k]    = 1/H sum_h p[h][k];   align_b = 1/P sum_{k<P} (m[k] - reference_map[b][k])^2
+ *   loss_b  = mix_loss_b + entropy_weight ent_b + alignment_weight align_b
+ * reference_map is a constant (the reference stops the gradient): DINOv2's last-layer CLS attention over the patches, mean over
+ * heads, of the PRETRAINED encoder (scripts/train.py:432-438).  alignment_weight is the effective weight: the caller applies the
+ * annealing (1 - step / num_steps) on the host.  The gradient of mean_b loss_b flows through the attention row into everything the
+ * step differentiates (with train_encoder != 0 into the shared DINOv2 leaves too, through the policy's keys).
+ * A host-side setting kept on the context, like hvla_train_frozen: nothing is launched, pointers are kept by POINTER and stay the
+ * caller's while set, hvla_train_buffers / hvla_train_hyper keep their layout and hvla_train_sizes its values (no workspace).
+ * While a weight is > 0, hvla_train_step launches one small kernel behind the loss (forward_only too: buf->loss includes the
+ * terms, entropy / alignment receive ent_b / align_b -- alignment only while alignment_weight > 0) and once more inside the last
+ * policy layer's backward; all sums in a fixed order, no atomics.  With both weights 0, or after opts == NULL (the state of a new
+ * context), hvla_train_step launches exactly what it launched.
+ * HVLA_E_SHAPE, before anything is stored (the previous setting stays in force): struct_size != sizeof(hvla_train_attention), a
+ * negative or non-finite weight, alignment_weight > 0 with a NULL reference_map, a use_language_token context.              */
+typedef struct hvla_train_attention {
+  uint32_t struct_size;
+  float entropy_weight;         /* auxiliary_loss.attention_entropy                                   */
+  float alignment_weight;       /* (1 - step/num_steps) * auxiliary_loss.attention_map_alignment      */
+  const float* reference_map;   /* device f32 [B, P]; needed iff alignment_weight > 0                  */
+  float* entropy;               /* device f32 [B] out, or NULL                                        */
+  float* alignment;             /* device f32 [B] out, or NULL                                        */
+} hvla_train_attention;
+int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts);   /* NULL: off */
 
 /* Replaces: InferenceWrapper._resize_image (data/utils/hypervla_interface.py:89-121): optionally
  * tf.image.resize_with_pad(image, 256, 320) (bilinear, zero padding; `padded_resize`), then
