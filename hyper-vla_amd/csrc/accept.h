@@ -1,0 +1,107 @@
+// accept.h -- which geometries hvla_create serves (no HIP types): ONE predicate from (hvla_config, use_language_token) to
+// HVLA_OK / HVLA_E_SHAPE / HVLA_E_DTYPE, and next to it the two dynamic-LDS formulas it refuses by.  The launchers
+// (launch_ctx_encoder in hypernet.hip, launch_policy_nw in policy.hip) size their launches with the same functions, so a geometry
+// the predicate lets through cannot fail its first launch for LDS.  A CPU test walks the predicate over every edge of the contract
+// and checks the launch-side preconditions of everything it accepts (tests/native/accept_check.cpp, built with g++ under ASan /
+// UBSan by tests/test_host_sanitizers.py).
+//
+// What the hand-written kernels are specialised for (anything else is refused, never emulated):
+//   policy     dim == 64, heads == 4, mlp % 32 == 0, mlp >= 32, layers >= 1, 1 <= horizon, 2 <= action_dim,
+//              horizon * action_dim <= 32 (one 32-row head tile), and the per-layer vectors fit the policy kernel's LDS
+//              (policy_lds_bytes <= 160 KiB: at P = 256 layers <= 7 at mlp = 128, mlp <= 768 at layers = 4)
+//   encoder    enc_dim % 128 == 0, 128 <= enc_dim <= 1024, enc_mlp % 128 == 0, enc_mlp >= 128, head width 64,
+//              0 <= enc_layers <= ENC_MAX_LAYERS, image_size % patch == 0, P = (image_size / patch)^2 in {256, 64}
+//   context    ctx_dim in {128, 64, 32}, ctx_dim % ctx_heads == 0 with a head width that is a multiple of 4 (the score loop's
+//              k-steps of the f32 MFMA), ctx_mlp % 16 == 0, 0 <= ctx_layers <= CTX_MAX_LAYERS, 2 <= lang_tokens <= 38,
+//              lang_dim % 4 == 0, and the working set fits the context encoder's LDS (ctx_encoder_lds_bytes <= 160 KiB)
+//   use_language_token   additionally lang_tokens <= 32 (one 32-key tile) and lang_dim % 64 == 0
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/hvla.h"
+#include "layout.h"
+#include "plan.h"
+
+namespace hvla {
+
+constexpr int CTX_MAX_LAYERS = 8;     // CtxParams::layer
+constexpr int ENC_MAX_LAYERS = 24;    // EncWeights::layer
+// Two kernel constants the LDS formulas below depend on.  They are DEFINED here so that the formulas stand in a header without HIP
+// types; what each is for is told where it is used (hypernet.hip, policy.hip).
+constexpr int CTX_THREADS = 1024;     // ctx_encoder_kernel's workgroup: 16 waves
+constexpr int PRING = 4;              // policy_kernel's ring of staged weight tiles, 8 KiB each
+
+// ---- context encoder: floats of its third LDS buffer (q | k | v or the MLP hidden rows; the staged token chunk; the CLS row and
+// the partial sums of its projection), and the dynamic LDS of ctx_encoder_kernel for T task tokens, width C, MLP width F, image width E
+inline size_t ctx_big_elems(int T, int C, int F, int E) {
+  const int S = T + 2;
+  const int ldq = 3 * C + 4, ldf = F + 4;
+  int bigld = ldq > ldf ? ldq : ldf;
+  if (bigld < 132) bigld = 132;
+  size_t big_elems = (size_t)S * bigld;
+  if (big_elems < (size_t)E + CTX_THREADS) big_elems = (size_t)E + CTX_THREADS;
+  return big_elems;
+}
+inline size_t ctx_encoder_lds_bytes(int T, int C, int F, int E) {
+  return ((size_t)2 * (T + 2) * (C + 4) + ctx_big_elems(T, C, F, E) + 64) * sizeof(float);   // x, h, big, the key mask
+}
+
+// ---- generated policy: the dynamic LDS of policy_kernel<NW> (NW = P / 32 waves; policy_body.inc lays it out).  layer_vec_floats =
+// PolicyLayout::Gv - v_layer0, the per-layer vectors + encoder_norm + head bias the kernel copies to LDS once.
+inline size_t policy_lds_bytes(int NW, bool lang, int layer_vec_floats) {
+  const int SP = NW * 32, VLD = SP + 8;
+  const int NP = lang ? 10 : 9, SPX = SP + (lang ? 32 : 0);   // policy_body.inc: partial table, attention-map keys
+  return (size_t)PRING * 8192 + ((size_t)2 * 2 * SP * 16 + (size_t)2 * 32 * VLD) * 2 /* 16-bit K and V^T */ + (size_t)NW * 4096 +
+         (lang ? (size_t)LANG_PAIR_BYTES : 0) + (size_t)layer_vec_floats * sizeof(float) +
+         (size_t)(((384 + 2 * NP * 20 + NW * 32 + 2 * SPX + 96 + NW * 64) * 4 + 1023) & ~1023);
+}
+
+inline Geom geom_of(const hvla_config& c, int lang) {
+  return Geom{c.image_size, c.patch, c.enc_dim, c.enc_layers, c.enc_heads, c.enc_mlp,
+              c.dim, c.layers, c.heads, c.mlp, c.horizon, c.action_dim, c.tanh_scale, c.max_action,
+              c.ctx_dim, c.ctx_layers, c.ctx_heads, c.ctx_mlp, c.lang_tokens, c.lang_dim, c.scale_context,
+              c.clip_target != 0, lang};
+}
+
+// the policy kernel's LDS for an ACCEPTED width set (dim 64, mlp % 32 == 0, small layer count: the offsets are ints)
+inline size_t policy_lds_bytes_of(const hvla_config& c, int lang) {
+  PolicyLayout pl{};
+  LangLayout ll;
+  policy_offsets(geom_of(c, lang), pl, ll);
+  const int grid = c.image_size / c.patch;
+  return policy_lds_bytes(grid * grid / 32, lang != 0, pl.Gv - pl.v_layer0);
+}
+
+// HVLA_OK, or why hvla_create refuses the geometry.  Every divisor is checked before it divides and every product is formed in 64
+// bits: the verdict arrives for ANY field values.  (struct_size and the options' struct_size are the caller's.)
+inline int accept_geometry(const hvla_config& c, int lang) {
+  if (c.enc_dtype != HVLA_ENC_F16 && c.enc_dtype != HVLA_ENC_BF16) return HVLA_E_DTYPE;
+  if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
+  if (c.max_batch < 1 || c.streams < 0 || c.streams > 2) return HVLA_E_SHAPE;
+  // generated policy
+  if (c.dim != 64 || c.heads != 4 || c.mlp < 32 || c.mlp % 32 != 0 || c.layers < 1) return HVLA_E_SHAPE;
+  if (c.horizon < 1 || c.action_dim < 2 || (int64_t)c.horizon * c.action_dim > 32) return HVLA_E_SHAPE;
+  // image encoder
+  if (c.enc_dim < 128 || c.enc_dim > 1024 || c.enc_dim % 128 != 0 || c.enc_mlp < 128 || c.enc_mlp % 128 != 0) return HVLA_E_SHAPE;
+  if (c.enc_heads < 1 || c.enc_dim % c.enc_heads != 0 || c.enc_dim / c.enc_heads != 64) return HVLA_E_SHAPE;
+  if (c.enc_layers < 0 || c.enc_layers > ENC_MAX_LAYERS) return HVLA_E_SHAPE;
+  if (c.patch < 1 || c.image_size < 1 || c.image_size % c.patch != 0) return HVLA_E_SHAPE;
+  const int64_t grid = c.image_size / c.patch, P = grid * grid;
+  if (P != 256 && P != 64) return HVLA_E_SHAPE;     // (32 patches are no square: policy_kernel<1> cannot be reached)
+  // context encoder
+  if (c.ctx_dim != 128 && c.ctx_dim != 64 && c.ctx_dim != 32) return HVLA_E_SHAPE;
+  if (c.ctx_heads < 1 || c.ctx_dim % c.ctx_heads != 0 || (c.ctx_dim / c.ctx_heads) % 4 != 0) return HVLA_E_SHAPE;
+  if (c.ctx_mlp < 16 || c.ctx_mlp % 16 != 0 || c.ctx_layers < 0 || c.ctx_layers > CTX_MAX_LAYERS) return HVLA_E_SHAPE;
+  if (c.lang_tokens < 2 || c.lang_tokens > 38 || c.lang_dim < 4 || c.lang_dim % 4 != 0) return HVLA_E_SHAPE;
+  // use_language_token: the language prefix is one 32-key tile of the policy kernel, its projection runs in k-steps of 64
+  if (lang && (c.lang_tokens > 32 || c.lang_dim % 64 != 0)) return HVLA_E_SHAPE;
+  // the context encoder keeps its token block, q / k / v and the MLP hidden rows in LDS, the policy kernel its per-layer vectors:
+  // a geometry that does not fit is refused here, not at the first hvla_generate / hvla_step
+  if (ctx_encoder_lds_bytes(c.lang_tokens, c.ctx_dim, c.ctx_mlp, c.enc_dim) > LDS_LIMIT) return HVLA_E_SHAPE;
+  if ((int64_t)c.layers * (9 * 64 + (int64_t)c.mlp) * (int64_t)sizeof(float) > (int64_t)LDS_LIMIT) return HVLA_E_SHAPE;   // (keeps the offsets in int)
+  if (policy_lds_bytes_of(c, lang) > LDS_LIMIT) return HVLA_E_SHAPE;
+  return HVLA_OK;
+}
+
+}  // namespace hvla

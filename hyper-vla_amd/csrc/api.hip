@@ -147,27 +147,11 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
   ctx->cfg = *c;
   ctx->device = device;
   Geom& g = ctx->g;
-  g = Geom{c->image_size, c->patch, c->enc_dim, c->enc_layers, c->enc_heads, c->enc_mlp,
-           c->dim, c->layers, c->heads, c->mlp, c->horizon, c->action_dim, c->tanh_scale, c->max_action,
-           c->ctx_dim, c->ctx_layers, c->ctx_heads, c->ctx_mlp, c->lang_tokens, c->lang_dim, c->scale_context,
-           c->clip_target != 0, lang};
-  // what the hand-written kernels are specialised for (anything else is refused, never emulated)
+  // what the hand-written kernels are specialised for (anything else is refused, never emulated): the predicate of accept.h,
+  // which also refuses a context encoder or a policy that does not fit its kernel's LDS here, not at the first hvla_generate / hvla_step
+  if (const int verdict = accept_geometry(*c, lang)) return verdict;
+  g = geom_of(*c, lang);
   const int P = g.P();
-  const bool ok = c->dim == 64 && c->heads == 4 && c->mlp % 32 == 0 && c->mlp >= 32 && c->enc_dim % 128 == 0 &&
-                  c->enc_dim <= 1024 && c->enc_mlp % 128 == 0 && c->enc_dim / c->enc_heads == 64 &&
-                  (P == 256 || P == 64 || P == 32) && c->image_size % c->patch == 0 &&
-                  (c->ctx_dim == 128 || c->ctx_dim == 64 || c->ctx_dim == 32) && c->ctx_dim % c->ctx_heads == 0 &&
-                  c->ctx_mlp % 16 == 0 && c->lang_tokens + 2 <= 40 && c->lang_tokens >= 2 && c->lang_dim % 4 == 0 &&
-                  c->ctx_layers <= CTX_MAX_LAYERS && c->enc_layers <= ENC_MAX_LAYERS && c->layers >= 1 &&
-                  c->horizon * (c->action_dim - 1) + c->horizon <= 32 && c->max_batch >= 1 &&
-                  (c->enc_dtype == HVLA_ENC_F16 || c->enc_dtype == HVLA_ENC_BF16);
-  if (!ok) return c->enc_dtype != HVLA_ENC_F16 && c->enc_dtype != HVLA_ENC_BF16 ? HVLA_E_DTYPE : HVLA_E_SHAPE;
-  // use_language_token: the language prefix is one 32-key tile of the policy kernel, its projection runs in k-steps of 64
-  if (lang && (c->lang_tokens > 32 || c->lang_dim % 64 != 0)) return HVLA_E_SHAPE;
-  if (lang && c->dim / 16 * 512 != 4 * 512) return HVLA_E_SHAPE;    // policy_body.inc finds the prefix at m_head + 4 fragments
-  // the context encoder keeps its token block, q / k / v and the MLP hidden rows in LDS: a geometry that does not fit is
-  // refused here, not at the first hvla_generate
-  if (ctx_encoder_lds_bytes(c->lang_tokens, c->ctx_dim, c->ctx_mlp, c->enc_dim) > 160 * 1024) return HVLA_E_SHAPE;
   if (hipSetDevice(device) != hipSuccess) return HVLA_E_DEVICE;
   ctx->lay = build_layout(g);
   ctx->Kp = serving::patch_kp(g);
@@ -200,8 +184,6 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess)
       return HVLA_E_HIP;
-  } else if (c->streams != 0 && c->streams != 1) {
-    return HVLA_E_SHAPE;
   }
   *out = ctx.release();
   return HVLA_OK;

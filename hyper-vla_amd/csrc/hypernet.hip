@@ -23,7 +23,9 @@ namespace hvla {
 // ------------------------------------------------------------------------------------------------
 // context encoder
 // ------------------------------------------------------------------------------------------------
-constexpr int CTX_THREADS = 1024;   // 16 waves: one workgroup (one episode) per CU, so the waves of that one workgroup have to hide each other's latencies
+// CTX_THREADS = 1024 (defined in accept.h, whose LDS formula depends on it): 16 waves, one workgroup (one episode) per CU, so the
+// waves of that one workgroup have to hide each other's latencies
+static_assert(CTX_THREADS == 1024, "ctx_encoder_kernel is written for 16 waves");
 constexpr int CTX_WAVES = CTX_THREADS / 64;
 constexpr int CTX_RG = 20;   // S <= 2 * CTX_RG = 40 rows: three 16-row MFMA tiles at most
 
@@ -436,28 +438,12 @@ hipError_t debug_ctx_stamps(unsigned long long* out) { return hipMemcpyFromSymbo
 #endif
 
 // ---- launchers -----------------------------------------------------------------------------------
-// LDS the context encoder needs for a geometry (T task tokens, width C, MLP width F, image width E): hvla_create refuses a
-// configuration that does not fit instead of letting the first hvla_generate fail with a bare HIP error
-static size_t ctx_big_elems(int T, int C, int F, int E) {
-  const int S = T + 2;
-  const int ldq = 3 * C + 4, ldf = F + 4;
-  int bigld = ldq > ldf ? ldq : ldf;
-  if (bigld < 132) bigld = 132;
-  size_t big_elems = (size_t)S * bigld;
-  if (big_elems < (size_t)E + CTX_THREADS) big_elems = (size_t)E + CTX_THREADS;
-  return big_elems;
-}
-size_t ctx_encoder_lds_bytes(int T, int C, int F, int E) {
-  return ((size_t)2 * (T + 2) * (C + 4) + ctx_big_elems(T, C, F, E) + 64) * sizeof(float);
-}
-
+// (the LDS the context encoder needs for a geometry: ctx_big_elems / ctx_encoder_lds_bytes of accept.h, by which hvla_create refuses
+// a configuration that does not fit instead of letting the first hvla_generate fail with a bare HIP error)
 hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st) {
-  const int S = p.T + 2;
-  const int ldx = p.C + 4;
-  const size_t big_elems = ctx_big_elems(p.T, p.C, p.F, p.E);
   CtxParams q = p;
-  q.big_elems = (int)big_elems;
-  const size_t smem = ((size_t)2 * S * ldx + big_elems + 64) * sizeof(float);      // + the key mask (= ctx_encoder_lds_bytes)
+  q.big_elems = (int)ctx_big_elems(p.T, p.C, p.F, p.E);
+  const size_t smem = ctx_encoder_lds_bytes(p.T, p.C, p.F, p.E);      // x, h, big and the key mask
   static bool attr_done[64] = {};                              // per device: the attribute belongs to the device's code object
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -468,7 +454,7 @@ hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st) {
     if (e != hipSuccess) return e;
     attr_done[dev] = true;
   }
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
+  if (smem > LDS_LIMIT) return hipErrorInvalidValue;
   hipLaunchKernelGGL(ctx_encoder_kernel, dim3(B), dim3(CTX_THREADS), smem, st, q);
   return hipGetLastError();
 }

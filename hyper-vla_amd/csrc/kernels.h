@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/hvla.h"
+#include "accept.h"
 #include "layout.h"
 
 namespace hvla {
@@ -14,7 +15,6 @@ namespace hvla {
 struct CtxLayer {
   const float *ln0_s, *ln0_b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *ln1_s, *ln1_b, *w1, *b1, *w2, *b2;
 };
-constexpr int CTX_MAX_LAYERS = 8;
 struct CtxParams {
   int T, C, F, heads, layers, lang_dim, E, scale_context;
   int big_elems;             // floats in the kernel's third LDS buffer (set by launch_ctx_encoder)
@@ -35,7 +35,7 @@ struct WeightGenParams {
   int B, Gm, Gv, ntiles;
 };
 hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st);
-size_t ctx_encoder_lds_bytes(int T, int C, int F, int E);       // dynamic LDS of ctx_encoder_kernel for a geometry (<= 160 KiB or refused at create)
+// (ctx_encoder_lds_bytes, the dynamic LDS of ctx_encoder_kernel for a geometry -- <= 160 KiB or refused at create -- is accept.h's)
 hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st);
 // episode pool: weightgen_kernel's output row of input episode r is arena row slot[r] of an arena of `rows`;
 // launch_pool_assign puts the K new context rows (f32 workspace rows 0 .. K-1) at arena rows slot[k] and zeroes those rows'
@@ -53,7 +53,6 @@ struct EncLayerW {
   const float *bqkv, *bo, *b1, *b2;              // f32
   const float *ln1_s, *ln1_b, *ln2_s, *ln2_b, *ls1, *ls2;
 };
-constexpr int ENC_MAX_LAYERS = 24;
 struct EncWeights {
   const void* w_patch;        // 16-bit [E][Kp] (normalisation folded in)
   const float* b_patch;       // [E] (bias - sum W mean/std)

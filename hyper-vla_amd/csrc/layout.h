@@ -141,19 +141,12 @@ struct PackedLayout {
   std::vector<int32_t> perm;   // [Gm + Gv] -> reference flat index or -1
 };
 
-inline PackedLayout build_layout(const Geom& g) {
-  PackedLayout out;
-  PolicyLayout& p = out.pl;
-  const int D = g.D, M = g.M, H = g.H, hd = g.hd(), E = g.E, S = g.S();
+// Every offset of PolicyLayout / LangLayout except G (which needs the leaf list): sizes alone, no allocation, so that the
+// acceptance predicate (accept.h) can ask how many per-layer floats the policy kernel keeps in LDS without building perm.
+inline void policy_offsets(const Geom& g, PolicyLayout& p, LangLayout& ll) {
+  const int D = g.D, M = g.M, H = g.H, E = g.E, S = g.S();
   const int TD = D / 32, TM = M / 32;
-  auto leaves = generated_leaves(g);
-  auto find = [&](const std::string& n) -> const LeafInfo& {
-    for (auto& l : leaves)
-      if (l.flat == n) return l;
-    static LeafInfo none;
-    return none;
-  };
-  p.G = (int)(leaves.back().offset + leaves.back().size);
+  p.G = 0;
   // ---- matrix region offsets
   int m = 0;
   p.m_proj = m;  m += TD * (E / 16) * 512;
@@ -164,7 +157,6 @@ inline PackedLayout build_layout(const Geom& g) {
   p.m_layer_stride = p.m_fc2 + TM * TD * 2 * 512;
   p.m_layer0 = m;  m += g.L * p.m_layer_stride;
   p.m_head = m;  m += (D / 16) * 512;
-  LangLayout& ll = out.ll;
   ll.on = g.lang_in_policy ? 1 : 0;
   if (ll.on) {
     ll.m_lkv = m;  m += g.L * 2 * (LANG_PAIR_BYTES / 4);             // (policy_body.inc derives it as m_head + 4 frags)
@@ -187,6 +179,23 @@ inline PackedLayout build_layout(const Geom& g) {
   p.v_norm_b = v;  v += D;
   p.v_head_b = v;  v += 32;
   p.Gv = (v + 31) / 32 * 32;
+}
+
+inline PackedLayout build_layout(const Geom& g) {
+  PackedLayout out;
+  PolicyLayout& p = out.pl;
+  LangLayout& ll = out.ll;
+  policy_offsets(g, p, ll);
+  const int D = g.D, M = g.M, H = g.H, hd = g.hd(), E = g.E, S = g.S();
+  const int TD = D / 32, TM = M / 32;
+  auto leaves = generated_leaves(g);
+  auto find = [&](const std::string& n) -> const LeafInfo& {
+    for (auto& l : leaves)
+      if (l.flat == n) return l;
+    static LeafInfo none;
+    return none;
+  };
+  p.G = (int)(leaves.back().offset + leaves.back().size);
 
   out.perm.assign((size_t)p.Gm + p.Gv, -1);
   int32_t* pm = out.perm.data();

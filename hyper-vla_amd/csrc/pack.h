@@ -1,6 +1,6 @@
 // pack.h — the element formulas of the serving buffers and the host packing of W_cat and the encoder matrices (no HIP types: the
 // programs of tests/native/ run it under -fsanitize=address,undefined on the CPU).  Every formula exists once: the host packer
-// (serving_layout.h) and publish.hip run this text.  HVLA_HD is `__host__ __device__` under hipcc, empty for a host compiler.
+// (serving_layout.h) and publish.hip run this text.  HVLA_PACK_HD is `__host__ __device__` under hipcc, empty for a host compiler.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -10,28 +10,28 @@
 #include "layout.h"
 
 #if defined(__HIPCC__)
-#define HVLA_HD __host__ __device__
+#define HVLA_PACK_HD __host__ __device__
 #else
-#define HVLA_HD
+#define HVLA_PACK_HD
 #endif
 
 namespace hvla {
 namespace pack {
 
-HVLA_HD inline uint16_t f2bf(float f) {          // round-to-nearest-even, NaN preserved
+HVLA_PACK_HD inline uint16_t f2bf(float f) {          // round-to-nearest-even, NaN preserved
   uint32_t u;
   memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-HVLA_HD inline float bf2f(uint16_t h) {
+HVLA_PACK_HD inline float bf2f(uint16_t h) {
   uint32_t u = (uint32_t)h << 16;
   float f;
   memcpy(&f, &u, 4);
   return f;
 }
 // IEEE binary16, round-to-nearest-even, subnormals kept, overflow to infinity (== the hardware conversion)
-HVLA_HD inline uint16_t f2h(float f) {
+HVLA_PACK_HD inline uint16_t f2h(float f) {
   uint32_t u;
   memcpy(&u, &f, 4);
   const uint32_t sign = (u >> 16) & 0x8000u;
@@ -48,7 +48,7 @@ HVLA_HD inline uint16_t f2h(float f) {
   const uint32_t v = u - 0x38000000u;                                // rebias 127 -> 15
   return (uint16_t)(sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13));
 }
-HVLA_HD inline float h2f(uint16_t h) {
+HVLA_PACK_HD inline float h2f(uint16_t h) {
   const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
   uint32_t u;
   if (e == 0) {
@@ -65,27 +65,27 @@ HVLA_HD inline float h2f(uint16_t h) {
   memcpy(&f, &u, 4);
   return f;
 }
-HVLA_HD inline uint16_t to16(float f, bool bf) { return bf ? f2bf(f) : f2h(f); }
-HVLA_HD inline float from16(uint16_t h, bool bf) { return bf ? bf2f(h) : h2f(h); }
+HVLA_PACK_HD inline uint16_t to16(float f, bool bf) { return bf ? f2bf(f) : f2h(f); }
+HVLA_PACK_HD inline float from16(uint16_t h, bool bf) { return bf ? bf2f(h) : h2f(h); }
 
 // one element of a transposing pack: the 16-bit weight and what the rounding dropped, x 4096 (stays in the normal range of fp16)
-HVLA_HD inline void round_pair(float w, bool bf, uint16_t& w16, uint16_t& d16) {
+HVLA_PACK_HD inline void round_pair(float w, bool bf, uint16_t& w16, uint16_t& d16) {
   w16 = to16(w, bf);
   d16 = to16((w - from16(w16, bf)) * 4096.f, bf);
 }
 // one element of W_cat: hi = bf16(w), lo = bf16(w - hi)
-HVLA_HD inline void split_pair(float w, uint16_t& hi, uint16_t& lo) {
+HVLA_PACK_HD inline void split_pair(float w, uint16_t& hi, uint16_t& lo) {
   hi = f2bf(w);
   lo = f2bf(w - bf2f(hi));
 }
 // fragment lane rho (+ 32 for the upper eight k of a k-step) holds column tau of its 32-column tile, and the inverse
-HVLA_HD inline int tau_of_rho(int rho) { return 16 * ((rho >> 2) & 1) + (rho & 3) + 4 * (rho >> 3); }
-HVLA_HD inline int rho_of_tau(int tau) { return (tau & 3) + 4 * (tau >> 4) + 8 * ((tau >> 2) & 3); }
+HVLA_PACK_HD inline int tau_of_rho(int rho) { return 16 * ((rho >> 2) & 1) + (rho & 3) + 4 * (rho >> 3); }
+HVLA_PACK_HD inline int rho_of_tau(int tau) { return (tau & 3) + 4 * (tau >> 4) + 8 * ((tau >> 2) & 3); }
 
 // output channel nn of the patch embedding: row nn of [E][hi Kp/2 | lo Kp/2] and its bias.  `pk` [Kreal][E].
 // ((p/255 - mean)/std) . w  ==  (p - 128) . w' / 256 + const with w' = 256 w / (255 std): x256 keeps small weights in the 16-bit
 // normal range.  The rescale is done in double and rounded to f32 once; the bias is accumulated in double, ascending k.
-HVLA_HD inline float patch_channel(const float* pk, float pb, int E, int nn, int Kreal, int Kp, bool bf, uint16_t* row) {
+HVLA_PACK_HD inline float patch_channel(const float* pk, float pb, int E, int nn, int Kreal, int Kp, bool bf, uint16_t* row) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif

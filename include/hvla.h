@@ -52,12 +52,16 @@ typedef struct hvla_config {
                                                 returns HVLA_E_SHAPE when it is not this library's (the struct is passed by pointer
                                                 and grows at its end; a binder built against another header is refused, never
                                                 read past its end)                                                      */
-  int32_t image_size, patch;                 /* 224, 14                                         */
+  int32_t image_size, patch;                 /* 224, 14.  (image_size / patch)^2 must be 256 or 64 patches (the whole list of what
+                                                hvla_create serves: csrc/accept.h; anything else is HVLA_E_SHAPE)               */
   int32_t enc_dim, enc_layers, enc_heads, enc_mlp; /* DINOv2-base: 768, 12, 12, 3072            */
-  int32_t dim, layers, heads, mlp;           /* generated vit_t: 64, 4, 4, 128                  */
-  int32_t horizon, action_dim;               /* 4, 7                                            */
+  int32_t dim, layers, heads, mlp;           /* generated vit_t: 64, 4, 4, 128.  dim == 64, heads == 4, mlp % 32 == 0, layers >= 1, and
+                                                the per-layer vectors -- layers x (576 + mlp) + 160 floats -- must fit the policy kernel's
+                                                LDS (at 256 patches 5632 floats, 3584 with use_language_token): HVLA_E_SHAPE otherwise  */
+  int32_t horizon, action_dim;               /* 4, 7.  horizon >= 1, action_dim >= 2, horizon * action_dim <= 32                */
   float tanh_scale, max_action;              /* 5, 5 (action_heads.py:469-470)                  */
-  int32_t ctx_dim, ctx_layers, ctx_heads, ctx_mlp; /* hypernet: 128, 6, 4, 512.  ctx_mlp % 16 == 0 (the f32 MFMA's column
+  int32_t ctx_dim, ctx_layers, ctx_heads, ctx_mlp; /* hypernet: 128, 6, 4, 512.  ctx_dim 128, 64 or 32; ctx_dim / ctx_heads a multiple
+                                                of 4 (the score loop's k-steps); ctx_mlp % 16 == 0 (the f32 MFMA's column
                                                 tiles), and the context encoder's LDS working set -- (lang_tokens + 2) rows of
                                                 max(3 ctx_dim, ctx_mlp) + 2 ctx_dim floats -- must fit 160 KiB: hvla_create
                                                 returns HVLA_E_SHAPE otherwise                                          */

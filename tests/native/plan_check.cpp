@@ -209,6 +209,19 @@ int main(int argc, char** argv) {
     REQUIRE(p.main.kernel == G256LNNT_RES_P && p.lnx_G == 10 && p.lnx_rows_aligned == 120 && p.lnx_rounds_div == 4 && p.lnx_rows_xcd == 128 && p.lnx_rcp == 21846, "B = 1024: lnx numbers");
     REQUIRE(p.lnx_rows_aligned + (256 / 8 - p.lnx_G * 3) * p.lnx_rounds_div == p.lnx_rows_xcd, "B = 1024: the groups' and the left-over workgroups' images add up");
   }
+  // tests/test_gpu_geometry_contract.py runs the persistent fused LayerNorm once per column-tile count: on 256 CUs these three
+  // (width, batch) pairs take it in the patch embedding and in both residual GEMMs, and the same widths at B = 9 do not
+  for (const Geo& g : {Geo{"e1024", 224, 14, 1024, 2048, 16}, Geo{"e512", 224, 14, 512, 1024, 8}, Geo{"e256", 224, 14, 256, 512, 4}}) {
+    const int nbn = g.E / 256, B = 256 / nbn;
+    const EncSizes z = sizes(g, B, 1), nine = sizes(g, 9, 1);
+    const GemmPlan pe = plan_gemm(z, EPI_PATCH, g.E, plan_call(z).Kp, 0, true, false), out = plan_gemm(z, EPI_RES, g.E, g.E, 4, true, false),
+                   fc2 = plan_gemm(z, EPI_RES, g.E, g.F, 6, true, false);
+    REQUIRE(pe.main.kernel == G256LN_PATCH_P && out.main.kernel == G256LN_RES_P && fc2.main.kernel == G256LN_RES_P, "E = %d, B = %d: persistent fused LayerNorm", g.E, B);
+    for (const GemmPlan* p : {&pe, &out, &fc2})
+      REQUIRE(p->ln_fused && p->nbn == nbn && p->nbm == B && (int)p->main.grid == 256 && lnx_covers(*p, 256), "E = %d, B = %d: %d column tiles of an image in one round", g.E, B, nbn);
+    REQUIRE(plan_gemm(nine, EPI_PATCH, g.E, plan_call(nine).Kp, 0, true, false).main.kernel == G256LN_PATCH &&
+            plan_gemm(nine, EPI_RES, g.E, g.E, 4, true, false).main.kernel == G256LN_RES, "E = %d, B = 9: one workgroup per tile", g.E);
+  }
   REQUIRE(plan_gemm(sizes(README, 2720, 12), EPI_GELU, Fm, E, 5, false, false).main.kernel == G256NT_GELU, "B = 2720: fc1 stores non-temporally");
   REQUIRE(plan_gemm(sizes(README, 2721, 12), EPI_GELU, Fm, E, 5, false, false).main.kernel == G256_GELU, "B = 2721: fc1's output is 4 GiB, the plain form");
   {

@@ -144,13 +144,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=8)
     ap.add_argument("--style", default="synthetic")
-    ap.add_argument("--geometry", default="full")
+    ap.add_argument("--geometry", default="full", choices=["full", "mid", "e1024"])   # e1024: tests/test_gpu_geometry_contract.py's widest encoder, one layer
+    ap.add_argument("--kind", default="f16", choices=["f16", "bf16"])                    # operand type of study "bias"
     ap.add_argument("--threads", type=int, default=8)
     ap.add_argument("--study", default="sites", choices=["sites", "weights", "bias", "foldln", "hilo"])
     ap.add_argument("--images", default="noise", choices=["noise", "structured"])
     a = ap.parse_args()
     torch.set_num_threads(a.threads)
     g = FULL if a.geometry == "full" else MID
+    if a.geometry == "e1024":
+        import dataclasses
+        g = dataclasses.replace(FULL, enc_dim=1024, enc_heads=16, enc_mlp=1152, enc_layers=1, layers=1, ctx_layers=1)
     B = a.episodes
     hp = syn.synthetic_params(g) if a.style == "synthetic" else syn.synthetic_params_trained_like(g)
     leaves, enc_shapes = generated_leaves(g), dict(encoder_leaves(g))
@@ -173,13 +177,13 @@ def main():
     if a.study == "bias":
         cal = syn.synthetic_images(8, g, rank=77) if a.images == "noise" else syn.synthetic_images_structured(8, g, rank=77)
         means = {}
-        encoder(hp, g, enc_shapes, cal[:, 0], allsites, "f16", collect=means)     # calibration run on OTHER images
-        for name, corr in (("f16, no compensation", None), ("f16 + static bias corr", means), ("f16 + per-image corr", "dynamic")):
-            tok, _ = encoder(hp, g, enc_shapes, im[:, 0], allsites, "f16", corr=corr)
+        encoder(hp, g, enc_shapes, cal[:, 0], allsites, a.kind, collect=means)     # calibration run on OTHER images
+        for name, corr in ((a.kind + ", no compensation", None), (a.kind + " + static bias corr", means), (a.kind + " + per-image corr", "dynamic")):
+            tok, _ = encoder(hp, g, enc_shapes, im[:, 0], allsites, a.kind, corr=corr)
             act, logit, _ = onp.policy(bp, g, tok.numpy())
             d = np.abs(act[..., :6] - act0[..., :6])
             dt = (tok - tok0).numpy()
-            print(f"{name:24s} action MAE {d.mean():.2e} max {d.max():.2e} p99 {np.quantile(d, 0.99):.2e} | logit max {np.abs(logit - logit0).max():.2e} | "
+            print(f"{name:24s} action MAE {d.mean():.2e} max {d.max():.2e} p99 {np.quantile(d, 0.99):.2e} | logit mean {np.abs(logit - logit0).mean():.2e} max {np.abs(logit - logit0).max():.2e} | "
                   f"token rms {np.sqrt((dt * dt).mean()):.2e} max {np.abs(dt).max():.2e}", flush=True)
         return
     if a.study == "hilo":

@@ -41,7 +41,8 @@ def test_launch_plan_arithmetic_under_asan_ubsan(tmp_path):
     (a 64-column slice of W / dW on at most two XCDs at the B = 256 launch shapes), and the non-temporal 16-bit epilogue, whose
     stores carry 32-bit BYTE offsets, is only chosen for outputs below 4 GiB (fc1 from B = 2721 on would wrap).  The
     launch plan of an encoder call: the launch counts the committed profiles record, the boundaries between its forms, and, launch
-    for launch over a sweep of geometries, batches and CU counts, the trace recorded from the dispatch it replaced."""
+    for launch over a sweep of geometries, batches and CU counts, the trace recorded from the dispatch it replaced.  The three (width,
+    batch) pairs at which tests/test_gpu_geometry_contract.py runs the persistent fused LayerNorm take those kernels on 256 CUs."""
     exe = tmp_path / "plan_check"
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
@@ -49,5 +50,24 @@ def test_launch_plan_arithmetic_under_asan_ubsan(tmp_path):
          "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
     run = subprocess.run([str(exe), os.path.join(ROOT, "tests", "native", "encoder_plan_trace.txt")], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
+    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_accepted_geometries_under_asan_ubsan(tmp_path):
+    """csrc/accept.h, the predicate hvla_create refuses a geometry by: over a grid of configs -- every pair of fields through its lower
+    and upper edges, one step outside each, zero, negative and INT_MAX, from four accepted bases -- the verdict arrives without a
+    division by zero or an overflow (a zero heads / patch is HVLA_E_SHAPE), and everything accepted meets the launch-side
+    preconditions, computed by the functions the launchers call: context and policy LDS <= 160 KiB (both language forms), context
+    head width % 4 == 0, P in {64, 256}, an encoder plan at B = 1.  The largest policy the LDS admits at P = 256 is pinned
+    (tests/test_gpu_geometry_contract.py runs it and asserts one step further is refused)."""
+    exe = tmp_path / "accept_check"
+    build = subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+         "-Werror", "-I", os.path.join(ROOT, "hyper-vla_amd", "csrc"), os.path.join(ROOT, "tests", "native", "accept_check.cpp"),
+         "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
