@@ -25,8 +25,7 @@
 
 namespace hvla {
 
-constexpr int CTX_MAX_LAYERS = 8;     // CtxParams::layer
-constexpr int ENC_MAX_LAYERS = 24;    // EncWeights::layer
+// (CTX_MAX_LAYERS, ENC_MAX_LAYERS: layout.h)
 // Two kernel constants the LDS formulas below depend on.  They are DEFINED here so that the formulas stand in a header without HIP
 // types; what each is for is told where it is used (hypernet.hip, policy.hip).
 constexpr int CTX_THREADS = 1024;     // ctx_encoder_kernel's workgroup: 16 waves

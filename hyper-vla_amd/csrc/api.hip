@@ -53,13 +53,24 @@ struct hvla_post {               // per-slot post-processing state (hvla_post_*,
   DevBuf state;                  // PostSlot [B]
 };
 
+struct TrainState {               // what the hvla_train_* entries keep per context
+  TrainLayout L{};                // the layout of the context's geometry, built by the first entry that train_refusal lets through
+  bool have_layout = false;
+  bool timer = false;             // this context switched its device's GEMM timer on (hvla_train_profile): hvla_destroy gives the events back
+  TrainOptions sel;               // what the setters selected, all the caller's device memory: hvla_train_position_source (ps.n == 0: the baked
+                                  // table is the parameter), hvla_train_frozen (mask and wholly frozen buckets), hvla_train_attention_losses
+  int64_t frozen_n = 0;           // the mask's length, one of the two of hvla_train_sizes when it was set ...
+  bool frozen_enc = false;        //   ... namely the one of this train_encoder value
+  hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
+  bool bucket_recorded[3] = {false, false, false};
+};
+
 struct hvla_ctx {
   hvla_config cfg{};
   Geom g{};
   int device = 0;
   std::string err;
   bool loaded = false;
-  bool train_timer = false;      // this context switched its device's GEMM timer on (hvla_train_profile): hvla_destroy gives the events back
   PackedLayout lay;
   int Kp = 0;
   // device weights
@@ -84,18 +95,10 @@ struct hvla_ctx {
   std::vector<hvla_weights*> arena_pool;
   std::mutex pool_mu;                        // hvla_weights_free can arrive from another thread (Python's GC) than hvla_generate
   static constexpr size_t ARENA_POOL_MAX = 4;
-  int pos_n = 0;                 // hvla_train_position_source: side of the position table's source grid (0: the baked table is the parameter)
-  const float* pos_w = nullptr;  //   its [n, grid] resize weights (device, the caller's)
-  const uint8_t* frozen = nullptr;   // hvla_train_frozen: device mask [frozen_n] of create_optimizer's frozen_keys (the caller's), or off
-  int64_t frozen_n = 0;              //   its length, one of the two of hvla_train_sizes when it was set ...
-  bool frozen_enc = false;           //   ... namely the one of this train_encoder value
-  int frozen_buckets = 0;            //   gradient buckets the caller declared wholly frozen (bits 0..2)
-  AttnAux aux;                       // hvla_train_attention_losses: weights, the reference map and the metric outputs (the caller's), or off
-  hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
-  bool bucket_recorded[3] = {false, false, false};
+  TrainState train;
   ~hvla_ctx() {
     for (hvla_weights* w : arena_pool) delete w;
-    for (hipEvent_t e : ev_bucket)
+    for (hipEvent_t e : train.ev_bucket)
       if (e) (void)hipEventDestroy(e);
     if (ev_fork) (void)hipEventDestroy(ev_fork);
     if (ev_join) (void)hipEventDestroy(ev_join);
@@ -192,7 +195,7 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
 void hvla_destroy(hvla_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  if (ctx->train_timer) train_gemm_timer_release();
+  if (ctx->train.timer) train_gemm_timer_release();
   delete ctx;
 }
 
@@ -246,7 +249,7 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   HN(cp, at, w_tok); HN(cp, at, b_tok); HN(cp, at, w_img); HN(cp, at, b_img); HN(cp, at, pos_tok); HN(cp, at, pos_img);
   HN(cp, at, pos_layer); HN(cp, at, norm_s); HN(cp, at, norm_b);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    const TrainLayout::CL& o = at.layer[l];
+    const BlockLeaves& o = at.layer[l];
     CtxLayer& c = cp.layer[l];
     HN(c, o, ln0_s); HN(c, o, ln0_b); HN(c, o, wq); HN(c, o, bq); HN(c, o, wk); HN(c, o, bk); HN(c, o, wv); HN(c, o, bv);
     HN(c, o, wo); HN(c, o, bo); HN(c, o, ln1_s); HN(c, o, ln1_b); HN(c, o, w1); HN(c, o, b1); HN(c, o, w2); HN(c, o, b2);
@@ -257,12 +260,12 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   EncWeights& w = ctx->encw;
   w.w_patch = e16 + at.e_pk; w.b_patch = df + at.e_pb; w.pos = df + at.e_pos; w.lnf_s = df + at.e_lns; w.lnf_b = df + at.e_lnb;
   for (int i = 0; i < g.enc_layers; ++i) {
-    const TrainLayout::EL& o = at.enc[i];
+    const BlockLeaves& o = at.enc[i];
     EncLayerW& L = w.layer[i];
-    L.wqkv = e16 + o.qk; L.wo = e16 + o.ok; L.w1 = e16 + o.f1k; L.w2 = e16 + o.f2k;
-    L.dqkv = dd + o.qk; L.dwo = dd + o.ok; L.dw1 = dd + o.f1k; L.dw2 = dd + o.f2k;
-    L.bqkv = df + o.qb; L.bo = df + o.ob; L.b1 = df + o.f1b; L.b2 = df + o.f2b;
-    L.ln1_s = df + o.n1s; L.ln1_b = df + o.n1b; L.ln2_s = df + o.n2s; L.ln2_b = df + o.n2b; L.ls1 = df + o.ls1; L.ls2 = df + o.ls2;
+    L.wqkv = e16 + o.wq; L.wo = e16 + o.wo; L.w1 = e16 + o.w1; L.w2 = e16 + o.w2;
+    L.dqkv = dd + o.wq; L.dwo = dd + o.wo; L.dw1 = dd + o.w1; L.dw2 = dd + o.w2;
+    L.bqkv = df + o.bq; L.bo = df + o.bo; L.b1 = df + o.b1; L.b2 = df + o.b2;
+    L.ln1_s = df + o.ln0_s; L.ln1_b = df + o.ln0_b; L.ln2_s = df + o.ln1_s; L.ln2_b = df + o.ln1_b; L.ls1 = df + o.ls1; L.ls2 = df + o.ls2;
   }
   HIPCHK(ctx, hipDeviceSynchronize());
   ctx->loaded = true;
@@ -690,24 +693,45 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* logits, const fl
   return HVLA_OK;
 }
 
-static PosSource pos_source(const hvla_ctx* ctx, bool train_encoder);
+// the selection as an entry with this train_encoder value sees it: the position source is off unless the encoder is trained
+static TrainOptions train_options(const hvla_ctx* ctx, bool train_encoder) {
+  TrainOptions o = ctx->train.sel;
+  if (!train_encoder) o.ps = PosSource();
+  return o;
+}
 
-int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[4]) {
-  if (!ctx || !out) return HVLA_E_STATE;
-  if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
-  const TrainLayout L = make_train_layout(ctx->g);
-  out[0] = L.total + (train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0); out[1] = L.G;
-  out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0); out[3] = L.total;
+// the mask set by hvla_train_frozen must be the one of this call's train_encoder value and of the vector's present length (the
+// position source may have changed since): checked before anything is launched, so that no kernel indexes it past its end
+static int frozen_fits(hvla_ctx* ctx, bool train_encoder) {
+  const TrainState& t = ctx->train;
+  if (!t.sel.frozen) return HVLA_OK;
+  const int64_t n = train_vector_elems(t.L, t.sel.ps, train_encoder);
+  if (t.frozen_enc != train_encoder || t.frozen_n != n)
+    FAIL(ctx, HVLA_E_STATE, "the frozen mask was set for train_encoder = %d and %lld elements, this call has train_encoder = %d and %lld: "
+         "call hvla_train_frozen first", (int)t.frozen_enc, (long long)t.frozen_n, (int)train_encoder, (long long)n);
   return HVLA_OK;
 }
 
-// the position-table source as the training entries see it: off unless the encoder is trained
-static PosSource pos_source(const hvla_ctx* ctx, bool train_encoder) {
-  PosSource ps;
-  if (train_encoder && ctx->pos_n > 0) { ps.n = ctx->pos_n; ps.w = ctx->pos_w; ps.grid = ctx->g.image_size / ctx->g.patch; ps.E = ctx->g.E; }
-  return ps;
+// The head of every hvla_train_* entry, before it looks at its other arguments: the null checks (`args`: the entry's other
+// must-not-be-null pointers), whether the training path serves the geometry at all, the device, the layout (built once per
+// context) and, for the entries that read the frozen mask (frozen_for = their train_encoder value, else -1), that the mask fits.
+static int train_entry(hvla_ctx* ctx, bool args = true, int frozen_for = -1) {
+  if (!ctx || !args) return HVLA_E_STATE;
+  if (const char* why = train_refusal(ctx->g)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  TrainState& t = ctx->train;
+  if (!t.have_layout) { t.L = make_train_layout(ctx->g); t.have_layout = true; }
+  if (!t.L.policy_ok) FAIL(ctx, HVLA_E_STATE, "the generated policy has no leaf of a name the training path reads");
+  return frozen_for < 0 ? HVLA_OK : frozen_fits(ctx, frozen_for != 0);
+}
+
+int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[4]) {
+  if (int rc = train_entry(ctx, out != nullptr)) return rc;
+  if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
+  const TrainLayout& L = ctx->train.L;
+  out[0] = train_vector_elems(L, ctx->train.sel.ps, train_encoder != 0); out[1] = L.G;
+  out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0); out[3] = L.total;
+  return HVLA_OK;
 }
 
 static int position_args(hvla_ctx* ctx, const void* a, int32_t n, const void* w, const void* b) {
@@ -737,55 +761,43 @@ int hvla_position_interp_adjoint(hvla_ctx* ctx, const float* ddst, int32_t n, co
 
 int hvla_train_position_source(hvla_ctx* ctx, int32_t n, const float* w) {
   if (!ctx) return HVLA_E_STATE;
-  if (n == 0) { ctx->pos_n = 0; ctx->pos_w = nullptr; return HVLA_OK; }
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
+  if (n == 0) { ctx->train.sel.ps = PosSource(); return HVLA_OK; }
+  if (int rc = train_entry(ctx)) return rc;
   if (!w) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   if (n < 2 || n > 1024) FAIL(ctx, HVLA_E_SHAPE, "source grid %d outside [2, 1024]", n);
-  const TrainLayout L = make_train_layout(ctx->g);
+  const TrainLayout& L = ctx->train.L;
   // the kernels move 16 bytes at a time: the slot and the tail must start on a multiple of 4 elements of the flat vector
   if ((L.total + L.e_pos) % 4 != 0 || (L.total + L.enc_total) % 4 != 0 || ctx->g.E % 4 != 0)
     FAIL(ctx, HVLA_E_SHAPE, "the position table is not 16-byte aligned in this geometry's training vector");
-  ctx->pos_n = n;
-  ctx->pos_w = w;
+  ctx->train.sel.ps = PosSource{n, w, ctx->g.image_size / ctx->g.patch, ctx->g.E};
   return HVLA_OK;
 }
 
 int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, int32_t frozen_buckets) {
   if (!ctx) return HVLA_E_STATE;
-  if (!frozen) { ctx->frozen = nullptr; ctx->frozen_n = 0; ctx->frozen_enc = false; ctx->frozen_buckets = 0; return HVLA_OK; }
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  const TrainLayout L = make_train_layout(ctx->g);
-  const int64_t n_hyper = L.total, n_enc = L.total + L.enc_total + pos_source(ctx, true).tail();
+  TrainState& t = ctx->train;
+  if (!frozen) { t.sel.frozen = nullptr; t.sel.frozen_buckets = 0; t.frozen_n = 0; t.frozen_enc = false; return HVLA_OK; }
+  if (int rc = train_entry(ctx)) return rc;
+  const int64_t n_hyper = t.L.total, n_enc = train_vector_elems(t.L, t.sel.ps, true);
   if (n_params != n_hyper && n_params != n_enc)
     FAIL(ctx, HVLA_E_SHAPE, "frozen mask of %lld elements: the training vector has %lld (frozen encoder) or %lld (trained encoder)",
          (long long)n_params, (long long)n_hyper, (long long)n_enc);
   const bool enc = n_params == n_enc;
   if (frozen_buckets & ~7) FAIL(ctx, HVLA_E_SHAPE, "frozen_buckets 0x%x: buckets are 0, 1, 2", (unsigned)frozen_buckets);
   if (enc && (frozen_buckets & 1)) FAIL(ctx, HVLA_E_SHAPE, "the whole image encoder frozen is train_encoder == 0");
-  ctx->frozen = frozen; ctx->frozen_n = n_params; ctx->frozen_enc = enc; ctx->frozen_buckets = frozen_buckets;
+  t.sel.frozen = frozen; t.sel.frozen_buckets = frozen_buckets; t.frozen_n = n_params; t.frozen_enc = enc;
   return HVLA_OK;
 }
 
 int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts) {
   if (!ctx) return HVLA_E_STATE;
-  if (!opts) { ctx->aux = AttnAux(); return HVLA_OK; }
+  if (!opts) { ctx->train.sel.aux = AttnAux(); return HVLA_OK; }
+  if (int rc = train_entry(ctx)) return rc;
   if (opts->struct_size != sizeof(hvla_train_attention)) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_attention.struct_size %u: this library's is %zu", opts->struct_size, sizeof(hvla_train_attention));
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
   const float we = opts->entropy_weight, wa = opts->alignment_weight;
   if (!std::isfinite(we) || !std::isfinite(wa) || we < 0.f || wa < 0.f) FAIL(ctx, HVLA_E_SHAPE, "attention loss weights (%g, %g) must be finite and >= 0", (double)we, (double)wa);
   if (wa > 0.f && !opts->reference_map) FAIL(ctx, HVLA_E_SHAPE, "alignment_weight %g > 0 needs reference_map [B, P]", (double)wa);
-  ctx->aux.w_ent = we; ctx->aux.w_align = wa; ctx->aux.ref = opts->reference_map; ctx->aux.ent = opts->entropy; ctx->aux.align = opts->alignment;
-  return HVLA_OK;
-}
-
-// the mask set by hvla_train_frozen must be the one of this call's train_encoder value and of the vector's present length (the
-// position source may have changed since): checked before anything is launched, so that no kernel indexes it past its end
-static int frozen_fits(hvla_ctx* ctx, const TrainLayout& L, bool train_encoder) {
-  if (!ctx->frozen) return HVLA_OK;
-  const int64_t n = L.total + (train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0);
-  if (ctx->frozen_enc != train_encoder || ctx->frozen_n != n)
-    FAIL(ctx, HVLA_E_STATE, "the frozen mask was set for train_encoder = %d and %lld elements, this call has train_encoder = %d and %lld: "
-         "call hvla_train_frozen first", (int)ctx->frozen_enc, (long long)ctx->frozen_n, (int)train_encoder, (long long)n);
+  ctx->train.sel.aux = AttnAux{we, wa, opts->reference_map, opts->entropy, opts->alignment};
   return HVLA_OK;
 }
 
@@ -801,39 +813,34 @@ static TrainHyper to_hp(const hvla_train_hyper* hy) {
 int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* tok, const int64_t* mask, const float* cls,
                     const float* tokens, const uint8_t* images, const float* target, const uint8_t* tmask,
                     const uint8_t* amask, int32_t B, const hvla_train_hyper* hy, void* stream) {
-  if (!ctx || !buf || !hy) return HVLA_E_STATE;
+  if (int rc = train_entry(ctx, buf && hy, images != nullptr)) return rc;
   if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
   if (!buf->params || !buf->grads || !buf->theta || !buf->dtheta || !buf->work || !buf->loss || !tok || !mask || !cls ||
       !target || !tmask || !amask)
     FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   if ((tokens != nullptr) == (images != nullptr)) FAIL(ctx, HVLA_E_SHAPE, "pass exactly one of tokens (frozen encoder) / images (trained encoder)");
   if ((images != nullptr) != (hy->train_encoder != 0)) FAIL(ctx, HVLA_E_STATE, "hyper.train_encoder does not match the inputs");
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const TrainLayout L = make_train_layout(ctx->g);
-  if (int rc = frozen_fits(ctx, L, images != nullptr)) return rc;
+  TrainState& t = ctx->train;
   TrainInputs in{tok, mask, cls, tokens, images, target, tmask, amask};
   const TrainHyper hp = to_hp(hy);
-  for (hipEvent_t& e : ctx->ev_bucket)
+  for (hipEvent_t& e : t.ev_bucket)
     if (!e) HIPCHK(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIPCHK(ctx, train_step(ctx->g, L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : ctx->ev_bucket,
-                         pos_source(ctx, images != nullptr), ctx->frozen ? ctx->frozen_buckets : 0, ctx->aux));
+  HIPCHK(ctx, train_step(ctx->g, t.L, to_tb(buf), in, B, hp, reinterpret_cast<hipStream_t>(stream), hp.forward_only ? nullptr : t.ev_bucket,
+                         train_options(ctx, images != nullptr)));
   // ONE pending backward per ctx: the bucket events belong to the last hvla_train_step that ran a backward pass, and
   // hvla_train_wait_bucket refers to that step.  A forward-only step (evaluation between a step and its apply) records
   // nothing and leaves the pending step's events alone.
   if (!hp.forward_only) {
-    ctx->bucket_recorded[0] = images != nullptr;
-    ctx->bucket_recorded[1] = ctx->bucket_recorded[2] = true;
+    t.bucket_recorded[0] = images != nullptr;
+    t.bucket_recorded[1] = t.bucket_recorded[2] = true;
   }
   return HVLA_OK;
 }
 
 int hvla_train_bucket_ranges(hvla_ctx* ctx, int32_t train_encoder, int64_t out[6]) {
-  if (!ctx || !out) return HVLA_E_STATE;
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  const TrainLayout L = make_train_layout(ctx->g);
-  out[0] = L.total; out[1] = train_encoder ? L.enc_total + pos_source(ctx, true).tail() : 0;     // the shared DINOv2 leaves (+ the position source)
+  if (int rc = train_entry(ctx, out != nullptr)) return rc;
+  const TrainLayout& L = ctx->train.L;
+  out[0] = L.total; out[1] = train_vector_elems(L, ctx->train.sel.ps, train_encoder != 0) - L.total;     // the shared DINOv2 leaves (+ the position source)
   out[2] = L.wcat; out[3] = L.total - L.wcat;                     // the output heads (W_cat, b_cat)
   out[4] = 0; out[5] = L.wcat;                                    // the context encoder
   return HVLA_OK;
@@ -842,18 +849,18 @@ int hvla_train_bucket_ranges(hvla_ctx* ctx, int32_t train_encoder, int64_t out[6
 int hvla_train_wait_bucket(hvla_ctx* ctx, int32_t bucket, void* stream) {
   if (!ctx) return HVLA_E_STATE;
   if (bucket < 0 || bucket > 2) FAIL(ctx, HVLA_E_SHAPE, "bucket %d outside [0, 2]", bucket);
-  if (!ctx->bucket_recorded[bucket]) FAIL(ctx, HVLA_E_STATE, "bucket %d was not produced by the last hvla_train_step", bucket);
+  if (!ctx->train.bucket_recorded[bucket]) FAIL(ctx, HVLA_E_STATE, "bucket %d was not produced by the last hvla_train_step", bucket);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  HIPCHK(ctx, hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), ctx->ev_bucket[bucket], 0));
+  HIPCHK(ctx, hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), ctx->train.ev_bucket[bucket], 0));
   return HVLA_OK;
 }
 
 int hvla_train_profile(hvla_ctx* ctx, int32_t on) {
   if (!ctx) return HVLA_E_STATE;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const bool first = on && !ctx->train_timer;
+  const bool first = on && !ctx->train.timer;
   train_gemm_timer(on != 0, first);
-  if (on) ctx->train_timer = true;
+  if (on) ctx->train.timer = true;
   return HVLA_OK;
 }
 
@@ -867,47 +874,36 @@ int hvla_train_profile_read(hvla_ctx* ctx, float* gemm_ms, double* gemm_flops, i
 }
 
 int hvla_train_apply(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_train_hyper* hy, void* stream) {
-  if (!ctx || !buf || !hy) return HVLA_E_STATE;
+  if (int rc = train_entry(ctx, buf && hy, hy && hy->train_encoder != 0)) return rc;
   if (!buf->params || !buf->grads || !buf->mu || !buf->nu || !buf->sqsum) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  const TrainLayout L = make_train_layout(ctx->g);
-  if (int rc = frozen_fits(ctx, L, hy->train_encoder != 0)) return rc;
-  HIPCHK(ctx, train_apply(L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
-                          pos_source(ctx, hy->train_encoder != 0), ctx->frozen));
+  HIPCHK(ctx, train_apply(ctx->train.L, to_tb(buf), to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
+                          train_options(ctx, hy->train_encoder != 0)));
   return HVLA_OK;
 }
 
 int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* acc, float inv_k, const hvla_train_hyper* hy,
                           void* stream) {
-  if (!ctx || !buf || !hy) return HVLA_E_STATE;
+  if (int rc = train_entry(ctx, buf && hy, hy && hy->train_encoder != 0)) return rc;
   if (!buf->grads || !buf->sqsum || !acc) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  const TrainLayout L = make_train_layout(ctx->g);
-  if (int rc = frozen_fits(ctx, L, hy->train_encoder != 0)) return rc;
-  HIPCHK(ctx, train_accumulate(L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
-                               pos_source(ctx, hy->train_encoder != 0), ctx->frozen));
+  HIPCHK(ctx, train_accumulate(ctx->train.L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
+                               train_options(ctx, hy->train_encoder != 0)));
   return HVLA_OK;
 }
 
 int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int32_t train_encoder, void* stream) {
-  if (!ctx) return HVLA_E_STATE;
+  if (int rc = train_entry(ctx)) return rc;
   if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "hvla_train_publish before hvla_load_weights");
-  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the training path does not build use_language_token");
-  if (ctx->g.ctx_layers > 8 || ctx->g.L > 16 || ctx->g.enc_layers > 24) FAIL(ctx, HVLA_E_SHAPE, "too many layers for the training path");
   if (!params) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   const Geom& g = ctx->g;
-  const TrainLayout L = make_train_layout(g);
-  const PosSource ps = pos_source(ctx, train_encoder != 0);
-  const int64_t want = L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
+  const TrainLayout& L = ctx->train.L;
+  const PosSource ps = train_options(ctx, train_encoder != 0).ps;
+  const int64_t want = train_vector_elems(L, ps, train_encoder != 0);
   if (n_params != want) FAIL(ctx, HVLA_E_SHAPE, "n_params %lld, the training vector has %lld", (long long)n_params, (long long)want);
   if (ps.n > 0 && (serving::enc_map(g, L).f_pos % 4 != 0 || (uintptr_t)params % 16 != 0))
     FAIL(ctx, HVLA_E_SHAPE, "the position table is not 16-byte aligned");
   // (the transposing kernel's whole 64 x 64 tiles: hvla_create admits encoder widths in multiples of 128 only)
   const PolicyLayout& pl = ctx->lay.pl;
   const int Gtot = pl.Gm + pl.Gv;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   PublishArgs a{g, params, ctx->hn_f32.as<float>(), ctx->perm.as<int32_t>(), ctx->wcat_hi.as<uint16_t>(), ctx->wcat_lo.as<uint16_t>(),
                 ctx->bcat.as<float>(), Gtot, ctx->enc16.as<uint16_t>(), ctx->encd16.as<uint16_t>(), ctx->encf32.as<float>(),
                 ctx->cfg.enc_dtype == HVLA_ENC_BF16, train_encoder != 0};

@@ -23,6 +23,12 @@
 
 namespace hvla {
 
+// layer counts the fixed-size tables are built for: hvla_create refuses more context / image-encoder layers (accept.h), the
+// training path more policy layers as well (train_layout.h)
+constexpr int CTX_MAX_LAYERS = 8;               // CtxParams::layer, TrainLayout::layer
+constexpr int ENC_MAX_LAYERS = 24;              // EncWeights::layer, TrainLayout::enc
+constexpr int TRAIN_MAX_POLICY_LAYERS = 16;     // TrainLayout::pol
+
 struct Geom {
   int image_size, patch, E, enc_layers, enc_heads, enc_mlp;
   int D, L, H, M, horizon, action_dim;

@@ -76,8 +76,8 @@ inline Extent served_ctx(const Geom& g, const TrainLayout& L, Offsets& at, F&& f
   put("layer_pos_embedding", C, L.pos_layer, at.pos_layer, PAD4);
   put("Transformer_0/encoder_norm/scale", C, L.norm_s, at.norm_s, PAD4); put("Transformer_0/encoder_norm/bias", C, L.norm_b, at.norm_b, PAD4);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    const TrainLayout::CL& s = L.layer[l];
-    TrainLayout::CL& d = at.layer[l];
+    const BlockLeaves& s = L.layer[l];
+    BlockLeaves& d = at.layer[l];
     put.in("Transformer_0/encoderblock_", "/", l, 0);
     put("LayerNorm_0/scale", C, s.ln0_s, d.ln0_s, PAD4); put("LayerNorm_0/bias", C, s.ln0_b, d.ln0_b, PAD4);
     put(HVLA_ATT "query/kernel", C * C, s.wq, d.wq, PAD4); put(HVLA_ATT "query/bias", C, s.bq, d.bq, PAD4);
@@ -107,17 +107,17 @@ inline Extent served_enc(const Geom& g, const TrainLayout& L, Offsets& at, F&& f
   put("embeddings_position_embeddings", g.S() * E, L.e_pos, at.e_pos, POS);
   put("layernorm_scale", E, L.e_lns, at.e_lns, COPY); put("layernorm_bias", E, L.e_lnb, at.e_lnb, COPY);
   for (int l = 0; l < g.enc_layers; ++l) {
-    const TrainLayout::EL& s = L.enc[l];
-    TrainLayout::EL& d = at.enc[l];
+    const BlockLeaves& s = L.enc[l];
+    BlockLeaves& d = at.enc[l];
     put.in("encoder_image_encoder_encoder_layer_", "_", l, L.total);
-    put("attention_attention_query_kernel", E * E, s.qk, d.qk, TRANSPOSE, E); put("attention_attention_query_bias", E, s.qb, d.qb, COPY);
-    put("attention_attention_key_kernel", E * E, s.kk, d.kk, TRANSPOSE, E); put("attention_attention_key_bias", E, s.kb, d.kb, COPY);
-    put("attention_attention_value_kernel", E * E, s.vk, d.vk, TRANSPOSE, E); put("attention_attention_value_bias", E, s.vb, d.vb, COPY);
-    put("attention_output_dense_kernel", E * E, s.ok, d.ok, TRANSPOSE, E); put("attention_output_dense_bias", E, s.ob, d.ob, COPY);
-    put("mlp_fc1_kernel", E * Fe, s.f1k, d.f1k, TRANSPOSE, E); put("mlp_fc1_bias", Fe, s.f1b, d.f1b, COPY);
-    put("mlp_fc2_kernel", Fe * E, s.f2k, d.f2k, TRANSPOSE, Fe); put("mlp_fc2_bias", E, s.f2b, d.f2b, COPY);
-    put("norm1_scale", E, s.n1s, d.n1s, COPY); put("norm1_bias", E, s.n1b, d.n1b, COPY);
-    put("norm2_scale", E, s.n2s, d.n2s, COPY); put("norm2_bias", E, s.n2b, d.n2b, COPY);
+    put("attention_attention_query_kernel", E * E, s.wq, d.wq, TRANSPOSE, E); put("attention_attention_query_bias", E, s.bq, d.bq, COPY);
+    put("attention_attention_key_kernel", E * E, s.wk, d.wk, TRANSPOSE, E); put("attention_attention_key_bias", E, s.bk, d.bk, COPY);
+    put("attention_attention_value_kernel", E * E, s.wv, d.wv, TRANSPOSE, E); put("attention_attention_value_bias", E, s.bv, d.bv, COPY);
+    put("attention_output_dense_kernel", E * E, s.wo, d.wo, TRANSPOSE, E); put("attention_output_dense_bias", E, s.bo, d.bo, COPY);
+    put("mlp_fc1_kernel", E * Fe, s.w1, d.w1, TRANSPOSE, E); put("mlp_fc1_bias", Fe, s.b1, d.b1, COPY);
+    put("mlp_fc2_kernel", Fe * E, s.w2, d.w2, TRANSPOSE, Fe); put("mlp_fc2_bias", E, s.b2, d.b2, COPY);
+    put("norm1_scale", E, s.ln0_s, d.ln0_s, COPY); put("norm1_bias", E, s.ln0_b, d.ln0_b, COPY);
+    put("norm2_scale", E, s.ln1_s, d.ln1_s, COPY); put("norm2_bias", E, s.ln1_b, d.ln1_b, COPY);
     put("layer_scale1_lambda1", E, s.ls1, d.ls1, COPY); put("layer_scale2_lambda1", E, s.ls2, d.ls2, COPY);
   }
   return put.e;
@@ -183,9 +183,9 @@ inline EncMap enc_map(const Geom& g, const TrainLayout& L) {
   m.n16 = e.n16;
   m.vec.dst_total = e.nf;
   if (g.enc_layers > 0) {
-    m.vec.src_stride = m.mat_src_stride = g.enc_layers > 1 ? L.enc[1].kb - L.enc[0].kb : 0;
-    m.vec.dst_stride = (e.nf - at.enc[0].qb) / g.enc_layers;
-    m.mat_dst_stride = (e.n16 - at.enc[0].qk) / g.enc_layers;
+    m.vec.src_stride = m.mat_src_stride = g.enc_layers > 1 ? L.enc[1].bk - L.enc[0].bk : 0;
+    m.vec.dst_stride = (e.nf - at.enc[0].bq) / g.enc_layers;
+    m.mat_dst_stride = (e.n16 - at.enc[0].wq) / g.enc_layers;
   }
   return m;
 }

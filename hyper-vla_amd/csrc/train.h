@@ -102,12 +102,23 @@ struct AttnAux {
   float* align = nullptr;             // [B] out, nullable: align_b (written iff w_align > 0)
   bool on() const { return w_ent > 0.f || w_align > 0.f; }
 };
+// what the hvla_train_* setters selected, in one struct for the three entries below (default: everything off)
+struct TrainOptions {
+  PosSource ps;                       // hvla_train_position_source (trained encoder only)
+  const uint8_t* frozen = nullptr;    // hvla_train_frozen: the mask of train_apply / train_accumulate ...
+  int frozen_buckets = 0;             //   ... and the buckets train_step leaves out
+  AttnAux aux;                        // hvla_train_attention_losses
+};
+// vector length of params / grads / mu / nu: the shared leaves and the position table's source follow the hypernetwork's when
+// the image encoder is trained
+inline long train_vector_elems(const TrainLayout& L, const PosSource& ps, bool train_encoder) {
+  return L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
+}
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done = nullptr, const PosSource& ps = PosSource(),
-                      int frozen_buckets = 0, const AttnAux& aux = AttnAux());
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const TrainOptions& opt);
 hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
-                       const PosSource& ps = PosSource(), const uint8_t* frozen = nullptr);
+                       const TrainOptions& opt);
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st, const PosSource& ps = PosSource(), const uint8_t* frozen = nullptr);
+                            bool train_encoder, hipStream_t st, const TrainOptions& opt);
 
 }  // namespace hvla

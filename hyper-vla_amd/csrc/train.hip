@@ -407,6 +407,11 @@ hipError_t train_gemm_timer_read(float* ms, double* flops, int* launches) {
 }
 static void bgemm_launch(hipStream_t st, bool ta, bool tb, BG g, int nb0);
 void bgemm(hipStream_t st, bool ta, bool tb, BG g, int nb0) {
+#ifdef HVLA_TRAIN_TRACE
+  void bgemm_trace(bool ta, bool tb, const BG& g, int nb0);
+  bgemm_trace(ta, tb, g, nb0);
+  return;
+#endif
   if (g_gemm_timers_on == 0) { bgemm_launch(st, ta, tb, g, nb0); return; }
   GemmTimer* tp = gemm_timer_here();
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1176,38 +1181,31 @@ __global__ void adamw_frozen_kernel(float* __restrict__ p, const float* __restri
 // ------------------------------------------------------------------------------------------------
 // host sequencing
 // ------------------------------------------------------------------------------------------------
+// The launch seam: everything train_step / train_apply / train_accumulate enqueue goes through KL, ENQ or bgemm().  Under
+// HVLA_TRAIN_TRACE (tools/train_launch_trace.cpp; neither library sets it) the three print one line per operation and enqueue
+// nothing: tests/native/train_step_trace.txt pins what a step launches, argument for argument.
+#ifdef HVLA_TRAIN_TRACE
+#include "../../tools/train_launch_trace.h"
+#else
 #define KL(kernel, grid, block, ...) hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__)
+#define ENQ(fn, ...) (void)fn(__VA_ARGS__)
+#endif
 static inline dim3 g1(long n, int bs = 256) { long b = (n + bs - 1) / bs; return dim3((unsigned)(b > 65535 ? 65535 : b)); }
-
-struct Off { int wp, bp, pos, ns, nb, wc, bc, wd, bd; struct Lyr { int l0s, l0b, l1s, l1b, w1, b1, w2, b2, wk, bk, wo, bo, wq, bq, wv, bv; } l[16]; };
-static Off leaf_offsets(const Geom& g) {
-  Off o{};
-  auto lv = generated_leaves(g);
-  auto f = [&](const std::string& n) { for (auto& l : lv) if (l.flat == n) return (int)l.offset; return -1; };
-  o.bc = f("action_head_continuous_head_bias"); o.wc = f("action_head_continuous_head_kernel");
-  o.bd = f("action_head_discrete_head_bias"); o.wd = f("action_head_discrete_head_kernel");
-  o.nb = f("encoder_Transformer_0_encoder_norm_bias"); o.ns = f("encoder_Transformer_0_encoder_norm_scale");
-  o.bp = f("encoder_image_embedding_projection_bias"); o.wp = f("encoder_image_embedding_projection_kernel");
-  o.pos = f("encoder_pos_embedding");
-  for (int l = 0; l < g.L; ++l) {
-    const std::string B = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_", A = B + "MultiHeadDotProductAttention_0_";
-    Off::Lyr& y = o.l[l];
-    y.l0b = f(B + "LayerNorm_0_bias"); y.l0s = f(B + "LayerNorm_0_scale"); y.l1b = f(B + "LayerNorm_1_bias"); y.l1s = f(B + "LayerNorm_1_scale");
-    y.b1 = f(B + "MlpBlock_0_Dense_0_bias"); y.w1 = f(B + "MlpBlock_0_Dense_0_kernel");
-    y.b2 = f(B + "MlpBlock_0_Dense_1_bias"); y.w2 = f(B + "MlpBlock_0_Dense_1_kernel");
-    y.bk = f(A + "key_bias"); y.wk = f(A + "key_kernel"); y.bo = f(A + "out_bias"); y.wo = f(A + "out_kernel");
-    y.bq = f(A + "query_bias"); y.wq = f(A + "query_kernel"); y.bv = f(A + "value_bias"); y.wv = f(A + "value_kernel");
-  }
-  return o;
-}
 
 // Transformer block forward / backward on rows [nb][S][D] with weights at W + b * wstride (wstride = G for
 // the per-episode policy, 0 for the shared context encoder).  Buffers for one layer:
 // h, h2, g (the two LayerNorm outputs and the GELU output): kept per block when the plan has room for them (the backward pass
 // then reads them instead of recomputing them: two LayerNorm passes and one GELU pass per block), else nullptr
 struct BlkBuf { float *x_in, *mean0, *rstd0, *q, *k, *v, *p, *o, *x_mid, *mean1, *rstd1, *u, *y1, *y2, *h, *h2, *g; };
-struct BlkW { const float *l0s, *l0b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *l1s, *l1b, *w1, *b1, *w2, *b2, *ls1, *ls2; };
-struct BlkG { float *l0s, *l0b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *l1s, *l1b, *w1, *b1, *w2, *b2, *ls1, *ls2; };
+// one block's leaves as pointers (T = const float: weights, T = float: their gradients): BlockLeaves' members, bound to a base
+template <class T> struct Blk { T *l0s, *l0b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *l1s, *l1b, *w1, *b1, *w2, *b2, *ls1, *ls2; };
+using BlkW = Blk<const float>;
+using BlkG = Blk<float>;
+template <class T> static Blk<T> bind(T* base, const BlockLeaves& y) {
+  auto at = [&](long o) { return o < 0 ? nullptr : base + o; };      // -1: the block has no such leaf (LayerScale)
+  return Blk<T>{at(y.ln0_s), at(y.ln0_b), at(y.wq), at(y.bq), at(y.wk), at(y.bk), at(y.wv), at(y.bv), at(y.wo), at(y.bo),
+                at(y.ln1_s), at(y.ln1_b), at(y.w1), at(y.b1), at(y.w2), at(y.b2), at(y.ls1), at(y.ls2)};
+}
 // block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
 // HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention)
 struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; };
@@ -1275,7 +1273,7 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     linear(st, nb, S, ws, a.o, w.wo, w.bo, a.y1, D, D, 0);
     scale_add(st, a.x_mid, a.x_in, a.y1, w.ls1, (long)rows * D, D);
   } else {
-    (void)hipMemcpyAsync(a.x_mid, a.x_in, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
+    ENQ(hipMemcpyAsync, a.x_mid, a.x_in, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
     linear(st, nb, S, ws, a.o, w.wo, w.bo, a.x_mid, D, D, 1);
   }
   KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_mid, h2, a.mean1, a.rstd1, w.l1s, w.l1b, ws, rows, S, D);
@@ -1285,7 +1283,7 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     linear(st, nb, S, ws, gg, w.w2, w.b2, a.y2, F, D, 0);
     scale_add(st, x_out, a.x_mid, a.y2, w.ls2, (long)rows * D, D);
   } else {
-    (void)hipMemcpyAsync(x_out, a.x_mid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
+    ENQ(hipMemcpyAsync, x_out, a.x_mid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
     linear(st, nb, S, ws, gg, w.w2, w.b2, x_out, F, D, 1);
   }
 }
@@ -1440,14 +1438,15 @@ size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
 }
 
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
-                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const PosSource& ps, int frozen_buckets,
-                      const AttnAux& aux) {
+                      const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const TrainOptions& opt) {
+  const PosSource& ps = opt.ps;
+  const AttnAux& aux = opt.aux;
+  const int frozen_buckets = opt.frozen_buckets;
   const int S = g.S(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
   const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
   const bool enc = in.images != nullptr;
   const long G = L.G;
-  const Off off = leaf_offsets(g);
   const Plan pl = make_plan(g, B, enc, tb.work);
   const std::vector<BlkBuf>&cb = pl.cb, &pb = pl.pb, &eb = pl.eb;
   float *cx_fin = pl.cx_fin, *cdx = pl.cdx, *px_fin = pl.px_fin, *pdx = pl.pdx;
@@ -1458,23 +1457,21 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const float* Pe = Pm + L.total;          // shared DINOv2 leaves (only touched when enc)
   float* Ge = Gm + L.total;
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
-  (void)hipMemsetAsync(Gm, 0, (size_t)(L.total + (enc ? L.enc_total : 0) + (src_on ? ps.tail() : 0)) * 4, st);
-  (void)hipMemsetAsync(tb.dtheta, 0, (size_t)B * G * 4, st);
+  ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
+  ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
   const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0}, enc_opt{2, nullptr, 1};
 
   // =============================== DINOv2 forward in f32, activations kept (HF Dinov2Model; base_vit.py:111-131) =====
-  auto ew = [&](int l, const float* b) { const TrainLayout::EL& y = L.enc[l]; return BlkW{b + y.n1s, b + y.n1b, b + y.qk, b + y.qb, b + y.kk, b + y.kb, b + y.vk, b + y.vb, b + y.ok, b + y.ob, b + y.n2s, b + y.n2b, b + y.f1k, b + y.f1b, b + y.f2k, b + y.f2b, b + y.ls1, b + y.ls2}; };
-  auto eg = [&](int l, float* b) { const TrainLayout::EL& y = L.enc[l]; return BlkG{b + y.n1s, b + y.n1b, b + y.qk, b + y.qb, b + y.kk, b + y.kb, b + y.vk, b + y.vb, b + y.ok, b + y.ob, b + y.n2s, b + y.n2b, b + y.f1k, b + y.f1b, b + y.f2k, b + y.f2b, b + y.ls1, b + y.ls2}; };
   const float* tokens = in.tokens;         // [B][P][E] rows, episode stride tok_stride
   long tok_stride = (long)P * E;
   if (enc) {
     float* ex0 = eb.empty() ? pl.ex_fin : eb[0].x_in;
-    if (src_on) (void)launch_position_interp(Pe + L.enc_total, ps.n, ps.w, tb.params + L.total + L.e_pos, ps.grid, E, st);     // tail -> slot
+    if (src_on) ENQ(launch_position_interp, Pe + L.enc_total, ps.n, ps.w, tb.params + L.total + L.e_pos, ps.grid, E, st);     // tail -> slot
     KL(im2col_f32_kernel, g1((long)B * P * Kp), dim3(256), in.images, pl.patches, B, g.image_size, g.patch);
     bgemm(st, false, false, BG{pl.patches, Pe + L.e_pk, ex0 + E, Pe + L.e_pb, P, E, Kp, Kp, E, E, (long)P * Kp, 0, 0, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
     KL(enc_x0_kernel, g1((long)B * Se * E), dim3(256), ex0, Pe + L.e_cls, Pe + L.e_pos, B, Se, E);
     for (int l = 0; l < g.enc_layers; ++l)
-      block_fwd(st, B, Se, E, He, Fe, 0, ew(l, Pe), eb[l], l + 1 < g.enc_layers ? eb[l + 1].x_in : pl.ex_fin, t, enc_opt);
+      block_fwd(st, B, Se, E, He, Fe, 0, bind(Pe, L.enc[l]), eb[l], l + 1 < g.enc_layers ? eb[l + 1].x_in : pl.ex_fin, t, enc_opt);
     KL(ln_fwd_kernel, dim3((B * Se + 3) / 4), dim3(256), pl.ex_fin, pl.eh, pl.emean, pl.erstd, Pe + L.e_lns, Pe + L.e_lnb, 0, B * Se, Se, E);
     tokens = pl.eh + E;                    // drop the CLS row through the pointer: rows 1.. of every [Se][E] block
     tok_stride = (long)Se * E;
@@ -1486,10 +1483,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   bgemm(st, false, false, BG{in.tok, Pm + L.w_tok, cx0, Pm + L.b_tok, T, C, g.lang_dim, g.lang_dim, C, C, (long)T * g.lang_dim, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
   bgemm(st, false, false, BG{in.cls, Pm + L.w_img, cx0 + (long)T * C, Pm + L.b_img, 1, C, E, E, C, C, (long)E, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
   KL(ctx_rows_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, C);
-  auto cw = [&](int l) { const TrainLayout::CL& c = L.layer[l]; return BlkW{Pm + c.ln0_s, Pm + c.ln0_b, Pm + c.wq, Pm + c.bq, Pm + c.wk, Pm + c.bk, Pm + c.wv, Pm + c.bv, Pm + c.wo, Pm + c.bo, Pm + c.ln1_s, Pm + c.ln1_b, Pm + c.w1, Pm + c.b1, Pm + c.w2, Pm + c.b2, nullptr, nullptr}; };
-  auto cg = [&](int l) { const TrainLayout::CL& c = L.layer[l]; return BlkG{Gm + c.ln0_s, Gm + c.ln0_b, Gm + c.wq, Gm + c.bq, Gm + c.wk, Gm + c.bk, Gm + c.wv, Gm + c.bv, Gm + c.wo, Gm + c.bo, Gm + c.ln1_s, Gm + c.ln1_b, Gm + c.w1, Gm + c.b1, Gm + c.w2, Gm + c.b2, nullptr, nullptr}; };
   for (int l = 0; l < g.ctx_layers; ++l)
-    block_fwd(st, B, Sc, C, Hc, Fc, 0, cw(l), cb[l], l + 1 < g.ctx_layers ? cb[l + 1].x_in : cx_fin, t, ctx_opt);
+    block_fwd(st, B, Sc, C, Hc, Fc, 0, bind(Pm, L.layer[l]), cb[l], l + 1 < g.ctx_layers ? cb[l + 1].x_in : cx_fin, t, ctx_opt);
   // ctx = LN_f(x[:, -1]) (/ sqrt(C)); rows gathered through a stride: x = cx_fin + (Sc-1)*C, row stride Sc*C
   KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
   // =============================== theta = ctx W_cat + b_cat (hypernetwork.py:205-233) ===============================
@@ -1497,15 +1492,13 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // =============================== policy forward with per-episode weights ===============================
   const float* TH = tb.theta;
   float* px0 = pb[0].x_in;
-  bgemm(st, false, false, BG{tokens, TH + off.wp, px0, TH + off.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
-  KL(x0_finish_kernel, g1((long)B * S * D), dim3(256), px0, TH + off.pos, G, S, D, B);
-  auto pw = [&](int l, const float* b) { const Off::Lyr& y = off.l[l]; return BlkW{b + y.l0s, b + y.l0b, b + y.wq, b + y.bq, b + y.wk, b + y.bk, b + y.wv, b + y.bv, b + y.wo, b + y.bo, b + y.l1s, b + y.l1b, b + y.w1, b + y.b1, b + y.w2, b + y.b2, nullptr, nullptr}; };
-  auto pg = [&](int l, float* b) { const Off::Lyr& y = off.l[l]; return BlkG{b + y.l0s, b + y.l0b, b + y.wq, b + y.bq, b + y.wk, b + y.bk, b + y.wv, b + y.bv, b + y.wo, b + y.bo, b + y.l1s, b + y.l1b, b + y.w1, b + y.b1, b + y.w2, b + y.b2, nullptr, nullptr}; };
+  bgemm(st, false, false, BG{tokens, TH + L.wp, px0, TH + L.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
+  KL(x0_finish_kernel, g1((long)B * S * D), dim3(256), px0, TH + L.pos, G, S, D, B);
   for (int l = 0; l < g.L; ++l)
-    block_fwd(st, B, S, D, H, F, G, pw(l, TH), pb[l], l + 1 < g.L ? pb[l + 1].x_in : px_fin, t, pol_opt);
+    block_fwd(st, B, S, D, H, F, G, bind(TH, L.pol[l]), pb[l], l + 1 < g.L ? pb[l + 1].x_in : px_fin, t, pol_opt);
   // =============================== head + loss (+ backward seed) ===============================
-  (void)hipMemsetAsync(pdx, 0, (size_t)B * S * D * 4, st);
-  HeadP hpp{px_fin, (long)S * D, TH, tb.dtheta, G, off.wc, off.bc, off.wd, off.bd, off.ns, off.nb, in.target, in.tmask, in.amask,
+  ENQ(hipMemsetAsync, pdx, 0, (size_t)B * S * D * 4, st);
+  HeadP hpp{px_fin, (long)S * D, TH, tb.dtheta, G, (int)L.wc, (int)L.bc, (int)L.wd, (int)L.bd, (int)L.ns, (int)L.nb, in.target, in.tmask, in.amask,
             tb.loss, hp.forward_only ? nullptr : dxrow, tb.actions, tb.logits, B, S, D, g.horizon, g.action_dim, g.tanh_scale, g.max_action, g.clip_target};
   KL(head_loss_kernel, dim3(B), dim3(64), hpp);
   // hvla_train_attention_losses: the last layer's action row, [B][H][S][Sp] like t.dp (block_fwd / block_bwd)
@@ -1518,32 +1511,32 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   KL(add_strided_kernel, g1((long)B * D), dim3(256), pdx + (long)(S - 1) * D, (long)S * D, dxrow, (long)D, B);
   // =============================== policy backward ===============================
   for (int l = g.L - 1; l >= 0; --l)
-    block_bwd(st, B, S, D, H, F, G, G, pw(l, TH), pg(l, tb.dtheta), pb[l], pdx, t, pol_opt, aux.on() && l == g.L - 1 ? &auxp : nullptr);
+    block_bwd(st, B, S, D, H, F, G, G, bind(TH, L.pol[l]), bind(tb.dtheta, L.pol[l]), pb[l], pdx, t, pol_opt, aux.on() && l == g.L - 1 ? &auxp : nullptr);
   // x0 = [tokens Wp + bp ; 0] + pos : dpos = dx0, dbp = sum_{t<P} dx0, dWp = tokens^T dx0[:P]
-  KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + off.pos, G, pdx, (long)S * D, B);
-  KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx, tb.dtheta + off.bp, G, S, P, D, B);
-  bgemm(st, true, false, BG{tokens, pdx, tb.dtheta + off.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+  KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + L.pos, G, pdx, (long)S * D, B);
+  KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx, tb.dtheta + L.bp, G, S, P, D, B);
+  bgemm(st, true, false, BG{tokens, pdx, tb.dtheta + L.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
   // =============================== DINOv2 backward ===============================
   if (enc) {
     // d tokens_b = dx0_b[:P] Wp_b^T -> rows 1.. of the final-LayerNorm output gradient (CLS row gets none)
     float* dh = t.y;                                                      // [B][Se][E]; t.y is free between blocks
-    (void)hipMemsetAsync(dh, 0, (size_t)B * Se * E * 4, st);
-    bgemm(st, false, true, BG{pdx, TH + off.wp, dh + E, nullptr, P, E, D, D, D, E, (long)S * D, 0, G, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
+    ENQ(hipMemsetAsync, dh, 0, (size_t)B * Se * E * 4, st);
+    bgemm(st, false, true, BG{pdx, TH + L.wp, dh + E, nullptr, P, E, D, D, D, E, (long)S * D, 0, G, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
     float* edx = pl.edx;
     KL(ln_bwd_kernel, dim3((B * Se + 3) / 4), dim3(256), pl.ex_fin, dh, pl.emean, pl.erstd, Pe + L.e_lns, edx, (float*)nullptr, (float*)nullptr, 0, B * Se, Se, E, 0);
     KL(ln_pgrad_kernel, dim3((E + 63) / 64, (B * Se + 63) / 64), dim3(64), pl.ex_fin, dh, pl.emean, pl.erstd, Ge + L.e_lns, Ge + L.e_lnb, B * Se, E);
     for (int l = g.enc_layers - 1; l >= 0; --l)
-      block_bwd(st, B, Se, E, He, Fe, 0, 0, ew(l, Pe), eg(l, Ge), eb[l], edx, t, enc_opt);
+      block_bwd(st, B, Se, E, He, Fe, 0, 0, bind(Pe, L.enc[l]), bind(Ge, L.enc[l]), eb[l], edx, t, enc_opt);
     // x0[b][0] = cls + pos[0]; x0[b][1+t] = patch_t Wk + bk + pos[1+t]
     KL(colsum_kernel, dim3((Se * E + 63) / 64, 1, (B + 63) / 64), dim3(64), edx, Ge + L.e_pos, 0, B, B, Se * E, 1);       // dpos = sum_b dx0
-    (void)hipMemcpyAsync(Ge + L.e_cls, Ge + L.e_pos, (size_t)E * 4, hipMemcpyDeviceToDevice, st);                          // dcls = dpos[0]
+    ENQ(hipMemcpyAsync, Ge + L.e_cls, Ge + L.e_pos, (size_t)E * 4, hipMemcpyDeviceToDevice, st);                          // dcls = dpos[0]
     KL(colsum_kernel, dim3((E + 63) / 64, 1, (P + 63) / 64), dim3(64), Ge + L.e_pos + E, Ge + L.e_pb, 0, P, P, E, 1);     // dbias = sum_{t>=1} dpos[t]
     bgemm(st, true, false, BG{pl.patches, edx + E, Ge + L.e_pk, nullptr, Kp, E, P, Kp, E, E, (long)P * Kp, 0, (long)Se * E, 0, 0, 0, 0, 1, 1.f, 2}, B);
     if (src_on) {                                                        // dsource = A^T dslot; the slot is no parameter: its gradient is zero
-      (void)launch_position_adjoint(Ge + L.e_pos, ps.n, ps.w, Ge + L.enc_total, ps.grid, E, st);
-      (void)hipMemsetAsync(Ge + L.e_pos, 0, (size_t)Se * E * 4, st);
+      ENQ(launch_position_adjoint, Ge + L.e_pos, ps.n, ps.w, Ge + L.enc_total, ps.grid, E, st);
+      ENQ(hipMemsetAsync, Ge + L.e_pos, 0, (size_t)Se * E * 4, st);
     }
-    if (bucket_done) (void)hipEventRecord(bucket_done[0], st);           // the shared DINOv2 leaves are final
+    if (bucket_done) ENQ(hipEventRecord, bucket_done[0], st);           // the shared DINOv2 leaves are final
   }
   // =============================== weight generation backward ===============================
   // hvla_train_frozen: a bucket declared frozen is not computed -- its range of `grads` stays the zeros of the memset above, its
@@ -1554,31 +1547,33 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     KL(colsum_kernel, dim3((unsigned)((G + 63) / 64), 1, (B + 63) / 64), dim3(64), tb.dtheta, Gm + L.bcat, 0, B, B, (int)G, 1);                  // db_cat
   }
   if (ctx_on) {
-    (void)hipMemsetAsync(dctx, 0, (size_t)B * C * 4, st);
+    ENQ(hipMemsetAsync, dctx, 0, (size_t)B * C * 4, st);
     // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
     bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
   }
-  if (bucket_done) (void)hipEventRecord(bucket_done[1], st);             // W_cat, b_cat are final
+  if (bucket_done) ENQ(hipEventRecord, bucket_done[1], st);             // W_cat, b_cat are final
   // =============================== context encoder backward ===============================
   if (ctx_on) {
-    (void)hipMemsetAsync(cdx, 0, (size_t)B * Sc * C * 4, st);
+    ENQ(hipMemsetAsync, cdx, 0, (size_t)B * Sc * C * 4, st);
     KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
     for (int l = g.ctx_layers - 1; l >= 0; --l)
-      block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, cw(l), cg(l), cb[l], cdx, t, ctx_opt);
+      block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, bind(Pm, L.layer[l]), bind(Gm, L.layer[l]), cb[l], cdx, t, ctx_opt);
     // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
     KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
     bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
     bgemm(st, true, false, BG{in.cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
   }
-  if (bucket_done) (void)hipEventRecord(bucket_done[2], st);             // the context encoder's leaves: everything is final
+  if (bucket_done) ENQ(hipEventRecord, bucket_done[2], st);             // the context encoder's leaves: everything is final
   return hipGetLastError();
 }
 
 hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const TrainHyper& hp, bool train_encoder, hipStream_t st,
-                       const PosSource& ps, const uint8_t* frozen) {
+                       const TrainOptions& opt) {
+  const PosSource& ps = opt.ps;
+  const uint8_t* frozen = opt.frozen;
   const long tail = train_encoder ? ps.tail() : 0;           // the position table's source (shared group; the slot's gradient is zero)
-  const long n = L.total + (train_encoder ? L.enc_total : 0) + tail;
-  (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
+  const long n = train_vector_elems(L, ps, train_encoder);
+  ENQ(hipMemsetAsync, tb.sqsum, 0, 4, st);
   const float t = (float)(hp.step + 1);
   const float bc1 = 1.f - powf(hp.b1, t), bc2 = 1.f - powf(hp.b2, t);
   if (frozen) {                                               // hvla_train_frozen: the norm and both groups over the trainable elements
@@ -1600,16 +1595,17 @@ hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const Train
   }
   if (tail) {                                                 // the derived slots follow their tails
     const long slot = L.total + L.e_pos, src = L.total + L.enc_total;
-    (void)launch_position_interp(tb.params + src, ps.n, ps.w, tb.params + slot, ps.grid, ps.E, st);
-    if (hp.ema_decay > 0.f && tb.ema) (void)launch_position_interp(tb.ema + src, ps.n, ps.w, tb.ema + slot, ps.grid, ps.E, st);
+    ENQ(launch_position_interp, tb.params + src, ps.n, ps.w, tb.params + slot, ps.grid, ps.E, st);
+    if (hp.ema_decay > 0.f && tb.ema) ENQ(launch_position_interp, tb.ema + src, ps.n, ps.w, tb.ema + slot, ps.grid, ps.E, st);
   }
   return hipGetLastError();
 }
 
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
-                            bool train_encoder, hipStream_t st, const PosSource& ps, const uint8_t* frozen) {
-  const long n = L.total + (train_encoder ? L.enc_total + ps.tail() : 0);
-  (void)hipMemsetAsync(tb.sqsum, 0, 4, st);
+                            bool train_encoder, hipStream_t st, const TrainOptions& opt) {
+  const uint8_t* frozen = opt.frozen;
+  const long n = train_vector_elems(L, opt.ps, train_encoder);
+  ENQ(hipMemsetAsync, tb.sqsum, 0, 4, st);
   if (frozen) {                                               // the clip's norm is over the trainable elements
     KL(sqsum_frozen_kernel, dim3(1024), dim3(256), tb.grads, frozen, n, tb.sqsum);
   } else {

@@ -7,15 +7,32 @@
 
 namespace hvla {
 
+// The leaves of ONE transformer block, as offsets into whatever holds it: the context encoder's blocks in the hypernetwork's
+// part of the vector, DINOv2's blocks in the shared part, the generated policy's blocks in a row of theta -- and, in the serving
+// tables (serving_layout.h), the same members as offsets into the serving buffers.  ls1 / ls2 (LayerScale): DINOv2 only, else -1.
+struct BlockLeaves { long ln0_s, ln0_b, wq, bq, wk, bk, wv, bv, wo, bo, ln1_s, ln1_b, w1, b1, w2, b2, ls1, ls2; };
+
 // flat layout of the trainable hypernetwork parameters (float32 elements)
 // `total` = the hypernetwork's own parameters; the shared DINOv2 leaves follow at [total, total + enc_total) when the
 // image encoder is trained too (`fine_tune_pretrained_image_encoder=True`), in hypervla.config.encoder_leaves order.
+// wp .. bd and pol[]: the generated policy's leaves in a row of theta [G] (generated_leaves order, by flax name).
 struct TrainLayout {
   long w_tok, b_tok, w_img, b_img, pos_tok, pos_img, pos_layer, norm_s, norm_b, wcat, bcat, total, G;
-  struct CL { long ln0_s, ln0_b, ln1_s, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, w1, b1, w2, b2; } layer[8];
+  BlockLeaves layer[CTX_MAX_LAYERS];
   long e_cls, e_mask, e_pb, e_pk, e_pos, e_lnb, e_lns, enc_total;
-  struct EL { long kb, kk, qb, qk, vb, vk, ob, ok, ls1, ls2, f1b, f1k, f2b, f2k, n1b, n1s, n2b, n2s; } enc[24];
+  BlockLeaves enc[ENC_MAX_LAYERS];
+  long wp, bp, pos, ns, nb, wc, bc, wd, bd;
+  BlockLeaves pol[TRAIN_MAX_POLICY_LAYERS];
+  bool policy_ok;          // every policy leaf above was found by its name (false beyond TRAIN_MAX_POLICY_LAYERS, which the serving
+                           // tables may be built for: they do not read the policy's offsets)
 };
+
+// nullptr, or why the training path (hvla_train_*) does not serve a geometry hvla_create accepted (HVLA_E_SHAPE with this text)
+inline const char* train_refusal(const Geom& g) {
+  if (g.lang_in_policy) return "the training path does not build use_language_token";
+  if (g.ctx_layers > CTX_MAX_LAYERS || g.L > TRAIN_MAX_POLICY_LAYERS || g.enc_layers > ENC_MAX_LAYERS) return "too many layers for the training path";
+  return nullptr;
+}
 inline TrainLayout make_train_layout(const Geom& g) {
   TrainLayout L{};
   long o = 0;
@@ -24,13 +41,15 @@ inline TrainLayout make_train_layout(const Geom& g) {
   add(L.w_tok, (long)g.lang_dim * C); add(L.b_tok, C); add(L.w_img, (long)g.E * C); add(L.b_img, C);
   add(L.pos_tok, (long)g.T * C); add(L.pos_img, C); add(L.pos_layer, C);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    TrainLayout::CL& c = L.layer[l];
+    BlockLeaves& c = L.layer[l];
     add(c.ln0_s, C); add(c.ln0_b, C); add(c.ln1_s, C); add(c.ln1_b, C);
     add(c.wq, (long)C * C); add(c.bq, C); add(c.wk, (long)C * C); add(c.bk, C); add(c.wv, (long)C * C); add(c.bv, C);
     add(c.wo, (long)C * C); add(c.bo, C); add(c.w1, (long)C * F); add(c.b1, F); add(c.w2, (long)F * C); add(c.b2, C);
+    c.ls1 = c.ls2 = -1;
   }
   add(L.norm_s, C); add(L.norm_b, C);
-  L.G = generated_leaves(g).back().offset + generated_leaves(g).back().size;
+  const std::vector<LeafInfo> leaves = generated_leaves(g);
+  L.G = leaves.back().offset + leaves.back().size;
   add(L.wcat, (long)C * L.G); add(L.bcat, L.G);
   L.total = o;
   // shared DINOv2 leaves, hypervla.config.encoder_leaves order, offsets relative to L.total
@@ -38,13 +57,35 @@ inline TrainLayout make_train_layout(const Geom& g) {
   const long E = g.E, Fe = g.enc_mlp, Se = g.P() + 1;
   add(L.e_cls, E); add(L.e_mask, E); add(L.e_pb, E); add(L.e_pk, (long)g.patch * g.patch * 3 * E); add(L.e_pos, Se * E);
   for (int l = 0; l < g.enc_layers; ++l) {
-    TrainLayout::EL& y = L.enc[l];
-    add(y.kb, E); add(y.kk, E * E); add(y.qb, E); add(y.qk, E * E); add(y.vb, E); add(y.vk, E * E); add(y.ob, E); add(y.ok, E * E);
-    add(y.ls1, E); add(y.ls2, E); add(y.f1b, Fe); add(y.f1k, E * Fe); add(y.f2b, E); add(y.f2k, Fe * E);
-    add(y.n1b, E); add(y.n1s, E); add(y.n2b, E); add(y.n2s, E);
+    BlockLeaves& y = L.enc[l];
+    add(y.bk, E); add(y.wk, E * E); add(y.bq, E); add(y.wq, E * E); add(y.bv, E); add(y.wv, E * E); add(y.bo, E); add(y.wo, E * E);
+    add(y.ls1, E); add(y.ls2, E); add(y.b1, Fe); add(y.w1, E * Fe); add(y.b2, E); add(y.w2, Fe * E);
+    add(y.ln0_b, E); add(y.ln0_s, E); add(y.ln1_b, E); add(y.ln1_s, E);
   }
   add(L.e_lnb, E); add(L.e_lns, E);
   L.enc_total = o;
+  // the generated policy, each leaf by its flax name
+  L.policy_ok = g.L <= TRAIN_MAX_POLICY_LAYERS;
+  auto f = [&](const std::string& n) {
+    for (const LeafInfo& l : leaves) if (l.flat == n) return (long)l.offset;
+    L.policy_ok = false;
+    return -1L;
+  };
+  L.bc = f("action_head_continuous_head_bias"); L.wc = f("action_head_continuous_head_kernel");
+  L.bd = f("action_head_discrete_head_bias"); L.wd = f("action_head_discrete_head_kernel");
+  L.nb = f("encoder_Transformer_0_encoder_norm_bias"); L.ns = f("encoder_Transformer_0_encoder_norm_scale");
+  L.bp = f("encoder_image_embedding_projection_bias"); L.wp = f("encoder_image_embedding_projection_kernel");
+  L.pos = f("encoder_pos_embedding");
+  for (int l = 0; l < g.L && l < TRAIN_MAX_POLICY_LAYERS; ++l) {
+    const std::string B = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_", A = B + "MultiHeadDotProductAttention_0_";
+    BlockLeaves& y = L.pol[l];
+    y.ln0_b = f(B + "LayerNorm_0_bias"); y.ln0_s = f(B + "LayerNorm_0_scale"); y.ln1_b = f(B + "LayerNorm_1_bias"); y.ln1_s = f(B + "LayerNorm_1_scale");
+    y.b1 = f(B + "MlpBlock_0_Dense_0_bias"); y.w1 = f(B + "MlpBlock_0_Dense_0_kernel");
+    y.b2 = f(B + "MlpBlock_0_Dense_1_bias"); y.w2 = f(B + "MlpBlock_0_Dense_1_kernel");
+    y.bk = f(A + "key_bias"); y.wk = f(A + "key_kernel"); y.bo = f(A + "out_bias"); y.wo = f(A + "out_kernel");
+    y.bq = f(A + "query_bias"); y.wq = f(A + "query_kernel"); y.bv = f(A + "value_bias"); y.wv = f(A + "value_kernel");
+    y.ls1 = y.ls2 = -1;
+  }
   return L;
 }
 

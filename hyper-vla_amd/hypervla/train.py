@@ -5,7 +5,7 @@ octo/utils/train_utils.py:295-443 ``create_optimizer``).
     ft = FineTuner(model, batch=32, train_encoder=True)     # README.md:55 fine_tune_pretrained_image_encoder=True
     loss = ft.step(instruction_dict, initial_state, images, batch)       # fwd + bwd + all-reduce + AdamW + EMA
 
-All arithmetic is in libhvla (csrc/train.hip); torch owns the device buffers and, when a process group is
+All arithmetic is in libhvla (csrc/train.hip, the vector's layout in csrc/train_layout.h); torch owns the device buffers and, when a process group is
 initialised, all-reduces the flat gradient (RCCL over xGMI on the GPU box — the `pmean` of train.py:460).
 """
 from __future__ import annotations
@@ -24,7 +24,7 @@ POSITION_LEAF = "encoder_image_encoder_embeddings_position_embeddings"
 
 def train_param_layout(g: Geometry, train_encoder: bool = False,
                        position_source: int = 0) -> Tuple[List[Tuple[str, int, Tuple[int, ...]]], int]:
-    """[(name, offset, shape)] of the flat trainable-parameter vector == make_train_layout() in csrc/train.hip.
+    """[(name, offset, shape)] of the flat trainable-parameter vector == make_train_layout() in csrc/train_layout.h.
     The 73 output heads are the fused entries "W_cat" [C, G] and "b_cat" [G] (columns in pytree leaf order); with
     `train_encoder` the shared DINOv2 leaves follow as flat vectors under their checkpoint names.  `position_source` = n
     (hvla_train_position_source, trained encoder only): the n x n source of the position table follows them as the tail
@@ -329,8 +329,7 @@ class FineTuner:
         self.frozen_count = int(plan.sum())
         self.trainable_count = int(plan.size) - self.frozen_count
         self.frozen = torch.as_tensor(plan).to(dev) if self.frozen_count else None
-        self._select_source()
-        self._select_frozen()
+        self._select()
         n, G, work, n_hyper = model._ctx.train_sizes(batch, self.train_encoder)
         layout, total = train_param_layout(self.g, self.train_encoder, self.source_n)
         assert n == total, (n, total)
@@ -370,6 +369,13 @@ class FineTuner:
         self.peak_lr, self.base_peak_lr, self.step_count = peak_lr, base_lr, 0
         self.ema_start_step = int(ema_start_step)
         self._bucket_setup()
+
+    def _select(self, reference=None, attention=False):
+        """What every call into the context starts with, in this order (the mask's length depends on the source); in front of a
+        step (`attention`) also the attention terms, whose annealed alignment weight it returns."""
+        self._select_source()
+        self._select_frozen()
+        return self._select_attention(reference) if attention else None
 
     def _select_source(self):
         """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this
@@ -467,9 +473,7 @@ class FineTuner:
         self._keep = (tok, msk, cls, obs, tgt, am, tm)
         self._keep_reference = ref
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
-        self._select_source()
-        self._select_frozen()
-        wa = self._select_attention(ref)
+        wa = self._select(ref, attention=True)
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
         self.aux_metrics = {}
         if self.attention_entropy > 0:
@@ -511,8 +515,7 @@ class FineTuner:
         on every k-th call only (optax.MultiSteps, octo/utils/train_utils.py:420-421); returns True when they moved."""
         self.all_reduce_gradient()
         ctx, st = self.model._ctx, self.model._stream()
-        self._select_source()
-        self._select_frozen()
+        self._select()
         if self.accum_k > 1:
             if self.micro == 0:
                 self.acc.zero_()
@@ -559,8 +562,7 @@ class FineTuner:
         range; it returns that audit's result, otherwise None."""
         m = self.model
         vec = self.ema if ema else self.params
-        self._select_source()
-        self._select_frozen()
+        self._select()
         if self.source_n:                          # the slot the host copy reads is the resize of the tail being published, whatever
             m._ctx.position_interp(vec[self.tail].data_ptr(), self.source_n, self.interp_w.data_ptr(),     # was done to the vector
                                    vec[self.slot].data_ptr(), m._stream())

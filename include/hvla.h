@@ -273,7 +273,9 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* gripper_logits, 
  * trained (README.md:55; its leaves form the "shared" optimizer group at base_lr / base_weight_decay).  Between the
  * two calls the caller all-reduces `grads` over ranks (RCCL; scripts/train.py:460 `pmean`).
  * Every buffer is DEVICE memory owned by the caller; the flat parameter order is make_train_layout()
- * (csrc/train.hip) == hypervla.train.train_param_layout(); sizes from hvla_train_sizes.                  */
+ * (csrc/train_layout.h) == hypervla.train.train_param_layout(); sizes from hvla_train_sizes.  Every hvla_train_*
+ * entry first asks whether the training path serves the context's geometry: use_language_token, more than 8 context,
+ * 16 policy or 24 image-encoder layers are HVLA_E_SHAPE before any other argument is looked at.         */
 typedef struct hvla_train_buffers {
   float* params;           /* [n_params]                                                     */
   float* grads;            /* [n_params]  written by hvla_train_step                          */

@@ -78,7 +78,7 @@ static Checkpoint cut_checkpoint(const Geom& g, const TrainLayout& L, const floa
   add("initial_image_projection/kernel", L.w_img, E * C); add("initial_image_projection/bias", L.b_img, C);
   add("task_pos_embedding", L.pos_tok, g.T * C); add("initial_image_pos_embedding", L.pos_img, C); add("layer_pos_embedding", L.pos_layer, C);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    const TrainLayout::CL& c = L.layer[l];
+    const BlockLeaves& c = L.layer[l];
     const std::string b = "Transformer_0/encoderblock_" + std::to_string(l) + "/", a = b + "MultiHeadDotProductAttention_0/";
     add(b + "LayerNorm_0/scale", c.ln0_s, C); add(b + "LayerNorm_0/bias", c.ln0_b, C);
     add(b + "LayerNorm_1/scale", c.ln1_s, C); add(b + "LayerNorm_1/bias", c.ln1_b, C);
@@ -103,14 +103,14 @@ static Checkpoint cut_checkpoint(const Geom& g, const TrainLayout& L, const floa
   add(ep + "embeddings_patch_embeddings_projection_kernel", X + L.e_pk, (int64_t)g.patch * g.patch * 3 * E);
   add(ep + "embeddings_position_embeddings", X + L.e_pos, g.S() * E);
   for (int l = 0; l < g.enc_layers; ++l) {
-    const TrainLayout::EL& y = L.enc[l];
+    const BlockLeaves& y = L.enc[l];
     const std::string b = ep + "encoder_layer_" + std::to_string(l) + "_", a = b + "attention_attention_";
-    add(a + "key_bias", X + y.kb, E); add(a + "key_kernel", X + y.kk, E * E); add(a + "query_bias", X + y.qb, E); add(a + "query_kernel", X + y.qk, E * E);
-    add(a + "value_bias", X + y.vb, E); add(a + "value_kernel", X + y.vk, E * E);
-    add(b + "attention_output_dense_bias", X + y.ob, E); add(b + "attention_output_dense_kernel", X + y.ok, E * E);
+    add(a + "key_bias", X + y.bk, E); add(a + "key_kernel", X + y.wk, E * E); add(a + "query_bias", X + y.bq, E); add(a + "query_kernel", X + y.wq, E * E);
+    add(a + "value_bias", X + y.bv, E); add(a + "value_kernel", X + y.wv, E * E);
+    add(b + "attention_output_dense_bias", X + y.bo, E); add(b + "attention_output_dense_kernel", X + y.wo, E * E);
     add(b + "layer_scale1_lambda1", X + y.ls1, E); add(b + "layer_scale2_lambda1", X + y.ls2, E);
-    add(b + "mlp_fc1_bias", X + y.f1b, Fe); add(b + "mlp_fc1_kernel", X + y.f1k, E * Fe); add(b + "mlp_fc2_bias", X + y.f2b, E); add(b + "mlp_fc2_kernel", X + y.f2k, Fe * E);
-    add(b + "norm1_bias", X + y.n1b, E); add(b + "norm1_scale", X + y.n1s, E); add(b + "norm2_bias", X + y.n2b, E); add(b + "norm2_scale", X + y.n2s, E);
+    add(b + "mlp_fc1_bias", X + y.b1, Fe); add(b + "mlp_fc1_kernel", X + y.w1, E * Fe); add(b + "mlp_fc2_bias", X + y.b2, E); add(b + "mlp_fc2_kernel", X + y.w2, Fe * E);
+    add(b + "norm1_bias", X + y.ln0_b, E); add(b + "norm1_scale", X + y.ln0_s, E); add(b + "norm2_bias", X + y.ln1_b, E); add(b + "norm2_scale", X + y.ln1_s, E);
   }
   add(ep + "layernorm_bias", X + L.e_lnb, E); add(ep + "layernorm_scale", X + L.e_lns, E);
   return ck;
@@ -129,16 +129,16 @@ static int members_agree(const Geom& g, const TrainLayout& L, const Offsets& at,
   AT(L, at, w_tok); AT(L, at, b_tok); AT(L, at, w_img); AT(L, at, b_img); AT(L, at, pos_tok); AT(L, at, pos_img); AT(L, at, pos_layer);
   AT(L, at, norm_s); AT(L, at, norm_b);
   for (int l = 0; l < g.ctx_layers; ++l) {
-    const TrainLayout::CL &s = L.layer[l], &d = at.layer[l];
+    const BlockLeaves &s = L.layer[l], &d = at.layer[l];
     AT(s, d, ln0_s); AT(s, d, ln0_b); AT(s, d, ln1_s); AT(s, d, ln1_b); AT(s, d, wq); AT(s, d, bq); AT(s, d, wk); AT(s, d, bk);
     AT(s, d, wv); AT(s, d, bv); AT(s, d, wo); AT(s, d, bo); AT(s, d, w1); AT(s, d, b1); AT(s, d, w2); AT(s, d, b2);
   }
   base = L.total;
   AT(L, at, e_cls); AT(L, at, e_mask); AT(L, at, e_pb); AT(L, at, e_pk); AT(L, at, e_pos); AT(L, at, e_lnb); AT(L, at, e_lns);
   for (int l = 0; l < g.enc_layers; ++l) {
-    const TrainLayout::EL &s = L.enc[l], &d = at.enc[l];
-    AT(s, d, kb); AT(s, d, kk); AT(s, d, qb); AT(s, d, qk); AT(s, d, vb); AT(s, d, vk); AT(s, d, ob); AT(s, d, ok); AT(s, d, ls1); AT(s, d, ls2);
-    AT(s, d, f1b); AT(s, d, f1k); AT(s, d, f2b); AT(s, d, f2k); AT(s, d, n1b); AT(s, d, n1s); AT(s, d, n2b); AT(s, d, n2s);
+    const BlockLeaves &s = L.enc[l], &d = at.enc[l];
+    AT(s, d, bk); AT(s, d, wk); AT(s, d, bq); AT(s, d, wq); AT(s, d, bv); AT(s, d, wv); AT(s, d, bo); AT(s, d, wo); AT(s, d, ls1); AT(s, d, ls2);
+    AT(s, d, b1); AT(s, d, w1); AT(s, d, b2); AT(s, d, w2); AT(s, d, ln0_b); AT(s, d, ln0_s); AT(s, d, ln1_b); AT(s, d, ln1_s);
   }
 #undef AT
   return 0;
@@ -154,11 +154,11 @@ static int refusals(const Geom& g) {
   auto refused = [&](const Checkpoint& ck, const std::string& want) -> int {
     HostImages H;
     H.hn.assign(3, 7.f); H.encf.assign(3, 7.f); H.enc16.assign(3, 7); H.encd16.assign(3, 7); H.lk.assign(3, nullptr); H.lb.assign(3, nullptr);
-    H.at.w_tok = H.at.enc[1].qk = 77;
+    H.at.w_tok = H.at.enc[1].wq = 77;
     REQUIRE(!pack_serving(g, false, ck, H), "the packer accepted a checkpoint without %s", want.c_str());
     REQUIRE(H.missing == want, "the packer names '%s', not '%s'", H.missing.c_str(), want.c_str());
     REQUIRE(H.hn == std::vector<float>(3, 7.f) && H.encf == H.hn && H.enc16 == std::vector<uint16_t>(3, 7) && H.encd16 == H.enc16 &&
-            H.lk.size() == 3 && H.lb.size() == 3 && H.leaves.empty() && H.at.w_tok == 77 && H.at.enc[1].qk == 77,
+            H.lk.size() == 3 && H.lb.size() == 3 && H.leaves.empty() && H.at.w_tok == 77 && H.at.enc[1].wq == 77,
             "the packer wrote before it refused %s", want.c_str());
     return 0;
   };
@@ -227,7 +227,7 @@ static int check(const Geom& g, const char* name, bool bf) {
     push(L.w_tok, (int64_t)g.lang_dim * C); push(L.b_tok, C); push(L.w_img, (int64_t)E * C); push(L.b_img, C);
     push(L.pos_tok, (int64_t)T * C); push(L.pos_img, C); push(L.pos_layer, C); push(L.norm_s, C); push(L.norm_b, C);
     for (int l = 0; l < g.ctx_layers; ++l) {
-      const TrainLayout::CL& c = L.layer[l];
+      const BlockLeaves& c = L.layer[l];
       push(c.ln0_s, C); push(c.ln0_b, C);
       push(c.wq, (int64_t)C * C); push(c.bq, C); push(c.wk, (int64_t)C * C); push(c.bk, C); push(c.wv, (int64_t)C * C); push(c.bv, C);
       push(c.wo, (int64_t)C * C); push(c.bo, C);
@@ -334,18 +334,18 @@ static int check(const Geom& g, const char* name, bool bf) {
     markf(E); memcpy(&wf[curf], X + L.e_lnb, E * 4);
     auto tr = [&](long src, int K, int N, size_t dst) { pack::pack_matrix_t(X + src, K, N, bf, &w16[dst], &d16[dst]); };
     for (int i = 0; i < g.enc_layers; ++i) {
-      const TrainLayout::EL& s = L.enc[i];
+      const BlockLeaves& s = L.enc[i];
       mark16((size_t)3 * E * E);
-      tr(s.qk, E, E, cur16); tr(s.kk, E, E, cur16 + (size_t)E * E); tr(s.vk, E, E, cur16 + (size_t)2 * E * E);
-      mark16((size_t)E * E); tr(s.ok, E, E, cur16);
-      mark16((size_t)E * Fe); tr(s.f1k, E, Fe, cur16);
-      mark16((size_t)Fe * E); tr(s.f2k, Fe, E, cur16);
+      tr(s.wq, E, E, cur16); tr(s.wk, E, E, cur16 + (size_t)E * E); tr(s.wv, E, E, cur16 + (size_t)2 * E * E);
+      mark16((size_t)E * E); tr(s.wo, E, E, cur16);
+      mark16((size_t)E * Fe); tr(s.w1, E, Fe, cur16);
+      mark16((size_t)Fe * E); tr(s.w2, Fe, E, cur16);
       markf(3 * E);
-      memcpy(&wf[curf], X + s.qb, E * 4); memcpy(&wf[curf + E], X + s.kb, E * 4); memcpy(&wf[curf + 2 * E], X + s.vb, E * 4);
-      markf(E); memcpy(&wf[curf], X + s.ob, E * 4);
-      markf(Fe); memcpy(&wf[curf], X + s.f1b, Fe * 4);
-      markf(E); memcpy(&wf[curf], X + s.f2b, E * 4);
-      const long six[6] = {s.n1s, s.n1b, s.n2s, s.n2b, s.ls1, s.ls2};
+      memcpy(&wf[curf], X + s.bq, E * 4); memcpy(&wf[curf + E], X + s.bk, E * 4); memcpy(&wf[curf + 2 * E], X + s.bv, E * 4);
+      markf(E); memcpy(&wf[curf], X + s.bo, E * 4);
+      markf(Fe); memcpy(&wf[curf], X + s.b1, Fe * 4);
+      markf(E); memcpy(&wf[curf], X + s.b2, E * 4);
+      const long six[6] = {s.ln0_s, s.ln0_b, s.ln1_s, s.ln1_b, s.ls1, s.ls2};
       for (int q = 0; q < 6; ++q) { markf(E); memcpy(&wf[curf], X + six[q], E * 4); }
     }
     REQUIRE(o16 == w16.size() && of == wf.size(), "%s: the transcription does not fill its own buffers", name);

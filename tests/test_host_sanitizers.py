@@ -71,3 +71,38 @@ def test_accepted_geometries_under_asan_ubsan(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_train_layout_under_asan_ubsan(tmp_path):
+    """csrc/train_layout.h, the one table of a transformer block's leaves the fine-tune step binds its pointers from: over the TINY,
+    MID and README geometries and the layer-count edges (0 / 8 context layers, 0 / 24 encoder layers, 1 / 16 policy layers) every
+    policy member is the offset of the generated leaf of its flax name, nothing is -1 but the LayerScale of blocks without one, the
+    members tile [0, total), [0, enc_total) and a row of theta without gap or overlap, and one layer more than a table holds is
+    refused by the predicate in front of make_train_layout.  The offsets the program prints for the MID and README vectors are
+    hypervla.train.train_param_layout's, name for name."""
+    from hypervla.config import MID, Geometry
+    from hypervla.train import train_param_layout
+    exe = tmp_path / "train_layout_check"
+    build = subprocess.run(
+        ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
+         "-Werror", "-I", os.path.join(ROOT, "hyper-vla_amd", "csrc"), os.path.join(ROOT, "tests", "native", "train_layout_check.cpp"),
+         "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
+    assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
+    printed, name = {}, None
+    for line in run.stdout.split("\n"):
+        if line.startswith("## "):
+            _, name, total = line.split()
+            printed[name] = ({}, int(total))
+        elif line and line != "OK":
+            leaf, off = line.rsplit(" ", 1)
+            assert leaf not in printed[name][0], leaf
+            printed[name][0][leaf] = int(off)
+    assert sorted(printed) == ["MID", "README"]
+    for name, g in (("MID", MID), ("README", Geometry())):
+        layout, total = train_param_layout(g, True)
+        assert printed[name][1] == total
+        assert printed[name][0] == {leaf: off for leaf, off, _ in layout}, name
