@@ -80,7 +80,9 @@ struct hvla_ctx {
   DevBuf enc16, encd16, encf32;  // encoder matrices (16-bit), their rounding residues x 4096 (16-bit) and vectors (f32)
   EncWeights encw{};
   // workspaces (sized for cfg.max_batch)
-  DevBuf ctx_hi, ctx_lo, ctx_f32, ws_x, ws_h, ws_qkv, ws_g, ws_corr, ws_abar, ws_lncnt, ws_lnpart, tokens, flags;
+  DevBuf ctx_hi, ctx_lo, ctx_f32, tokens, flags;
+  WorkspacePlan wsp;             // the encoder's workspace (plan.h): sizes of ws[] and where an episode's slice of each begins
+  DevBuf ws[NUM_WS];
   uint32_t ln_spin = 800;        // EncWorkspace::ln_spin (8 us); hvla_debug_lnx_spin of the bench library changes it
 #ifdef HVLA_BENCH_HOOKS
   int enc_stop = 0;              // EncWorkspace::stop_after (hvla_debug_encode_stop)
@@ -168,20 +170,15 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
     for (uint8_t s : seen)
       if (!s) return HVLA_E_STATE;
   }
-  const size_t Bm = c->max_batch, S = g.S(), E = g.E, F = g.enc_mlp;
-  size_t gbytes = Bm * S * F * 2;
-  if (gbytes < Bm * P * ctx->Kp * 2) gbytes = Bm * P * ctx->Kp * 2;
+  const size_t Bm = c->max_batch;
+  ctx->wsp = WorkspacePlan(P, g.S(), g.E, g.enc_mlp, ctx->Kp, c->max_batch);
   hipError_t e = hipSuccess;
   auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
   A(ctx->ctx_hi, Bm * g.C * 2); A(ctx->ctx_lo, Bm * g.C * 2); A(ctx->ctx_f32, Bm * g.C * 4);
-  A(ctx->ws_x, Bm * S * E * 4); A(ctx->ws_h, Bm * S * E * 2); A(ctx->ws_qkv, Bm * S * 3 * E * 2);
-  A(ctx->ws_g, gbytes); A(ctx->tokens, Bm * P * E * 4); A(ctx->flags, 64 * sizeof(int));
-  A(ctx->ws_corr, 2 * Bm * (F > 3 * E ? F : 3 * E) * 4);      // two rows per image (upper / lower half): encoder.hip GemmArgs::corr
-  A(ctx->ws_abar, 2 * Bm * (F > E ? F : E) * 2);
-  A(ctx->ws_lncnt, (Bm + 4) * 4 + 64);                          // arrival words of the fused LayerNorms, one per image (16-byte multiples per half batch)
-  A(ctx->ws_lnpart, Bm * 4 * 256 * 16);                         // their per-row partial statistics: [image][column tile <= 4][256] entries of 16 bytes
+  A(ctx->tokens, Bm * P * g.E * 4); A(ctx->flags, 64 * sizeof(int));
+  for (int i = 0; i < NUM_WS; ++i) A(ctx->ws[i], ctx->wsp.bytes(i));
   if (e != hipSuccess) return HVLA_E_ARENA_FULL;
-  if (hipMemset(ctx->ws_lncnt.p, 0, ctx->ws_lncnt.bytes) != hipSuccess) return HVLA_E_HIP;
+  if (hipMemset(ctx->ws[WS_LN_CNT].p, 0, ctx->ws[WS_LN_CNT].bytes) != hipSuccess) return HVLA_E_HIP;
   if (c->streams == 2) {
     if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -272,6 +269,43 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   return HVLA_OK;
 }
 
+// What the count argument of a serving entry counts: a batch of the context (and of the arena, if the entry has one), call rows
+// mapped to slots of a pool, or nothing.  `workspace`: the entry runs the context's weights in its max_batch-sized workspace --
+// all but the ensemble entries, which touch the arena alone and ask neither for loaded weights nor for max_batch.
+struct ServeCount {
+  enum Kind { NONE, BATCH, SLOTS } kind;
+  bool workspace;
+  int32_t n;
+  const hvla_weights* w;
+  const int32_t* slots;
+};
+static ServeCount batch_of(int32_t B, const hvla_weights* w = nullptr) { return {ServeCount::BATCH, true, B, w, nullptr}; }
+static ServeCount slots_of(const hvla_weights* w, const int32_t* slots, int32_t K, bool workspace = true) {
+  return {ServeCount::SLOTS, workspace, K, w, slots};
+}
+static ServeCount arena_only() { return {ServeCount::NONE, false, 0, nullptr, nullptr}; }
+
+// The head of every serving entry, in the order each of them used to check by hand: the handles (ctx, and `handles`: the entry's arena
+// or out pointer) -> HVLA_E_STATE, the weights loaded, the count, the entry's other must-not-be-null pointers (`args`), the device.
+// Hands the stream back.
+static int serve_entry(hvla_ctx* ctx, bool handles, const ServeCount& c, bool args, void* stream, hipStream_t& st) {
+  if (!ctx || !handles) return HVLA_E_STATE;
+  if (c.workspace && !ctx->loaded) FAIL(ctx, HVLA_E_STATE, "called before hvla_load_weights");
+  const int32_t Bm = ctx->cfg.max_batch;
+  if (c.kind == ServeCount::BATCH) {
+    if (c.n < 1 || c.n > Bm) FAIL(ctx, HVLA_E_SHAPE, "batch %d outside [1, %d]", c.n, Bm);
+    if (c.w && c.n != c.w->B) FAIL(ctx, HVLA_E_SHAPE, "batch %d != arena batch %d", c.n, c.w->B);
+  } else if (c.kind == ServeCount::SLOTS) {
+    if (!c.slots) FAIL(ctx, HVLA_E_SHAPE, "null slot map");
+    const int32_t cap = c.workspace && Bm < c.w->B ? Bm : c.w->B;
+    if (c.n < 1 || c.n > cap) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d] (a pool of %d slots, max_batch %d)", c.n, cap, c.w->B, Bm);
+  }
+  if (!args) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  st = reinterpret_cast<hipStream_t>(stream);
+  return HVLA_OK;
+}
+
 // an arena of B episodes: one handed back by hvla_weights_free if the ctx holds one of that size, else a new allocation
 static int take_arena(hvla_ctx* ctx, int32_t B, std::unique_ptr<hvla_weights>& w) {
   const PolicyLayout& pl = ctx->lay.pl;
@@ -321,30 +355,36 @@ static int lang_prefix(hvla_ctx* ctx, hvla_weights* w, const float* tok, int K, 
   return HVLA_OK;
 }
 
-int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const float* cls, int32_t B,
-                  hvla_weights** out, void* stream) {
-  if (!ctx || !out) return HVLA_E_STATE;
-  *out = nullptr;
-  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "hvla_generate before hvla_load_weights");
-  if (B < 1 || B > ctx->cfg.max_batch) FAIL(ctx, HVLA_E_SHAPE, "batch %d outside [1, %d]", B, ctx->cfg.max_batch);
-  if (!tok || !mask || !cls) FAIL(ctx, HVLA_E_SHAPE, "null input pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// K tasks through context encoder -> weight generation -> language prefix into arena w.  slots null (hvla_generate): into rows
+// 0 .. K-1, the f32 context rows straight into the arena.  Else (the episode pool) into rows slots[k]: the unchanged context encoder
+// writes workspace rows 0 .. K-1, and pool_assign moves the f32 rows to their slots and zeroes those slots' ensemble counters.
+static int generate_body(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int K, const float* tok, const int64_t* mask,
+                         const float* cls, hipStream_t st) {
   const PolicyLayout& pl = ctx->lay.pl;
   const Geom& g = ctx->g;
+  CtxParams cp = ctx->ctxp;
+  cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
+  cp.ctx = slots ? ctx->ctx_f32.as<float>() : w->ctx.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
+  HIPCHK(ctx, launch_ctx_encoder(cp, K, st));
+  WeightGenParams wp{ctx->wcat_hi.as<__bf16>(), ctx->wcat_lo.as<__bf16>(), ctx->bcat.as<float>(),
+                     ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
+                     w->vf.as<float>(), K, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
+  HIPCHK(ctx, launch_weightgen(wp, g.C, st, slots, w->B));
+  if (slots)
+    HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.C, w->B, st));
+  return lang_prefix(ctx, w, tok, K, slots, st);
+}
+
+int hvla_generate(hvla_ctx* ctx, const float* tok, const int64_t* mask, const float* cls, int32_t B,
+                  hvla_weights** out, void* stream) {
+  if (ctx && out) *out = nullptr;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, out != nullptr, batch_of(B), tok && mask && cls, stream, st)) return r;
   std::unique_ptr<hvla_weights> w;
   if (int r = take_arena(ctx, B, w)) return r;
   HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, st));
   HIPCHK(ctx, hipMemsetAsync(w->slot_count.p, 0, w->slot_count.bytes, st));   // (the arena may have served as an episode pool)
-  CtxParams cp = ctx->ctxp;
-  cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
-  cp.ctx = w->ctx.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
-  HIPCHK(ctx, launch_ctx_encoder(cp, B, st));
-  WeightGenParams wp{ctx->wcat_hi.as<__bf16>(), ctx->wcat_lo.as<__bf16>(), ctx->bcat.as<float>(),
-                     ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
-                     w->vf.as<float>(), B, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
-  HIPCHK(ctx, launch_weightgen(wp, g.C, st));
-  if (int r = lang_prefix(ctx, w.get(), tok, B, nullptr, st)) return r;
+  if (int r = generate_body(ctx, w.get(), nullptr, B, tok, mask, cls, st)) return r;
   *out = w.release();
   return HVLA_OK;
 }
@@ -387,68 +427,47 @@ int hvla_weights_export(hvla_ctx* ctx, const hvla_weights* w, float* theta, floa
   return HVLA_OK;
 }
 
-static int check_step(hvla_ctx* ctx, int32_t B) {
-  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "called before hvla_load_weights");
-  if (B < 1 || B > ctx->cfg.max_batch) FAIL(ctx, HVLA_E_SHAPE, "batch %d outside [1, %d]", B, ctx->cfg.max_batch);
-  return HVLA_OK;
-}
-
-// episodes [b0, b0 + nb) of the batch: every per-episode buffer is offset, the workspace slices are disjoint
-static int encode_range(hvla_ctx* ctx, const uint8_t* images, float* out, int b0, int nb, bool keep_cls, hipStream_t st) {
+// episodes [b0, b0 + nb) of the batch: every per-episode buffer is offset, the workspace slices are those of the context's table
+// (disjoint for the two halves of a two-stream step).  audit (hvla_encode_audit's test instrumentation): the call then runs outside
+// the profiler and the launch count, and exports no attention map.
+static int encode_range(hvla_ctx* ctx, const uint8_t* images, float* out, int b0, int nb, bool keep_cls, hipStream_t st,
+                        uint32_t* audit = nullptr) {
   const Geom& g = ctx->g;
-  const size_t S = g.S(), E = g.E, F = g.enc_mlp, rows = (size_t)b0 * S;
-  // ws_g holds an episode's MLP hidden rows [S][F] and, before that, its im2col rows [P][Kp]: the slices of two concurrent
-  // halves must be disjoint for the larger of the two
-  const size_t gper = S * F > (size_t)g.P() * ctx->Kp ? S * F : (size_t)g.P() * ctx->Kp;
-  EncWorkspace ws{ctx->ws_x.as<float>() + rows * E, static_cast<char*>(ctx->ws_h.p) + rows * E * 2,
-                  static_cast<char*>(ctx->ws_qkv.p) + rows * 3 * E * 2, static_cast<char*>(ctx->ws_g.p) + (size_t)b0 * gper * 2,
-                  ctx->ws_corr.as<float>() + (size_t)2 * b0 * (F > 3 * E ? F : 3 * E),
-                  static_cast<char*>(ctx->ws_abar.p) + (size_t)2 * b0 * (F > E ? F : E) * 2};
-  if (ctx->amap_dino) ws.amap = ctx->amap_dino + (size_t)b0 * g.enc_layers * g.enc_heads * g.P();
-  ws.ln_cnt = ctx->ws_lncnt.as<uint32_t>() + (size_t)((b0 + 3) / 4 * 4);   // (a second half starts on a 16-byte boundary)
-  ws.ln_part = ctx->ws_lnpart.as<float>() + (size_t)b0 * 4 * 256 * 4;
+  auto at = [&](int buf) { return static_cast<char*>(ctx->ws[buf].p) + ctx->wsp.offset(buf, b0); };
+  EncWorkspace ws{reinterpret_cast<float*>(at(WS_X)), at(WS_H), at(WS_QKV), at(WS_G), reinterpret_cast<float*>(at(WS_CORR)), at(WS_ABAR)};
+  if (ctx->amap_dino && !audit) ws.amap = ctx->amap_dino + (size_t)b0 * g.enc_layers * g.enc_heads * g.P();
+  ws.ln_cnt = reinterpret_cast<uint32_t*>(at(WS_LN_CNT));
+  ws.ln_part = reinterpret_cast<float*>(at(WS_LN_PART));
   ws.ln_spin = ctx->ln_spin;
 #ifdef HVLA_BENCH_HOOKS
-  ws.stop_after = ctx->enc_stop;
+  if (!audit) ws.stop_after = ctx->enc_stop;
 #endif
-  const size_t img = (size_t)g.image_size * g.image_size * 3, per = (keep_cls ? S : (size_t)g.P()) * E;
+  const size_t img = (size_t)g.image_size * g.image_size * 3, per = (keep_cls ? (size_t)g.S() : (size_t)g.P()) * g.E;
   HIPCHK(ctx, launch_encoder(g, ctx->cfg.enc_dtype, ctx->encw, ws, images + (size_t)b0 * img, out + (size_t)b0 * per, nb, st,
-                             &ctx->prof, keep_cls));
+                             audit ? nullptr : &ctx->prof, keep_cls, audit));
   return HVLA_OK;
 }
 
 int hvla_encode(hvla_ctx* ctx, const uint8_t* images, float* tokens, int32_t B, void* stream) {
-  if (!ctx) return HVLA_E_STATE;
-  if (int r = check_step(ctx, B)) return r;
-  if (!images || !tokens) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return encode_range(ctx, images, tokens, 0, B, false, reinterpret_cast<hipStream_t>(stream));
+  hipStream_t st;
+  if (int r = serve_entry(ctx, true, batch_of(B), images && tokens, stream, st)) return r;
+  return encode_range(ctx, images, tokens, 0, B, false, st);
 }
 
 int hvla_encode_hidden(hvla_ctx* ctx, const uint8_t* images, float* hidden, int32_t B, void* stream) {
-  if (!ctx) return HVLA_E_STATE;
-  if (int r = check_step(ctx, B)) return r;
-  if (!images || !hidden) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return encode_range(ctx, images, hidden, 0, B, true, reinterpret_cast<hipStream_t>(stream));
+  hipStream_t st;
+  if (int r = serve_entry(ctx, true, batch_of(B), images && hidden, stream, st)) return r;
+  return encode_range(ctx, images, hidden, 0, B, true, st);
 }
 
 // test instrumentation: the encoder with a range audit of every 16-bit MFMA operand it writes (LayerNorm outputs, q / k /
 // v, attention outputs, GELU outputs; all layers).  maxabs f32 [4], nonfinite i32 [4]: HOST pointers.
 int hvla_encode_audit(hvla_ctx* ctx, const uint8_t* images, int32_t B, float* maxabs, int32_t* nonfinite, void* stream) {
-  if (!ctx) return HVLA_E_STATE;
-  if (int r = check_step(ctx, B)) return r;
-  if (!images || !maxabs || !nonfinite) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStream_t st;
+  if (int r = serve_entry(ctx, true, batch_of(B), images && maxabs && nonfinite, stream, st)) return r;
   uint32_t* slots = reinterpret_cast<uint32_t*>(ctx->flags.p);
   HIPCHK(ctx, hipMemsetAsync(slots, 0, 8 * sizeof(uint32_t), st));
-  const Geom& g = ctx->g;
-  const size_t F = g.enc_mlp, E = g.E;
-  EncWorkspace ws{ctx->ws_x.as<float>(), ctx->ws_h.p, ctx->ws_qkv.p, ctx->ws_g.p, ctx->ws_corr.as<float>(), ctx->ws_abar.p};
-  (void)F; (void)E;
-  ws.ln_cnt = ctx->ws_lncnt.as<uint32_t>(); ws.ln_part = ctx->ws_lnpart.as<float>(); ws.ln_spin = ctx->ln_spin;
-  HIPCHK(ctx, launch_encoder(g, ctx->cfg.enc_dtype, ctx->encw, ws, images, ctx->tokens.as<float>(), B, st, nullptr, false, slots));
+  if (int r = encode_range(ctx, images, ctx->tokens.as<float>(), 0, B, false, st, slots)) return r;
   uint32_t h[8];
   HIPCHK(ctx, hipMemcpyAsync(h, slots, sizeof h, hipMemcpyDeviceToHost, st));
   HIPCHK(ctx, hipStreamSynchronize(st));
@@ -475,22 +494,16 @@ static int policy_range(hvla_ctx* ctx, const hvla_weights* w, const float* token
   if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * (g.P() + lang_T);
   ctx->prof.begin(HVLA_PROF_POLICY, st);
   ++ctx->prof.nlaunch;
-  if (slots)
-    HIPCHK(ctx, launch_policy_slots(p, slots + b0, w->B, st, lang_T));
-  else
-    HIPCHK(ctx, launch_policy(p, st, lang_T));
+  HIPCHK(ctx, launch_policy(p, st, lang_T, slots ? slots + b0 : nullptr, w->B));
   ctx->prof.end(HVLA_PROF_POLICY, st);
   return HVLA_OK;
 }
 
 int hvla_policy(hvla_ctx* ctx, const hvla_weights* w, const float* tokens, float* actions, float* logits, int32_t B,
                 void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (int r = check_step(ctx, B)) return r;
-  if (B != w->B) FAIL(ctx, HVLA_E_SHAPE, "batch %d != arena batch %d", B, w->B);
-  if (!tokens || !actions) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  return policy_range(ctx, w, tokens, actions, logits, 0, B, reinterpret_cast<hipStream_t>(stream));
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, batch_of(B, w), tokens && actions, stream, st)) return r;
+  return policy_range(ctx, w, tokens, actions, logits, 0, B, st);
 }
 
 int hvla_set_attention_outputs(hvla_ctx* ctx, float* dino_cls_attention, float* head_attention) {
@@ -500,60 +513,65 @@ int hvla_set_attention_outputs(hvla_ctx* ctx, float* dino_cls_attention, float* 
   return HVLA_OK;
 }
 
-int hvla_step(hvla_ctx* ctx, const hvla_weights* w, const uint8_t* images, float* actions, float* logits, int32_t B,
-              void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (int r = check_step(ctx, B)) return r;
-  if (B != w->B) FAIL(ctx, HVLA_E_SHAPE, "batch %d != arena batch %d", B, w->B);
-  if (!images || !actions) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// One step of n call rows on arena w: its episodes 0 .. n-1 (slots null), or call row b on the weights of arena row slots[b].
+static int step_body(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int n, const uint8_t* images, float* actions,
+                     float* logits, hipStream_t st) {
   float* tokens = ctx->tokens.as<float>();
-  if (!ctx->side || B < 64) {
-    if (int r = encode_range(ctx, images, tokens, 0, B, false, st)) return r;
-    return policy_range(ctx, w, tokens, actions, logits, 0, B, st);
+  if (!ctx->side || n < 64) {
+    if (int r = encode_range(ctx, images, tokens, 0, n, false, st)) return r;
+    return policy_range(ctx, w, tokens, actions, logits, 0, n, st, slots);
   }
   // two halves on two streams: while one half is in an HBM-bound kernel (LayerNorm, a residual epilogue, attention
   // staging) or in the ragged end of a grid, the other half's GEMM has the matrix cores.  Episodes are independent and
   // every kernel is batch-invariant, so the bytes are those of the single-stream step.
-  const int b0 = B / 2;
+  const int b0 = n / 2;
   HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
   HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
   if (int r = encode_range(ctx, images, tokens, 0, b0, false, st)) return r;
-  if (int r = encode_range(ctx, images, tokens, b0, B - b0, false, ctx->side)) return r;
-  if (int r = policy_range(ctx, w, tokens, actions, logits, 0, b0, st)) return r;
-  if (int r = policy_range(ctx, w, tokens, actions, logits, b0, B - b0, ctx->side)) return r;
+  if (int r = encode_range(ctx, images, tokens, b0, n - b0, false, ctx->side)) return r;
+  if (int r = policy_range(ctx, w, tokens, actions, logits, 0, b0, st, slots)) return r;
+  if (int r = policy_range(ctx, w, tokens, actions, logits, b0, n - b0, ctx->side, slots)) return r;
   HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
   HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
   return HVLA_OK;
 }
 
+int hvla_step(hvla_ctx* ctx, const hvla_weights* w, const uint8_t* images, float* actions, float* logits, int32_t B,
+              void* stream) {
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, batch_of(B, w), images && actions, stream, st)) return r;
+  return step_body(ctx, w, nullptr, B, images, actions, logits, st);
+}
+
 int hvla_ensemble_reset(hvla_ctx* ctx, hvla_weights* w, void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, reinterpret_cast<hipStream_t>(stream)));
-  HIPCHK(ctx, hipMemsetAsync(w->slot_count.p, 0, w->slot_count.bytes, reinterpret_cast<hipStream_t>(stream)));
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, arena_only(), true, stream, st)) return r;
+  HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, st));
+  HIPCHK(ctx, hipMemsetAsync(w->slot_count.p, 0, w->slot_count.bytes, st));
+  return HVLA_OK;
+}
+
+// slots null: the arena's B episodes on its one counter; else K call rows on the counters of their slots
+static int ensemble_body(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int K, const float* actions, const float* mean,
+                         const float* std, const uint8_t* mask, float* out, hipStream_t st) {
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_ensemble(actions, w->ring.as<float>(), slots ? w->slot_count.as<int>() : w->count.as<int>(), mean, std, mask, out,
+                              w->B, ctx->g.horizon, ctx->g.action_dim, st, slots, K));
   return HVLA_OK;
 }
 
 int hvla_ensemble(hvla_ctx* ctx, hvla_weights* w, const float* actions, const float* mean, const float* std,
                   const uint8_t* mask, float* out, void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (!actions || !mean || !std || !mask || !out) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  ++ctx->prof.nlaunch;
-  HIPCHK(ctx, launch_ensemble(actions, w->ring.as<float>(), w->count.as<int>(), mean, std, mask, out, w->B,
-                              ctx->g.horizon, ctx->g.action_dim, reinterpret_cast<hipStream_t>(stream)));
-  return HVLA_OK;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, arena_only(), actions && mean && std && mask && out, stream, st)) return r;
+  return ensemble_body(ctx, w, nullptr, 0, actions, mean, std, mask, out, st);
 }
 
 // ------------------------------------------------------------------ episode pool (include/hvla.h)
 int hvla_weights_alloc(hvla_ctx* ctx, int32_t B, hvla_weights** out, void* stream) {
-  if (!ctx || !out) return HVLA_E_STATE;
-  *out = nullptr;
-  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "hvla_weights_alloc before hvla_load_weights");
-  if (B < 1 || B > ctx->cfg.max_batch) FAIL(ctx, HVLA_E_SHAPE, "pool of %d slots outside [1, %d]", B, ctx->cfg.max_batch);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (ctx && out) *out = nullptr;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, out != nullptr, batch_of(B), true, stream, st)) return r;
   std::unique_ptr<hvla_weights> w;
   if (int r = take_arena(ctx, B, w)) return r;
   // empty slots: zero weights step to finite actions, zero counters start a fresh ensemble
@@ -563,71 +581,25 @@ int hvla_weights_alloc(hvla_ctx* ctx, int32_t B, hvla_weights** out, void* strea
   return HVLA_OK;
 }
 
-static int check_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K) {
-  if (!ctx->loaded) FAIL(ctx, HVLA_E_STATE, "called before hvla_load_weights");
-  if (!slots) FAIL(ctx, HVLA_E_SHAPE, "null slot map");
-  if (K < 1 || K > w->B || K > ctx->cfg.max_batch)
-    FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, min(%d slots of the pool, max_batch %d)]", K, w->B, ctx->cfg.max_batch);
-  return HVLA_OK;
-}
-
 int hvla_generate_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* tok, const int64_t* mask,
                         const float* cls, void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (int r = check_slots(ctx, w, slots, K)) return r;
-  if (!tok || !mask || !cls) FAIL(ctx, HVLA_E_SHAPE, "null input pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const PolicyLayout& pl = ctx->lay.pl;
-  const Geom& g = ctx->g;
-  // the K tasks through the unchanged context encoder into workspace rows 0 .. K-1, then into their slots
-  CtxParams cp = ctx->ctxp;
-  cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
-  cp.ctx = ctx->ctx_f32.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
-  HIPCHK(ctx, launch_ctx_encoder(cp, K, st));
-  WeightGenParams wp{ctx->wcat_hi.as<__bf16>(), ctx->wcat_lo.as<__bf16>(), ctx->bcat.as<float>(),
-                     ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
-                     w->vf.as<float>(), K, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
-  HIPCHK(ctx, launch_weightgen_slots(wp, g.C, slots, w->B, st));
-  HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.C, w->B, st));
-  return lang_prefix(ctx, w, tok, K, slots, st);
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, slots_of(w, slots, K), tok && mask && cls, stream, st)) return r;
+  return generate_body(ctx, w, slots, K, tok, mask, cls, st);
 }
 
 int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, int32_t K, const uint8_t* images, float* actions,
                     float* logits, void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (int r = check_slots(ctx, w, slots, K)) return r;
-  if (!images || !actions) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float* tokens = ctx->tokens.as<float>();
-  if (!ctx->side || K < 64) {
-    if (int r = encode_range(ctx, images, tokens, 0, K, false, st)) return r;
-    return policy_range(ctx, w, tokens, actions, logits, 0, K, st, slots);
-  }
-  const int b0 = K / 2;                                         // the two-stream form of hvla_step
-  HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));
-  HIPCHK(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-  if (int r = encode_range(ctx, images, tokens, 0, b0, false, st)) return r;
-  if (int r = encode_range(ctx, images, tokens, b0, K - b0, false, ctx->side)) return r;
-  if (int r = policy_range(ctx, w, tokens, actions, logits, 0, b0, st, slots)) return r;
-  if (int r = policy_range(ctx, w, tokens, actions, logits, b0, K - b0, ctx->side, slots)) return r;
-  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->side));
-  HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
-  return HVLA_OK;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, slots_of(w, slots, K), images && actions, stream, st)) return r;
+  return step_body(ctx, w, slots, K, images, actions, logits, st);
 }
 
 int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* actions, const float* mean,
                         const float* std, const uint8_t* mask, float* out, void* stream) {
-  if (!ctx || !w) return HVLA_E_STATE;
-  if (!slots) FAIL(ctx, HVLA_E_SHAPE, "null slot map");
-  if (K < 1 || K > w->B) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d]", K, w->B);
-  if (!actions || !mean || !std || !mask || !out) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  ++ctx->prof.nlaunch;
-  HIPCHK(ctx, launch_ensemble_slots(actions, w->ring.as<float>(), w->slot_count.as<int>(), slots, K, mean, std, mask, out, w->B,
-                                    ctx->g.horizon, ctx->g.action_dim, reinterpret_cast<hipStream_t>(stream)));
-  return HVLA_OK;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, slots_of(w, slots, K, false), actions && mean && std && mask && out, stream, st)) return r;
+  return ensemble_body(ctx, w, slots, K, actions, mean, std, mask, out, st);
 }
 
 // ------------------------------------------------------------------ post-processing of pool slots (include/hvla.h)
@@ -1092,8 +1064,8 @@ int hvla_profile_read(hvla_ctx* ctx, float* ms, int32_t* launches) {
 int hvla_debug_gemm(hvla_ctx* ctx, int M, int N, int K, int epi, int variant, int iters, float* ms) {
   if (!ctx || !ctx->loaded) return HVLA_E_STATE;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const void* A = K > ctx->g.E ? ctx->ws_g.p : ctx->ws_h.p;
-  void* out = epi == 3 ? ctx->ws_x.p : (epi == 1 ? ctx->ws_qkv.p : ctx->ws_g.p);
+  const void* A = ctx->ws[K > ctx->g.E ? WS_G : WS_H].p;
+  void* out = ctx->ws[epi == 3 ? WS_X : (epi == 1 ? WS_QKV : WS_G)].p;
   if (epi == 2 && K > ctx->g.E) return HVLA_E_SHAPE;
   const EncLayerW& L = ctx->encw.layer[0];
   const void* W = epi == 1 ? L.wqkv : (epi == 2 ? L.w1 : (K > ctx->g.E ? L.w2 : L.wo));
@@ -1162,7 +1134,7 @@ int hvla_debug_attention_stamps(hvla_ctx* ctx, int32_t B, const int32_t* wgs, in
   for (int i = 0; i < nwg; ++i) {
     HIPCHK(ctx, hipMemset(st.p, 0, 64));
     for (int rep = 0; rep < 2; ++rep)
-      HIPCHK(ctx, debug_attention_stamps(ctx->ws_qkv.p, ctx->ws_h.p, ctx->ws_abar.p, B, g.S(), g.E, g.enc_heads, wgs[i], st.as<unsigned long long>(), nullptr));
+      HIPCHK(ctx, debug_attention_stamps(ctx->ws[WS_QKV].p, ctx->ws[WS_H].p, ctx->ws[WS_ABAR].p, B, g.S(), g.E, g.enc_heads, wgs[i], st.as<unsigned long long>(), nullptr));
     HIPCHK(ctx, hipDeviceSynchronize());
     HIPCHK(ctx, hipMemcpy(out + (size_t)i * 8, st.p, 64, hipMemcpyDeviceToHost));
   }
@@ -1197,13 +1169,13 @@ int hvla_debug_train_gemm_exact(int on) {
 // shader-clock stamps of the last context-encoder launch (workgroup 0): see hypernet.hip CTX_STAMP
 int hvla_debug_ctx_stamps(unsigned long long* out) { return debug_ctx_stamps(out) == hipSuccess ? HVLA_OK : HVLA_E_HIP; }
 // device pointer and size of one encoder workspace buffer (tools/ read intermediates back with hipMemcpy):
-// 0 x (f32 residual stream), 1 h (16-bit LayerNorm / attention output), 2 qkv, 3 g (MLP hidden), 4 corr, 5 abar, 6 ln_cnt, 7 ln_part
+// `which` is plan.h's WsBuf: 0 x (f32 residual stream), 1 h (16-bit LayerNorm / attention output), 2 qkv, 3 g (MLP hidden), 4 corr,
+// 5 abar, 6 ln_cnt, 7 ln_part
 int hvla_debug_workspace(hvla_ctx* ctx, int which, void** ptr, size_t* bytes) {
   if (!ctx || !ptr || !bytes) return HVLA_E_STATE;
-  DevBuf* b[8] = {&ctx->ws_x, &ctx->ws_h, &ctx->ws_qkv, &ctx->ws_g, &ctx->ws_corr, &ctx->ws_abar, &ctx->ws_lncnt, &ctx->ws_lnpart};
-  if (which < 0 || which > 7) return HVLA_E_SHAPE;
-  *ptr = b[which]->p;
-  *bytes = b[which]->bytes;
+  if (which < 0 || which >= NUM_WS) return HVLA_E_SHAPE;
+  *ptr = ctx->ws[which].p;
+  *bytes = ctx->ws[which].bytes;
   return HVLA_OK;
 }
 int hvla_debug_lnx_stats(hvla_ctx* ctx, unsigned long long* out, int reset) {

@@ -459,29 +459,20 @@ hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st) {
+// slot null: weightgen_kernel (output row r); else weightgen_slots_kernel (arena row slot[r] of `rows`).  KS = C / 16.
+// (two tables, not a template per KS: the compiler emits the six instantiations in the order they are first named, and this one
+// keeps the code object as it was)
+hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st, const int32_t* slot, int rows) {
+  static void (*const plain[3])(WeightGenParams) = {weightgen_kernel<8>, weightgen_kernel<4>, weightgen_kernel<2>};
+  static void (*const pooled[3])(WeightGenParams, const int32_t*, int) = {weightgen_slots_kernel<8>, weightgen_slots_kernel<4>,
+                                                                           weightgen_slots_kernel<2>};
+  const int k = C == 128 ? 0 : C == 64 ? 1 : C == 32 ? 2 : -1;
+  if (k < 0) return hipErrorInvalidValue;
   const int blocks = (p.ntiles + 3) / 4;
-  if (C == 128)
-    hipLaunchKernelGGL(weightgen_kernel<8>, dim3(blocks), dim3(256), 0, st, p);
-  else if (C == 64)
-    hipLaunchKernelGGL(weightgen_kernel<4>, dim3(blocks), dim3(256), 0, st, p);
-  else if (C == 32)
-    hipLaunchKernelGGL(weightgen_kernel<2>, dim3(blocks), dim3(256), 0, st, p);
+  if (slot)
+    hipLaunchKernelGGL(pooled[k], dim3(blocks), dim3(256), 0, st, p, slot, rows);
   else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-hipError_t launch_weightgen_slots(const WeightGenParams& p, int C, const int32_t* slot, int rows, hipStream_t st) {
-  const int blocks = (p.ntiles + 3) / 4;
-  if (C == 128)
-    hipLaunchKernelGGL(weightgen_slots_kernel<8>, dim3(blocks), dim3(256), 0, st, p, slot, rows);
-  else if (C == 64)
-    hipLaunchKernelGGL(weightgen_slots_kernel<4>, dim3(blocks), dim3(256), 0, st, p, slot, rows);
-  else if (C == 32)
-    hipLaunchKernelGGL(weightgen_slots_kernel<2>, dim3(blocks), dim3(256), 0, st, p, slot, rows);
-  else
-    return hipErrorInvalidValue;
+    hipLaunchKernelGGL(plain[k], dim3(blocks), dim3(256), 0, st, p);
   return hipGetLastError();
 }
 

@@ -36,11 +36,10 @@ struct WeightGenParams {
 };
 hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st);
 // (ctx_encoder_lds_bytes, the dynamic LDS of ctx_encoder_kernel for a geometry -- <= 160 KiB or refused at create -- is accept.h's)
-hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st);
-// episode pool: weightgen_kernel's output row of input episode r is arena row slot[r] of an arena of `rows`;
-// launch_pool_assign puts the K new context rows (f32 workspace rows 0 .. K-1) at arena rows slot[k] and zeroes those rows'
+// episode pool, `slot` not null: weightgen_kernel's output row of input episode r is arena row slot[r] of an arena of
+// `rows`; launch_pool_assign puts the K new context rows (f32 workspace rows 0 .. K-1) at arena rows slot[k] and zeroes those rows'
 // ensemble counters.  Slot entries outside [0, rows) are skipped by both.
-hipError_t launch_weightgen_slots(const WeightGenParams& p, int C, const int32_t* slot, int rows, hipStream_t st);
+hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st, const int32_t* slot = nullptr, int rows = 0);
 hipError_t launch_pool_assign(const float* ctx_rows, float* ctx, int* count, const int32_t* slot, int K, int C, int rows,
                               hipStream_t st);
 hipError_t launch_export_theta(const __bf16* wh, const __bf16* wl, const float* vf, const int32_t* perm,
@@ -140,10 +139,9 @@ struct PolicyParams {
 };
 // lang_T > 0: use_language_token (policy_kernel_lang): the arena rows hold the language prefix lang_prefix_kernel
 // wrote (LangLayout::m_lkv), lang_T is the number of language tokens; p.amap is then [B, L, heads, lang_T + P]
-hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0);
-// episode pool: workgroup b takes its weights from arena row slots[b] (p.wh / wl / vf point at row 0 of an arena of `rows`
-// episodes); tokens, actions, logits and attention rows stay call rows.  Entries outside [0, rows) are skipped.
-hipError_t launch_policy_slots(const PolicyParams& p, const int32_t* slots, int rows, hipStream_t st, int lang_T = 0);
+// episode pool, `slots` not null: workgroup b takes its weights from arena row slots[b] (p.wh / wl / vf point at row 0 of an arena of
+// `rows` episodes); tokens, actions, logits and attention rows stay call rows.  Entries outside [0, rows) are skipped.
+hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0, const int32_t* slots = nullptr, int rows = 0);
 // use_language_token: the language tokens of K episodes through the policy once (lang_prefix_kernel): K / V of every layer into
 // the episodes' arena rows (LangLayout::m_lkv)
 struct LangPrefixParams {
@@ -158,14 +156,9 @@ struct LangPrefixParams {
 hipError_t launch_lang_prefix(const LangPrefixParams& p, int K, hipStream_t st);
 
 // ---------------------------------------------------------------- caller-side device helpers
-hipError_t launch_ensemble(const float* actions, float* ring, int* count, const float* mean,
-                           const float* std, const uint8_t* mask, float* out, int B, int horizon,
-                           int action_dim, hipStream_t st);
-
-// episode pool: count [B] one counter per arena row; call row k is arena row slots[k]
-hipError_t launch_ensemble_slots(const float* actions, float* ring, int* count, const int32_t* slots, int K, const float* mean,
-                                 const float* std, const uint8_t* mask, float* out, int B, int horizon, int action_dim,
-                                 hipStream_t st);
+// episode pool, `slots` not null: count [B] one counter per arena row; call row k of K is arena row slots[k].  Else count [1], B call rows.
+hipError_t launch_ensemble(const float* actions, float* ring, int* count, const float* mean, const float* std, const uint8_t* mask,
+                           float* out, int B, int horizon, int action_dim, hipStream_t st, const int32_t* slots = nullptr, int K = 0);
 
 // episode pool post-processing (postprocess.hip, include/hvla.h hvla_post_*): the caller-side state of one slot's episode
 // (InferenceWrapper's ensemble counter and gripper fields), next to a ring of its last `horizon` un-normalised predictions

@@ -111,13 +111,23 @@ struct EncSizes {                  // what an encoder call is decided from
 };
 HVLA_HD int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// What the fused LayerNorms keep in the workspace, sized by the limits above: an image has at most LNX_MAX_E / HBN_ column tiles,
+// a tile leaves one 16-byte entry {sum, tag, sum of squares, tag} per row, every image has one 4-byte arrival word, and the words
+// of a call are cleared (and a half batch's words begin) in multiples of 16 bytes.
+constexpr int LNX_MAX_E = 1024;                          // can_fuse_ln's width limit
+constexpr int LNX_TILES = LNX_MAX_E / HBN_;              // column tiles per image the workspace has room for
+constexpr int LNX_ENTRY_BYTES = 16, LNX_CNT_ALIGN = 16;
+static_assert(LNX_TILES == 4 && LNX_MAX_E % HBN_ == 0, "");
+inline size_t lnx_cnt_bytes(int nb) { return ((size_t)nb * sizeof(uint32_t) + LNX_CNT_ALIGN - 1) / LNX_CNT_ALIGN * LNX_CNT_ALIGN; }
+inline size_t lnx_part_bytes(int nb, int E) { return (size_t)nb * ((E + HBN_ - 1) / HBN_) * HBM_ * LNX_ENTRY_BYTES; }
+
 // small batch: does the GEMM [M][K] x [N][K] run as gemm64c_kernel (bias rows computed inside)?
 // (S >= 9: a block's 64 rows then belong to at most 8 images = the 16 rows of the kernels' bias-row tile)
 inline bool small_fused(const EncSizes& z, int N, int K) {
   return z.comp && z.M() <= G64_MAXM && (size_t)z.M() * K < (1ull << 31) && (size_t)N * K < (1ull << 31) && N % SBN == 0 && K % 64 == 0 && z.S >= 9;
 }
 // may a residual / patch GEMM on image-aligned tiles run the LayerNorm behind it inside its epilogue (LNX)?
-inline bool can_fuse_ln(const EncSizes& z) { return z.ln_ws && (size_t)z.M() * z.E * 4 < (1ull << 32) && z.E <= 1024; }
+inline bool can_fuse_ln(const EncSizes& z) { return z.ln_ws && (size_t)z.M() * z.E * 4 < (1ull << 32) && z.E <= LNX_MAX_E; }
 // the persistent form of an LNX launch keeps the nbn column tiles of an image in one round (tile_origin_x): the counts must divide
 inline bool lnx_persistent(int ncu, int nbm, int nbn) {
   const int nt = nbm * nbn;
@@ -265,8 +275,8 @@ inline CallPlan plan_call(const EncSizes& z) {
   if (!c.ok) return c;
   c.Kp = 2 * ((z.patch * z.patch * 3 + 63) / 64 * 64);
   if (can_fuse_ln(z) && z.P == HBM_ && M > G64_MAXM) {
-    c.cnt_bytes = (size_t)((z.B * 4 + 15) / 16 * 16);
-    c.part_bytes = (size_t)z.B * ceil_div(z.E, HBN_) * 256 * 16;
+    c.cnt_bytes = lnx_cnt_bytes(z.B);
+    c.part_bytes = lnx_part_bytes(z.B, z.E);
   }
   const size_t chunks = ((size_t)z.B * z.P * (c.Kp / 16) + 255) / 256;
   c.im2col = Launch{IM2COL, (unsigned)(chunks > 8192 ? 8192 : chunks), 1, 256, 0, 0};
@@ -275,5 +285,31 @@ inline CallPlan plan_call(const EncSizes& z) {
   c.final_norm = Launch{LN_FINAL, (unsigned)ceil_div(M, 4), 1, 256, 0, 1};
   return c;
 }
+
+// ------------------------------------------------------------------------------------------------ the workspace
+// The eight buffers an encoder call works in (EncWorkspace, kernels.h), ONCE: how large each is for a context of max_batch episodes
+// and where the slice of the episodes from b0 on begins.  hvla_create allocates by it and encode_range cuts by it, so the slices of
+// the two halves of a two-stream step are disjoint, and each holds what run_encoder touches for its episodes, wherever the CPU test
+// says so (plan_check.cpp: a sweep against the sizes and offsets recorded from the expressions this replaced).
+enum WsBuf : int { WS_X, WS_H, WS_QKV, WS_G, WS_CORR, WS_ABAR, WS_LN_CNT, WS_LN_PART, NUM_WS };
+struct WorkspacePlan {
+  size_t max_batch = 0;
+  size_t per[NUM_WS] = {};         // bytes per episode (ln_cnt: its 4-byte word; slices of it begin on LNX_CNT_ALIGN)
+  WorkspacePlan() = default;
+  WorkspacePlan(int P, int S, int E, int F, int Kp, int max_batch_) : max_batch((size_t)max_batch_) {
+    const size_t s = (size_t)S, e = (size_t)E, f = (size_t)F, elem = 2, im2col = (size_t)P * Kp;   // (16-bit operands of either dtype)
+    per[WS_X] = s * e * sizeof(float);                        // [S][E] f32 residual stream
+    per[WS_H] = s * e * elem;                                 // [S][E]
+    per[WS_QKV] = s * 3 * e * elem;                           // [S][3E]
+    per[WS_G] = (s * f > im2col ? s * f : im2col) * elem;     // the MLP hidden rows [S][F] and, before them, the im2col rows [P][Kp]
+    per[WS_CORR] = 2 * (f > 3 * e ? f : 3 * e) * sizeof(float);   // two bias rows per image (upper / lower half) of the widest GEMM
+    per[WS_ABAR] = 2 * (f > e ? f : e) * elem;                // two mean rows per image of the widest activation operand
+    per[WS_LN_CNT] = sizeof(uint32_t);
+    per[WS_LN_PART] = (size_t)LNX_TILES * HBM_ * LNX_ENTRY_BYTES;
+  }
+  // (ln_cnt: each half of a two-stream step clears a multiple of LNX_CNT_ALIGN bytes from an aligned start, and 64 bytes to spare)
+  size_t bytes(int buf) const { return buf == WS_LN_CNT ? (max_batch + 4) * per[buf] + 64 : max_batch * per[buf]; }
+  size_t offset(int buf, int b0) const { return buf == WS_LN_CNT ? lnx_cnt_bytes(b0) : (size_t)b0 * per[buf]; }
+};
 
 }  // namespace hvla

@@ -1,6 +1,7 @@
 // CPU-only check of csrc/plan.h (the launch plan of run_encoder and the XCD tile order of the small GEMM kernels).  Built and run
 // by tests/test_host_sanitizers.py with g++ -fsanitize=address,undefined; argv[1] = tests/native/encoder_plan_trace.txt, the
-// launches of the dispatch that plan.h replaced (recorded on the CPU from run_encoder with its launch macro turned into a logger).
+// launches of the dispatch that plan.h replaced (recorded on the CPU from run_encoder with its launch macro turned into a logger);
+// argv[2] = tests/native/encoder_workspace_trace.txt, the workspace sizes and slice offsets of the expressions WorkspacePlan replaced.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -125,6 +126,41 @@ static bool lnx_covers(const GemmPlan& p, int ncu) {
   return true;
 }
 
+// ---- the encoder workspace (WorkspacePlan): what run_encoder touches in buffer `buf` for nb images, in bytes from the slice's start
+static size_t ws_touched(const Geo& g, int buf, int nb) {
+  const EncSizes z = sizes(g, nb, 2);
+  const CallPlan c = plan_call(z);
+  const size_t n = (size_t)nb, S = (size_t)z.S, E = (size_t)z.E, F = (size_t)z.F, im2col = (size_t)z.P * c.Kp;
+  switch (buf) {
+    case WS_X: return n * S * E * 4;
+    case WS_H: return n * S * E * 2;
+    case WS_QKV: return n * S * 3 * E * 2;
+    case WS_G: return n * (im2col > S * F ? im2col : S * F) * 2;        // P * Kp im2col elements, then S * F hidden elements
+    case WS_CORR: return n * 2 * (3 * E > F ? 3 * E : F) * 4;
+    case WS_ABAR: return n * 2 * (E > F ? E : F) * 2;
+    case WS_LN_CNT: return c.cnt_bytes > lnx_cnt_bytes(nb) ? c.cnt_bytes : lnx_cnt_bytes(nb);   // (cleared at B >= 8 only: held at every nb)
+    default: return c.part_bytes > lnx_part_bytes(nb, z.E) ? c.part_bytes : lnx_part_bytes(nb, z.E);
+  }
+}
+// the halves [0, b0) and [b0, B) of a step in a context of w.max_batch >= B episodes: every slice starts on 16 bytes, the first ends
+// before the second begins, the second inside the allocation.  Returns the first buffer that fails, -1 when all hold.
+static int ws_halves_fail(const WorkspacePlan& w, const Geo& g, int B, int b0) {
+  for (int buf = 0; buf < NUM_WS; ++buf) {
+    if (w.offset(buf, 0) != 0 || w.offset(buf, b0) % 16 != 0) return buf;
+    if (b0 > 0 && ws_touched(g, buf, b0) > w.offset(buf, b0)) return buf;
+    if (B > b0 && w.offset(buf, b0) + ws_touched(g, buf, B - b0) > w.bytes(buf)) return buf;
+  }
+  return -1;
+}
+static bool read_file(const char* path, std::string& into) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  char buf[65536];
+  for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) into.append(buf, k);
+  fclose(f);
+  return true;
+}
+
 int main(int argc, char** argv) {
   // xcd_run: a bijection of [0, nwg) for every grid size, XCD x (= block id % 8) owning ONE contiguous run of tile indices
   for (int nwg = 1; nwg <= 4100; ++nwg) {
@@ -231,13 +267,7 @@ int main(int argc, char** argv) {
   }
   // ---- the sweep: every planned LDS size within the limit, every kernel id inside its table, and the launches those of the recorded trace
   std::string want;
-  if (argc > 1) {
-    FILE* f = fopen(argv[1], "rb");
-    REQUIRE(f != nullptr, "cannot open %s", argv[1]);
-    char buf[65536];
-    for (size_t k; (k = fread(buf, 1, sizeof buf, f)) > 0;) want.append(buf, k);
-    fclose(f);
-  }
+  if (argc > 1) REQUIRE(read_file(argv[1], want), "cannot open %s", argv[1]);
   const Geo geos[4] = {README, DINOV2S, {"mid", 112, 14, 128, 512, 2}, {"wide64", 112, 14, 768, 3072, 12}};
   const int Bs[14] = {1, 2, 4, 7, 8, 9, 64, 255, 256, 257, 1024, 2048, 2720, 2721};
   size_t at = 0;
@@ -260,6 +290,45 @@ int main(int argc, char** argv) {
             }
           }
   REQUIRE(argc > 1 && at == want.size() && at > 0, "usage: plan_check encoder_plan_trace.txt (%zu of %zu bytes matched)", at, want.size());
+  // ---- the encoder workspace: sizes and slice offsets are those recorded from the expressions WorkspacePlan replaced (argv[2]: the
+  // allocations of hvla_create, the slices of encode_range), and over the same sweep the halves of a two-stream step are disjoint,
+  // aligned and inside the allocation for everything run_encoder touches
+  std::string ws_want, ws_got;
+  REQUIRE(argc > 2 && read_file(argv[2], ws_want), "usage: plan_check encoder_plan_trace.txt encoder_workspace_trace.txt");
+  const Geo ws_geos[5] = {{"tiny", 56, 14, 32, 64, 2}, geos[2], README, DINOV2S, {"e1024", 224, 14, 1024, 4096, 16}};
+  const int max_batches[9] = {1, 2, 5, 63, 64, 65, 96, 256, 1024};
+  for (const Geo& g : ws_geos)
+    for (int max_batch : max_batches) {
+      const EncSizes z = sizes(g, 1, 2);
+      const int Kp = plan_call(z).Kp;
+      const WorkspacePlan w(z.P, z.S, z.E, z.F, Kp, max_batch);
+      char line[256];
+      int k = snprintf(line, sizeof line, "# %s max_batch %d\nalloc", g.name, max_batch);
+      for (int buf = 0; buf < NUM_WS; ++buf) k += snprintf(line + k, sizeof line - k, " %zu", w.bytes(buf));
+      ws_got += line;
+      ws_got += '\n';
+      const int Bs2[7] = {0, 64, 65, 66, 67, 96, max_batch};
+      for (int i = 0; i < 7; ++i) {
+        const int B = Bs2[i], b0 = B / 2;
+        if (B > max_batch || (i == 6 && (B == 96 || (B >= 64 && B <= 67)))) continue;
+        k = snprintf(line, sizeof line, "B %d b0 %d:", B, b0);
+        for (int buf = 0; buf < NUM_WS; ++buf) k += snprintf(line + k, sizeof line - k, " %zu", w.offset(buf, b0));
+        ws_got += line;
+        ws_got += '\n';
+        const int fail = ws_halves_fail(w, g, B, b0);
+        REQUIRE(fail < 0, "%s, max_batch %d, halves [0, %d) and [%d, %d): buffer %d", g.name, max_batch, b0, b0, B, fail);
+        // the whole context as one call, too
+        REQUIRE(ws_halves_fail(w, g, max_batch, 0) < 0, "%s: %d episodes do not fit their own allocation", g.name, max_batch);
+        // the slices of g were once cut by S * F alone: at MID (P * Kp = 81920 > S * F = 33280) the first half's im2col rows then
+        // ran into the second half's (tests/test_gpu_parity.py::test_two_stream_step_with_a_narrow_mlp) -- this check refuses that cut
+        if (!strcmp(g.name, "mid") && b0 > 0) {
+          WorkspacePlan narrow = w;
+          narrow.per[WS_G] = (size_t)z.S * z.F * 2;
+          REQUIRE(ws_halves_fail(narrow, g, B, b0) == WS_G, "mid, halves at %d: g cut by S * F alone passes", b0);
+        }
+      }
+    }
+  REQUIRE(ws_got == ws_want, "the workspace table (%zu bytes) is not the recorded one (%zu bytes):\n%s", ws_got.size(), ws_want.size(), ws_got.c_str());
   printf("OK\n");
   return 0;
 }

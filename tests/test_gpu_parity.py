@@ -1103,7 +1103,7 @@ def test_launches_per_step_are_those_of_the_launch_plan(full):
     the CPU: 99 / 123 / 113) plus the policy's one launch, in each of the three regimes: B = 1 (every small-batch form, the
     LayerNorm's partials folded into its consumer), B = 4 (small batch, mean rows by their own launch) and B = 8 (image-aligned
     tiles, fused LayerNorms, the two memsets).  100 and 124 are the recorded values of profiles/r6_bench_b1.json / r6_bench_b4.json,
-    114 that of r6_bench_b256.json / r6_bench_b1024.json."""
+    114 that of r6_bench_b256.json / r6_bench_b1024.json.  The pooled step of 8 slots enqueues the 114 of the batch step."""
     from hypervla import synthetic as syn
     m, g = full["model"], full["g"]
     for B, want in ((1, 100), (4, 124), (8, 114)):
@@ -1112,6 +1112,12 @@ def test_launches_per_step_are_those_of_the_launch_plan(full):
         m._ctx.launches()                                   # (reads and clears the count)
         m.sample_actions(syn.synthetic_images(B, g), ins, tasks, np.ones((B, 1)), w)
         assert m._ctx.launches() == want, B
+    # an 8-slot pool stepped through its slot map (hvla_step_slots) enqueues what the batch step of 8 episodes does
+    pool = m.create_pool(8)
+    m.assign_tasks(pool, list(range(8)), ins, st)
+    m._ctx.launches()
+    m.sample_actions(syn.synthetic_images(8, g), None, None, None, pool, slots=list(range(8)))
+    assert m._ctx.launches() == 114, "pooled"
 
 
 def _encode_in_a_fresh_process(code, flavour=None):

@@ -42,14 +42,19 @@ def test_launch_plan_arithmetic_under_asan_ubsan(tmp_path):
     stores carry 32-bit BYTE offsets, is only chosen for outputs below 4 GiB (fc1 from B = 2721 on would wrap).  The
     launch plan of an encoder call: the launch counts the committed profiles record, the boundaries between its forms, and, launch
     for launch over a sweep of geometries, batches and CU counts, the trace recorded from the dispatch it replaced.  The three (width,
-    batch) pairs at which tests/test_gpu_geometry_contract.py runs the persistent fused LayerNorm take those kernels on 256 CUs."""
+    batch) pairs at which tests/test_gpu_geometry_contract.py runs the persistent fused LayerNorm take those kernels on 256 CUs.
+    The encoder workspace table (WorkspacePlan): byte for byte the allocation sizes and slice offsets recorded from the expressions it
+    replaced, over five geometries, nine context sizes and the half points of a two-stream step; there every slice starts on 16
+    bytes, the two halves are disjoint and inside the allocation for everything run_encoder touches, and the cut of `g` by S * F
+    alone, which once let two streams share rows at the MID geometry, fails the check."""
     exe = tmp_path / "plan_check"
     build = subprocess.run(
         ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra",
          "-Werror", "-I", os.path.join(ROOT, "hyper-vla_amd", "csrc"), os.path.join(ROOT, "tests", "native", "plan_check.cpp"),
          "-o", str(exe)], capture_output=True, text=True)
     assert build.returncode == 0, build.stderr
-    run = subprocess.run([str(exe), os.path.join(ROOT, "tests", "native", "encoder_plan_trace.txt")], capture_output=True, text=True, timeout=600)
+    run = subprocess.run([str(exe), os.path.join(ROOT, "tests", "native", "encoder_plan_trace.txt"),
+                          os.path.join(ROOT, "tests", "native", "encoder_workspace_trace.txt")], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0 and run.stdout.strip().endswith("OK"), run.stdout + run.stderr
     assert "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stderr
 
