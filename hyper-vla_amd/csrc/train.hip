@@ -1182,7 +1182,7 @@ __global__ void adamw_frozen_kernel(float* __restrict__ p, const float* __restri
 // host sequencing
 // ------------------------------------------------------------------------------------------------
 // The launch seam: everything train_step / train_apply / train_accumulate enqueue goes through KL, ENQ or bgemm().  Under
-// HVLA_TRAIN_TRACE (tools/train_launch_trace.cpp; neither library sets it) the three print one line per operation and enqueue
+// HVLA_TRAIN_TRACE (the two tools/train_*_trace.hip drivers; neither library sets it) the three print one line per operation and enqueue
 // nothing: tests/native/train_step_trace.txt pins what a step launches, argument for argument.
 #ifdef HVLA_TRAIN_TRACE
 #include "../../tools/train_launch_trace.h"
@@ -1395,11 +1395,18 @@ struct Plan {
   BlkTmp t;
   float *cmean, *crstd, *ctx, *dctx, *ctxn, *dxrow, *emean, *erstd;
   long used;
+#ifdef HVLA_TRAIN_TRACE
+  std::vector<std::pair<long, long>> taken;      // (offset, floats asked for) of every take(), in order: train_trace_plan prints them
+#endif
 };
 static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
   Plan pl;
   float* ws = base;
+#ifdef HVLA_TRAIN_TRACE
+  auto take = [&](long n) { float* p = ws; ws += (n + 3) / 4 * 4; pl.taken.push_back({p - base, n}); return p; };
+#else
   auto take = [&](long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
+#endif
   auto take_blk = [&](long nb, long s, long d, long h, long f, bool ls) {
     BlkBuf b; b.x_in = take(nb * s * d); b.mean0 = take(nb * s); b.rstd0 = take(nb * s); b.k = take(nb * s * d); b.q = take(nb * s * d);      // k, q, v: the order of the weight leaves (block_fwd batches the three)
     b.v = take(nb * s * d); b.p = take(nb * h * s * ((s + 3) & ~3L)); b.o = take(nb * s * d); b.x_mid = take(nb * s * d); b.mean1 = take(nb * s);
@@ -1423,10 +1430,13 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
     pl.patches = take((long)B * g.P() * g.patch * g.patch * 3);
     pl.emean = take(B * Se); pl.erstd = take(B * Se);
   }
-  // temporaries are used by one transformer at a time: size them for the largest
+  // temporaries are used by one transformer at a time: size them for the largest.  t.g and t.d hold rows x F (the GELU output's
+  // gradient, du) AND rows x D (dh2 = du W1^T and the three dh products go to t.g, do = dy Wo^T to t.d): the larger of the two,
+  // since accept.h admits F < D (policy mlp 32, ctx_mlp 16, enc_mlp 128 under a wider model)
   auto mx = [&](long a, long b, long c) { c = enc ? c : 0; return a > b ? (a > c ? a : c) : (b > c ? b : c); };
   const long rd = mx(B * S * D, B * Sc * C, B * Se * E), rf = mx(B * S * F, B * Sc * Fc, B * Se * Fe), hss = mx(B * H * S * ((S + 3) & ~3L), B * Hc * Sc * ((Sc + 3) & ~3L), B * He * Se * ((Se + 3) & ~3L));
-  pl.t.h = take(rd); pl.t.g = take(rf); pl.t.d = take(rf); pl.t.dk = take(rd); pl.t.dq = take(rd); pl.t.dv = take(rd);      /* k, q, v: the order of the leaves (block_bwd batches the three) */ pl.t.dp = take(hss);
+  const long rg = rf > rd ? rf : rd;
+  pl.t.h = take(rd); pl.t.g = take(rg); pl.t.d = take(rg); pl.t.dk = take(rd); pl.t.dq = take(rd); pl.t.dv = take(rd);      /* k, q, v: the order of the leaves (block_bwd batches the three) */ pl.t.dp = take(hss);
   pl.t.y = take(rd);
   pl.cmean = take(B); pl.crstd = take(B); pl.ctx = take(B * C); pl.dctx = take(B * C); pl.ctxn = take(B * C);
   pl.dxrow = take(B * D);
@@ -1436,6 +1446,38 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
 size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
   return (size_t)make_plan(g, B, train_encoder, nullptr).used + 64;
 }
+#ifdef HVLA_TRAIN_TRACE
+// One line `plan <name> <offset> <floats>` per buffer of make_plan (offsets into `work`, the floats the plan asked for), for
+// tools/train_extent_trace.hip: tests/test_train_workspace_extents.py holds every traced operand to ONE of these buffers.  A buffer
+// make_plan takes without a name below prints as `?`, which that test refuses.
+void train_trace_plan(const Geom& g, int B, bool train_encoder) {
+  float* const base = static_cast<float*>(train_trace_buffer("work"));
+  const Plan pl = make_plan(g, B, train_encoder, base);
+  std::vector<std::string> name(pl.taken.size(), "?");
+  auto put = [&](const std::string& n, const float* p) {
+    if (!p) return;
+    for (size_t i = 0; i < pl.taken.size(); ++i)
+      if (pl.taken[i].first == p - base && name[i] == "?") { name[i] = n; return; }
+  };
+  auto put_blk = [&](const char* kind, const std::vector<BlkBuf>& v) {
+    for (size_t l = 0; l < v.size(); ++l) {
+      const BlkBuf& b = v[l];
+      const std::string pre = std::string(kind) + "[" + std::to_string(l) + "].";
+      put(pre + "x_in", b.x_in); put(pre + "mean0", b.mean0); put(pre + "rstd0", b.rstd0); put(pre + "k", b.k); put(pre + "q", b.q);
+      put(pre + "v", b.v); put(pre + "p", b.p); put(pre + "o", b.o); put(pre + "x_mid", b.x_mid); put(pre + "mean1", b.mean1);
+      put(pre + "rstd1", b.rstd1); put(pre + "u", b.u); put(pre + "y1", b.y1); put(pre + "y2", b.y2); put(pre + "h", b.h);
+      put(pre + "h2", b.h2); put(pre + "g", b.g);
+    }
+  };
+  put_blk("cb", pl.cb); put_blk("pb", pl.pb); put_blk("eb", pl.eb);
+  put("cx_fin", pl.cx_fin); put("cdx", pl.cdx); put("px_fin", pl.px_fin); put("pdx", pl.pdx); put("ex_fin", pl.ex_fin); put("edx", pl.edx);
+  put("eh", pl.eh); put("patches", pl.patches); put("emean", pl.emean); put("erstd", pl.erstd);
+  put("t.h", pl.t.h); put("t.g", pl.t.g); put("t.d", pl.t.d); put("t.dk", pl.t.dk); put("t.dq", pl.t.dq); put("t.dv", pl.t.dv);
+  put("t.dp", pl.t.dp); put("t.y", pl.t.y);
+  put("cmean", pl.cmean); put("crstd", pl.crstd); put("ctx", pl.ctx); put("dctx", pl.dctx); put("ctxn", pl.ctxn); put("dxrow", pl.dxrow);
+  for (size_t i = 0; i < pl.taken.size(); ++i) printf("plan %s %ld %ld\n", name[i].c_str(), pl.taken[i].first, pl.taken[i].second);
+}
+#endif
 
 hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const TrainInputs& in, int B,
                       const TrainHyper& hp, hipStream_t st, hipEvent_t* bucket_done, const TrainOptions& opt) {

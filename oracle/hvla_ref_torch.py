@@ -96,12 +96,20 @@ class HyperNetRef:
 # ---------------------------------------------------------------- DINOv2 (HF torch model)
 def build_hf_dinov2(params: Dict[str, np.ndarray], g, enc_shapes, dtype=torch.float32):
     from transformers import Dinov2Config, Dinov2Model
+    # Dinov2Config carries the MLP width as an INTEGER multiple of the hidden size; accept.h admits any enc_mlp % 128 == 0 (128
+    # under 256 .. 1024, 384 under 640).  Where enc_mlp is not that multiple, fc1 / fc2 are replaced by Linears of the real width
+    # before the weights are loaded: Dinov2MLP is fc1 -> activation -> fc2 and reads no width from the config afterwards.
+    ratio = max(1, g.enc_mlp // g.enc_dim)
     cfg = Dinov2Config(hidden_size=g.enc_dim, num_hidden_layers=g.enc_layers,
-                       num_attention_heads=g.enc_heads, mlp_ratio=g.enc_mlp // g.enc_dim,
+                       num_attention_heads=g.enc_heads, mlp_ratio=ratio,
                        image_size=g.image_size, patch_size=g.patch, layer_norm_eps=1e-6,
                        hidden_act="gelu", layerscale_value=1.0, qkv_bias=True,
                        use_swiglu_ffn=False, attn_implementation="eager")
     m = Dinov2Model(cfg).eval()
+    if ratio * g.enc_dim != g.enc_mlp:
+        for layer in m.encoder.layer:
+            layer.mlp.fc1 = torch.nn.Linear(g.enc_dim, g.enc_mlp)
+            layer.mlp.fc2 = torch.nn.Linear(g.enc_mlp, g.enc_dim)
 
     def get(path):
         return torch.as_tensor(params["encoder_image_encoder_" + "_".join(path)]).reshape(enc_shapes[path]).float()

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from adamw_ref import bf16_round as _bf16_round, optax_step as _optax_step
+from train_parity import encoder_case as _encoder_case, frozen_encoder_case as _frozen_encoder_case
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -142,67 +143,11 @@ def test_loss_decreases_over_steps(setup):
 @pytest.mark.timeout(900)
 def test_full_geometry_gradients(golden_dir):
     """README geometry (vit_t policy on 256 DINOv2-base tokens, 201 500 generated parameters), B = 2."""
-    from hypervla import synthetic as syn
-    from hypervla.config import FULL, generated_leaves
-    from hypervla.model import HyperVLA
-    from hypervla.train import FineTuner, unpack_params
-    from oracle import hvla_ref_torch as ot
-    g, B = FULL, 2
-    model = HyperVLA.from_synthetic(g, max_batch=B)
-    ins, st = syn.synthetic_instructions(B, g), syn.synthetic_initial_state(B, g)
-    batch = syn.synthetic_action_batch(B, g)
-    tok = np.random.default_rng(9).standard_normal((B, g.patches, g.enc_dim)).astype(np.float32)   # frozen-encoder tokens
-    params = {k: v for k, v in model.params.items() if not k.startswith("encoder_image_encoder_")}
-    per, loss, grads = ot.train_loss_and_grads(params, g, generated_leaves(g), ins, st, tok, batch)
-    ft = FineTuner(model, B)
-    got_loss = ft.forward_backward(ins, st, tok, batch).cpu().numpy()
-    np.testing.assert_allclose(got_loss, per.numpy(), rtol=3e-4, atol=3e-5)
-    got = unpack_params(g, ft.grads.cpu().numpy())
-    gmax = max(float(v.abs().max()) for v in grads.values())
-    worst = max((np.abs(got[k].reshape(v.shape) - v.numpy()).max() / max(float(v.abs().max()), 1e-4 * gmax), k) for k, v in grads.items())
-    print("full geometry worst relative gradient error", worst)
-    assert worst[0] <= 3e-3, worst
+    from hypervla.config import FULL
+    _frozen_encoder_case(FULL, 2, 3e-3)
 
 
-# ------------------------------------------------------------------ trained image encoder (README.md:55)
-def _encoder_case(g, B, tol, seed_rank=0, stats=None):
-    from hypervla import synthetic as syn
-    from hypervla.config import encoder_leaves, generated_leaves
-    from hypervla.model import HyperVLA
-    from hypervla.train import FineTuner, unpack_params
-    from oracle import hvla_ref_torch as ot
-    model = HyperVLA.from_synthetic(g, max_batch=B)
-    ins, st, im = syn.synthetic_instructions(B, g, seed_rank), syn.synthetic_initial_state(B, g, seed_rank), syn.synthetic_images(B, g, seed_rank)
-    batch = syn.synthetic_action_batch(B, g, seed_rank)
-    per, loss, grads = ot.train_loss_and_grads(model.params, g, generated_leaves(g), ins, st, None, batch, images=im,
-                                               enc_shapes=dict(encoder_leaves(g)))
-    ft = FineTuner(model, B, train_encoder=True)
-    got_loss = ft.forward_backward(ins, st, im, batch).cpu().numpy()
-    np.testing.assert_allclose(got_loss, per.numpy(), rtol=3e-4, atol=3e-5)
-    got = unpack_params(g, ft.grads.cpu().numpy(), train_encoder=True)
-    assert set(got) == set(grads), set(got) ^ set(grads)
-    gmax = max(float(v.abs().max()) for v in grads.values())
-    rel = sorted(((np.abs(got[k].reshape(v.shape) - v.numpy()).max() / max(float(v.abs().max()), 1e-4 * gmax), k)
-                  for k, v in grads.items()), reverse=True)
-    print("worst relative gradient errors (trained encoder):", [(f"{r:.2e}", k) for r, k in rel[:6]])
-    enc_rel = [r for r in rel if r[1].startswith("encoder_image_encoder_")]
-    assert len(enc_rel) == len(encoder_leaves(g))
-    assert any(float(grads[k].abs().max()) > 0 for _, k in enc_rel)
-    if stats is not None:
-        # the bias and LayerScale leaves of the encoder are the outputs of the column-sum / LayerScale kernels (colsum*_kernel,
-        # ls_bwd*_kernel, the LayerNorm parameter gradients): per ELEMENT against the leaf's RMS, so that a lost column group or row
-        # block is not hidden behind a large neighbour of the same leaf
-        for k, v in grads.items():
-            if k.startswith("encoder_image_encoder_encoder_layer_") and (k.endswith("bias") or k.endswith("lambda1") or k.endswith("scale")):
-                ref = v.numpy()
-                rms = float(np.sqrt((ref * ref).mean()))
-                if rms > 1e-6 * gmax:                   # (key biases: the softmax is invariant to them, their gradient is rounding noise)
-                    stats[k] = float(np.abs(got[k].reshape(ref.shape) - ref).max() / rms)
-        stats["__max_metric__"] = rel[0]
-    assert rel[0][0] <= tol, rel[:6]
-    return model, ft, (ins, st, im, batch)
-
-
+# ------------------------------------------------------------------ trained image encoder (README.md:55); _encoder_case: tests/train_parity.py
 def test_encoder_gradients_match_autograd():
     """Every DINOv2 leaf (patch conv, cls / position embeddings, LayerScale, 12x attention + MLP, final LayerNorm) and
     every hypernetwork leaf against float64 autograd through transformers' Dinov2Model + the restated policy."""

@@ -131,6 +131,30 @@ def test_mix_loss_numpy_vs_torch_and_gradient_oracle():
     assert abs(fd - float(grads[key][idx])) <= 1e-6 * max(1.0, abs(fd))
 
 
+@pytest.mark.parametrize("widths", [dict(enc_dim=256, enc_heads=4, enc_mlp=128), dict(enc_dim=640, enc_heads=10, enc_mlp=384)],
+                         ids=["mlp-below-dim", "mlp-no-multiple-of-dim"])
+def test_torch_encoder_expresses_every_accepted_mlp_width(widths):
+    """transformers' Dinov2Config carries the MLP width as an integer multiple of the hidden size; hvla_create accepts any
+    enc_mlp % 128 == 0 (128 under enc_dim 256, 384 under 640).  build_hf_dinov2 replaces fc1 / fc2 for those: the float64 torch
+    encoder equals the numpy restatement at both geometries (tests/test_gpu_train_geometry.py's E1 and E2), so the gradient oracle
+    of the fine-tune step differentiates the encoder the device runs."""
+    import dataclasses
+    import torch
+    from hypervla.config import MID
+    from oracle import hvla_ref_torch as ot
+    g = dataclasses.replace(MID, **widths)
+    enc = dict(encoder_leaves(g))
+    P, im = syn.synthetic_params(g), syn.synthetic_images(2, g)
+    ref = onp.dinov2(P, g, enc, onp.normalize_images(im[:, 0]))
+    m = ot.build_hf_dinov2(P, g, enc, torch.float64)
+    assert m.encoder.layer[0].mlp.fc1.weight.shape == (g.enc_mlp, g.enc_dim)
+    x = torch.as_tensor(onp.normalize_images(im[:, 0])).permute(0, 3, 1, 2).contiguous()
+    with torch.no_grad():
+        got = m(pixel_values=x).last_hidden_state.numpy()
+    assert got.shape == ref.shape == (2, g.patches + 1, g.enc_dim)
+    assert np.abs(got - ref).max() <= 1e-12, np.abs(got - ref).max()
+
+
 def test_t5_restatement_matches_transformers_torch_t5():
     """The float64 T5 encoder restatement against transformers' own torch T5EncoderModel (same architecture as the
     FlaxT5EncoderModel the reference calls) on random weights, incl. padding and the relative-position buckets."""

@@ -1,6 +1,6 @@
-// train_launch_trace.h -- what csrc/train.hip's launch seam becomes under -DHVLA_TRAIN_TRACE (tools/train_launch_trace.cpp only;
-// neither library sets the flag).  Included by train.hip INSIDE namespace hvla, behind HeadP / AuxP / BG: KL, ENQ and bgemm()
-// print one line per operation and enqueue nothing, so the host sequencing of train_step / train_apply / train_accumulate runs on
+// train_launch_trace.h -- what csrc/train.hip's launch seam becomes under -DHVLA_TRAIN_TRACE (tools/train_launch_trace.hip and
+// tools/train_extent_trace.hip only; neither library sets the flag).  Included by train.hip INSIDE namespace hvla, behind
+// HeadP / AuxP / BG: KL, ENQ and bgemm() print one line per operation and enqueue nothing, so the host sequencing of train_step / train_apply / train_accumulate runs on
 // a machine without a GPU, on pointers nobody dereferences.  tests/native/train_step_trace.txt is this output, recorded once.
 //
 // Pointers print as buffer+offset (elements of the pointer's type) against the fake bases below, 2^40 bytes apart and 4 KiB

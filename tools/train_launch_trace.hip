@@ -6,88 +6,11 @@
 //
 // tests/native/train_step_trace.txt is its output, recorded from the sequencing before the block-leaf table;
 // tests/test_train_launch_trace.py builds it from the tree and compares byte for byte.  A change that moves a launch on purpose
-// regenerates the file and says so.
-#include <cstdio>
-
-#include "train.h"
-
-namespace hvla { void* train_trace_buffer(const char* name); }
-using namespace hvla;
-
-template <class T> static T* buf(const char* name) { return static_cast<T*>(train_trace_buffer(name)); }
-
-static Geom mid() {      // the MID geometry of the tests
-  Geom g{112, 14, 128, 2, 2, 512, 64, 2, 4, 128, 4, 7, 5.f, 5.f, 128, 2, 4, 256, 12, 64, 1};
-  return g;
-}
-static Geom readme2() {  // the README widths with two encoder layers
-  Geom g = mid();
-  g.image_size = 224; g.E = 768; g.enc_heads = 12; g.enc_mlp = 3072; g.L = 4; g.ctx_layers = 6; g.ctx_mlp = 512; g.T = 32; g.lang_dim = 768;
-  return g;
-}
-
-struct Point {
-  const char* geom; Geom g; int B;
-  int enc;               // 0 encoder frozen, 1 trained, 2 trained with a position source (n = 16)
-  int forward_only, frozen_buckets, frozen_mask;
-  int aux;               // 0 off, 1 entropy only, 2 both
-  float ema_decay, base_wd;
-};
-
-static int run(const Point& p) {
-  const Geom& g = p.g;
-  printf("# %s L=%d ctx_layers=%d enc_layers=%d B=%d enc=%d forward_only=%d frozen_buckets=%d frozen=%d aux=%d ema=%g base_wd=%g\n", p.geom, g.L,
-         g.ctx_layers, g.enc_layers, p.B, p.enc, p.forward_only, p.frozen_buckets, p.frozen_mask, p.aux, (double)p.ema_decay, (double)p.base_wd);
-  const bool enc = p.enc != 0;
-  printf("workspace %zu\n", train_workspace_floats(g, p.B, enc));
-  TrainBuffers tb{buf<float>("params"), buf<float>("grads"), buf<__bf16>("mu"), buf<float>("nu"), buf<float>("ema"), buf<float>("theta"),
-                  buf<float>("dtheta"), buf<float>("work"), buf<float>("loss"), buf<float>("actions"), buf<float>("logits"), buf<float>("sqsum"),
-                  buf<uint8_t>("wd_mask"), enc ? buf<float>("params0") : nullptr};
-  TrainInputs in{buf<float>("tok"), buf<int64_t>("attn_mask"), buf<float>("cls"), enc ? nullptr : buf<float>("tokens"),
-                 enc ? buf<uint8_t>("images") : nullptr, buf<float>("target"), buf<uint8_t>("tmask"), buf<uint8_t>("amask")};
-  TrainHyper hp{1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 1.f, p.ema_decay, 3, p.forward_only, 1e-4f, p.base_wd};
-  TrainOptions opt;
-  if (p.enc == 2) { opt.ps.n = 16; opt.ps.w = buf<float>("pos_w"); opt.ps.grid = g.grid(); opt.ps.E = g.E; }
-  AttnAux& aux = opt.aux;
-  if (p.aux >= 1) { aux.w_ent = 0.25f; aux.ent = buf<float>("aux_ent"); }
-  if (p.aux >= 2) { aux.w_align = 0.5f; aux.ref = buf<float>("aux_ref"); aux.align = buf<float>("aux_align"); }
-  opt.frozen_buckets = p.frozen_buckets;
-  opt.frozen = p.frozen_mask ? buf<uint8_t>("frozen") : nullptr;
-  hipEvent_t ev[3];
-  for (int i = 0; i < 3; ++i) ev[i] = reinterpret_cast<hipEvent_t>(buf<char>("event") + i);
-  hipStream_t st = reinterpret_cast<hipStream_t>(buf<char>("st"));
-  if (train_refusal(g)) { printf("refused: %s\n", train_refusal(g)); return 1; }
-  const TrainLayout L = make_train_layout(g);
-  if (!L.policy_ok) { printf("a policy leaf was not found\n"); return 1; }
-  printf("step\n");
-  (void)train_step(g, L, tb, in, p.B, hp, st, p.forward_only ? nullptr : ev, opt);
-  if (p.forward_only) return 0;
-  printf("accumulate\n");
-  (void)train_accumulate(L, tb, buf<float>("acc"), 0.5f, hp, enc, st, opt);
-  printf("apply\n");
-  (void)train_apply(L, tb, hp, enc, st, opt);
-  return 0;
-}
+// regenerates the file and says so.  The points and the driver of one point: tools/train_trace_driver.h.
+#include "train_trace_driver.h"
 
 int main() {
-  Geom l16 = mid(), l1 = mid();
-  l16.L = 16; l16.ctx_layers = 0;
-  l1.L = 1; l1.ctx_layers = 8;
-  const Point sweep[] = {
-      // geometry          B  enc fwd fb mask aux ema    base_wd
-      {"MID", mid(), 1, 2, 0, 0, 0, 2, 0.999f, 0.05f},
-      {"MID", mid(), 5, 0, 0, 2, 1, 0, 0.f, 0.f},
-      {"MID", mid(), 32, 1, 0, 0, 1, 1, 0.f, 0.05f},
-      {"MID", mid(), 32, 2, 1, 0, 0, 2, 0.f, 0.f},
-      {"README2", readme2(), 2, 0, 0, 4, 1, 0, 0.999f, 0.f},
-      {"README2", readme2(), 8, 1, 0, 6, 1, 0, 0.f, 0.f},
-      {"README2", readme2(), 32, 2, 0, 4, 0, 1, 0.999f, 0.05f},
-      // the layer-count edges, forward only (a block's backward is the same text for every layer; the per-layer offsets are
-      // tests/native/train_layout_check.cpp's)
-      {"MID-L16", l16, 1, 0, 1, 0, 0, 2, 0.f, 0.f},
-      {"MID-L1", l1, 5, 0, 1, 0, 0, 0, 0.f, 0.f},
-  };
-  for (const Point& p : sweep)
+  for (const Point& p : recorded_sweep())
     if (run(p)) return 1;
   return 0;
 }
