@@ -43,6 +43,7 @@ using hvla::pack::f2h;
 
 struct hvla_weights {
   int B = 0;
+  int Gm = 0, Gv = 0, C = 0;     // the row sizes it was allocated for: an arena of another geometry is refused where rows are written whole
   DevBuf wh, wl, vf, ctx, ring, count;
   DevBuf slot_count;             // int32 [B]: the episode pool's per-row ensemble counters (hvla_ensemble_slots)
 };
@@ -179,6 +180,9 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
   for (int i = 0; i < NUM_WS; ++i) A(ctx->ws[i], ctx->wsp.bytes(i));
   if (e != hipSuccess) return HVLA_E_ARENA_FULL;
   if (hipMemset(ctx->ws[WS_LN_CNT].p, 0, ctx->ws[WS_LN_CNT].bytes) != hipSuccess) return HVLA_E_HIP;
+  // the packed order on the device: a property of the geometry, so hvla_weights_import can run before any weights are loaded
+  if (ctx->perm.alloc(ctx->lay.perm.size() * 4) != hipSuccess) return HVLA_E_ARENA_FULL;
+  if (hipMemcpy(ctx->perm.p, ctx->lay.perm.data(), ctx->lay.perm.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return HVLA_E_HIP;
   if (c->streams == 2) {
     if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -230,7 +234,6 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   HIPCHK(ctx, up(ctx->wcat_hi, hi.data(), hi.size() * 2));
   HIPCHK(ctx, up(ctx->wcat_lo, lo.data(), lo.size() * 2));
   HIPCHK(ctx, up(ctx->bcat, bc.data(), bc.size() * 4));
-  HIPCHK(ctx, up(ctx->perm, ctx->lay.perm.data(), ctx->lay.perm.size() * 4));
   HIPCHK(ctx, up(ctx->enc16, h.enc16.data(), h.enc16.size() * 2));
   HIPCHK(ctx, up(ctx->encd16, h.encd16.data(), h.encd16.size() * 2));
   HIPCHK(ctx, up(ctx->encf32, h.encf.data(), h.encf.size() * 4));
@@ -321,6 +324,7 @@ static int take_arena(hvla_ctx* ctx, int32_t B, std::unique_ptr<hvla_weights>& w
   }
   w.reset(new hvla_weights);
   w->B = B;
+  w->Gm = pl.Gm; w->Gv = pl.Gv; w->C = g.C;
   hipError_t e = hipSuccess;
   auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
   auto all = [&]() {
@@ -600,6 +604,77 @@ int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, in
   hipStream_t st;
   if (int r = serve_entry(ctx, w != nullptr, slots_of(w, slots, K, false), actions && mean && std && mask && out, stream, st)) return r;
   return ensemble_body(ctx, w, slots, K, actions, mean, std, mask, out, st);
+}
+
+// ------------------------------------------------------------------ weight arenas as values (include/hvla.h)
+// None of these asks for loaded weights: the permutation is the geometry's, and the language prefix reads the arena and the tokens only.
+static ServeCount arena_batch_of(int32_t B) { return {ServeCount::BATCH, false, B, nullptr, nullptr}; }
+
+// rows are written whole, so the arena must have this context's row sizes (an arena of another context with the same geometry is fine)
+static int arena_fits(hvla_ctx* ctx, const hvla_weights* w, const char* what) {
+  const PolicyLayout& pl = ctx->lay.pl;
+  if (w->Gm != pl.Gm || w->Gv != pl.Gv || w->C != ctx->g.C)
+    FAIL(ctx, HVLA_E_SHAPE, "the %s arena belongs to another geometry (rows of %d + %d weights and %d context floats, this context's have %d + %d and %d)",
+         what, w->Gm, w->Gv, w->C, pl.Gm, pl.Gv, ctx->g.C);
+  return HVLA_OK;
+}
+
+// what an import refuses before it touches an arena: no theta, or tokens that do not go with the context's use_language_token
+static int import_args(hvla_ctx* ctx, int K, const float* theta, const float* tok) {
+  if (!theta) FAIL(ctx, HVLA_E_SHAPE, "null theta: the import needs the [%d, %d] parameter rows", K, ctx->lay.pl.G);
+  if (ctx->lay.ll.on && !tok)
+    FAIL(ctx, HVLA_E_SHAPE, "a use_language_token context imports with the episodes' token embeddings [%d, %d, %d]: none given", K,
+         ctx->g.T, ctx->g.lang_dim);
+  if (!ctx->lay.ll.on && tok) FAIL(ctx, HVLA_E_SHAPE, "token embeddings given to a context without use_language_token");
+  return HVLA_OK;
+}
+
+// theta [K, G] (+ context, + tokens) into rows slots[k] (null: rows k) of w: import_theta_kernel, then the language prefix of those rows
+static int import_body(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int K, const float* theta, const float* context,
+                       const float* tok, hipStream_t st) {
+  const PolicyLayout& pl = ctx->lay.pl;
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_import_theta(theta, context, ctx->perm.as<int32_t>(), slots, w->wh.as<__bf16>(), w->wl.as<__bf16>(),
+                                  w->vf.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), pl.Gm, pl.Gv, pl.G, ctx->g.C, K, w->B,
+                                  st));
+  return lang_prefix(ctx, w, tok, K, slots, st);
+}
+
+int hvla_weights_import(hvla_ctx* ctx, const float* theta, const float* context, const float* tok, int32_t B, hvla_weights** out,
+                        void* stream) {
+  if (ctx && out) *out = nullptr;
+  hipStream_t st;
+  if (int r = serve_entry(ctx, out != nullptr, arena_batch_of(B), true, stream, st)) return r;
+  if (int r = import_args(ctx, B, theta, tok)) return r;
+  std::unique_ptr<hvla_weights> w;
+  if (int r = take_arena(ctx, B, w)) return r;
+  HIPCHK(ctx, hipMemsetAsync(w->count.p, 0, 16, st));      // (the per-row counters are the kernel's)
+  if (int r = import_body(ctx, w.get(), nullptr, B, theta, context, tok, st)) return r;
+  *out = w.release();
+  return HVLA_OK;
+}
+
+int hvla_weights_import_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* theta,
+                              const float* context, const float* tok, void* stream) {
+  hipStream_t st;
+  if (int r = serve_entry(ctx, w != nullptr, slots_of(w, slots, K, false), true, stream, st)) return r;
+  if (int r = import_args(ctx, K, theta, tok)) return r;
+  if (int r = arena_fits(ctx, w, "destination")) return r;
+  return import_body(ctx, w, slots, K, theta, context, tok, st);
+}
+
+int hvla_weights_copy_slots(hvla_ctx* ctx, hvla_weights* dst, const int32_t* dst_slots, const hvla_weights* src,
+                            const int32_t* src_slots, int32_t K, void* stream) {
+  hipStream_t st;
+  if (int r = serve_entry(ctx, dst != nullptr && src != nullptr, slots_of(dst, dst_slots, K, false), true, stream, st)) return r;
+  if (!src_slots) FAIL(ctx, HVLA_E_SHAPE, "null source slot map");
+  if (K > src->B) FAIL(ctx, HVLA_E_SHAPE, "%d slots outside [1, %d] (the source arena has %d rows)", K, src->B, src->B);
+  if (int r = arena_fits(ctx, dst, "destination")) return r;
+  if (int r = arena_fits(ctx, src, "source")) return r;
+  ++ctx->prof.nlaunch;
+  HIPCHK(ctx, launch_copy_rows(src->wh.p, src->wl.p, src->vf.p, src->ctx.p, dst->wh.p, dst->wl.p, dst->vf.p, dst->ctx.p,
+                               dst->slot_count.as<int>(), src_slots, dst_slots, dst->Gm, dst->Gv, dst->C, K, src->B, dst->B, st));
+  return HVLA_OK;
 }
 
 // ------------------------------------------------------------------ post-processing of pool slots (include/hvla.h)

@@ -44,6 +44,16 @@ hipError_t launch_pool_assign(const float* ctx_rows, float* ctx, int* count, con
                               hipStream_t st);
 hipError_t launch_export_theta(const __bf16* wh, const __bf16* wl, const float* vf, const int32_t* perm,
                                int Gm, int Gv, int G, int B, float* theta, hipStream_t st);
+// weight arenas as values (weights_io.hip).  launch_import_theta: the export's inverse, theta [K, G] (+ context [K, C],
+// or null: zeros) into arena rows slot[k] (slot null: rows k) of an arena of `rows`, those rows' ensemble counters zeroed.
+// launch_copy_rows: rows src_slot[k] of one arena into rows dst_slot[k] of another, bytewise, the destination counters zeroed.  Slot
+// entries outside their arena are skipped, as above.
+hipError_t launch_import_theta(const float* theta, const float* context, const int32_t* perm, const int32_t* slot, __bf16* wh,
+                               __bf16* wl, float* vf, float* ctx, int* count, int Gm, int Gv, int G, int C, int K, int rows,
+                               hipStream_t st);
+hipError_t launch_copy_rows(const void* swh, const void* swl, const void* svf, const void* sctx, void* dwh, void* dwl, void* dvf,
+                            void* dctx, int* count, const int32_t* src_slot, const int32_t* dst_slot, int Gm, int Gv, int C, int K,
+                            int srows, int drows, hipStream_t st);
 
 // ---------------------------------------------------------------- image encoder (DINOv2)
 struct EncLayerW {

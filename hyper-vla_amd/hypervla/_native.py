@@ -26,7 +26,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
            "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
-           "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses"]
+           "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses",
+           "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots"]
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -191,6 +192,12 @@ def load_library():
     lib.hvla_step_slots.restype = C.c_int
     lib.hvla_ensemble_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.hvla_ensemble_slots.restype = C.c_int
+    lib.hvla_weights_import.argtypes = [vp, vp, vp, vp, i32, C.POINTER(vp), vp]
+    lib.hvla_weights_import.restype = C.c_int
+    lib.hvla_weights_import_slots.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.hvla_weights_import_slots.restype = C.c_int
+    lib.hvla_weights_copy_slots.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    lib.hvla_weights_copy_slots.restype = C.c_int
     lib.hvla_post_create.argtypes = [vp, i32, C.POINTER(vp), vp]
     lib.hvla_post_create.restype = C.c_int
     lib.hvla_post_free.argtypes = [vp, vp]
@@ -451,6 +458,22 @@ class Context:
     def ensemble_slots(self, w, slots_ptr, K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr, stream=0):
         self._check(self.lib.hvla_ensemble_slots(self.h, w, C.c_void_p(slots_ptr), K, act_ptr, mean_ptr, std_ptr, mask_ptr, out_ptr,
                                                  C.c_void_p(stream)), "hvla_ensemble_slots")
+
+    # weight arenas as values (include/hvla.h): device pointers as ints, 0 / None = NULL
+    def weights_import(self, theta_ptr, ctx_ptr, tok_ptr, B, stream=0):
+        w = C.c_void_p()
+        self._check(self.lib.hvla_weights_import(self.h, C.c_void_p(theta_ptr or None), C.c_void_p(ctx_ptr or None),
+                                                 C.c_void_p(tok_ptr or None), B, C.byref(w), C.c_void_p(stream)), "hvla_weights_import")
+        return w
+
+    def weights_import_slots(self, w, slots_ptr, K, theta_ptr, ctx_ptr, tok_ptr, stream=0):
+        self._check(self.lib.hvla_weights_import_slots(self.h, w, C.c_void_p(slots_ptr or None), K, C.c_void_p(theta_ptr or None),
+                                                       C.c_void_p(ctx_ptr or None), C.c_void_p(tok_ptr or None), C.c_void_p(stream)),
+                    "hvla_weights_import_slots")
+
+    def weights_copy_slots(self, dst, dst_slots_ptr, src, src_slots_ptr, K, stream=0):
+        self._check(self.lib.hvla_weights_copy_slots(self.h, dst, C.c_void_p(dst_slots_ptr or None), src,
+                                                     C.c_void_p(src_slots_ptr or None), K, C.c_void_p(stream)), "hvla_weights_copy_slots")
 
     # post-processing of pool slots (include/hvla.h hvla_post_*; hypervla.postprocess drives these)
     def post_create(self, B, stream=0):

@@ -207,6 +207,65 @@ def total_generated(g: Geometry) -> int:
 assert total_generated(FULL) == 201_500 and len(generated_leaves(FULL)) == 73
 
 
+def pytree_from_theta(g: Geometry, theta, squeeze: bool = False) -> Dict:
+    """theta [B, G] (reference leaf order, what `GeneratedWeights.export` returns) -> the reference's nested ``base_params`` dict of
+    the generated leaves, each [B, *shape] (``squeeze``: episode 0 alone, [*shape], as the reference's create_tasks squeezes B == 1)."""
+    theta = np.asarray(theta)
+    G = total_generated(g)
+    if theta.ndim != 2 or theta.shape[1] != G:
+        raise ValueError(f"theta must be [B, {G}], got {theta.shape}")
+    tree: Dict = {}
+    for lf in generated_leaves(g):
+        v = theta[:, lf.offset:lf.offset + lf.size].reshape((theta.shape[0],) + lf.shape)
+        if squeeze:
+            v = v[0]
+        node = tree
+        for key in lf.path[:-1]:
+            node = node.setdefault(key, {})
+        node[lf.path[-1]] = v
+    return tree
+
+
+def theta_from_pytree(g: Geometry, tree: Dict) -> np.ndarray:
+    """The inverse of :func:`pytree_from_theta`: a nested ``base_params`` dict -> float32 [B, G].  Leaves are [B, *shape], or
+    [*shape] throughout for one episode.  An ``encoder/image_encoder`` subtree -- the shared DINOv2 leaves the reference broadcasts
+    into ``base_params`` (hypernetwork.py:233), of which the device holds one copy -- is ignored.  A missing leaf raises KeyError,
+    an unknown one ValueError, a wrong shape ValueError, each naming the leaf's path."""
+    leaves = generated_leaves(g)
+    known = {lf.path for lf in leaves}
+
+    def walk(node, path):
+        for key, v in node.items():
+            p = path + (key,)
+            if p == ("encoder", "image_encoder"):
+                continue
+            if isinstance(v, dict):
+                walk(v, p)
+            elif p not in known:
+                raise ValueError(f"unknown leaf {'/'.join(p)}: not one of the {len(leaves)} generated leaves of this geometry")
+
+    walk(tree, ())
+    cols, B = [], None
+    for lf in leaves:
+        node, name = tree, "/".join(lf.path)
+        for key in lf.path:
+            if not isinstance(node, dict) or key not in node:
+                raise KeyError(f"missing leaf {name}")
+            node = node[key]
+        if isinstance(node, dict):
+            raise ValueError(f"leaf {name} is a subtree, expected an array of shape {('B',) + lf.shape}")
+        v = np.asarray(node)
+        if v.shape == lf.shape and B in (None, 0):
+            B, v = 0, v[None]                        # the single-episode form
+        elif v.ndim == len(lf.shape) + 1 and v.shape[1:] == lf.shape and B in (None, v.shape[0]) and v.shape[0] >= 1:
+            B = v.shape[0]
+        else:
+            want = lf.shape if B == 0 else (("B" if B is None else B),) + lf.shape
+            raise ValueError(f"leaf {name} has shape {v.shape}, expected {want}")
+        cols.append(v.reshape(v.shape[0], -1).astype(np.float32, copy=False))
+    return np.ascontiguousarray(np.concatenate(cols, 1))
+
+
 # --------------------------------------------------------------------------------------
 # config.json the evaluators read (data/utils/hypervla_interface.py:76-87, model.py:152-163)
 # --------------------------------------------------------------------------------------

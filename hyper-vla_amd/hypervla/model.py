@@ -30,7 +30,7 @@ import numpy as np
 
 from . import _native
 from .config import (FULL, Geometry, default_config, generated_leaves, geometry_from_config,
-                     hypernet_param_shapes)
+                     hypernet_param_shapes, pytree_from_theta, theta_from_pytree)
 
 
 def _torch():
@@ -44,8 +44,11 @@ class GeneratedWeights:
     episode pool is mutable in place: `HyperVLA.assign_tasks` regenerates slots of a handle from `create_pool` (or from
     `create_tasks`) and leaves its other rows as they are; `batch` is then the pool's capacity."""
 
-    def __init__(self, model: "HyperVLA", handle, batch: int):
+    def __init__(self, model: "HyperVLA", handle, batch: int, tokens=None):
         self._model, self._h, self.batch = model, handle, batch
+        # use_language_token: the token embeddings [batch, T, lang_dim] the rows' language prefixes were built from (a device tensor
+        # of the handle's own; None without the option) -- the prefix is not part of theta, so `save` needs them
+        self._tokens = tokens
 
     def __del__(self):
         try:
@@ -68,17 +71,19 @@ class GeneratedWeights:
     def to_pytree(self, squeeze: bool = False) -> Dict[str, Any]:
         """The reference's nested ``base_params`` dict (generated leaves only; the shared DINOv2 leaves
         live once on the device and are not broadcast, hypernetwork.py:233)."""
-        theta = self.export()[0].cpu().numpy()
-        tree: Dict[str, Any] = {}
-        for lf in generated_leaves(self._model.geometry):
-            v = theta[:, lf.offset:lf.offset + lf.size].reshape((self.batch,) + lf.shape)
-            if squeeze:
-                v = v[0]
-            node = tree
-            for key in lf.path[:-1]:
-                node = node.setdefault(key, {})
-            node[lf.path[-1]] = v
-        return tree
+        return pytree_from_theta(self._model.geometry, self.export()[0].cpu().numpy(), squeeze)
+
+    def save(self, path: str) -> None:
+        """Write the handle's policies to `path` as an npz: ``theta`` [B, G] and ``context`` [B, C] as `export` returns them and the
+        geometry's ``G``; with use_language_token also the ``token_embedding`` [B, T, lang_dim] the rows were built from.
+        `HyperVLA.load_tasks` reads it back (through `import_tasks`: the same theta and context bit for bit)."""
+        m = self._model
+        theta, ctx = self.export()
+        arrays = {"theta": theta.cpu().numpy(), "context": ctx.cpu().numpy(), "G": np.int64(m._ctx.num_generated)}
+        if m.geometry.lang_in_policy:
+            arrays["token_embedding"] = self._tokens.cpu().numpy()
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
 
 
 class HyperVLA:
@@ -370,7 +375,7 @@ class HyperVLA:
         torch.cuda.current_stream(self.device).synchronize()      # inputs may be temporaries
         tasks = {"pad_mask_dict": {"language_instruction": np.ones(B, dtype=bool)},     # model.py:51-70
                  "language_instruction": li}
-        return GeneratedWeights(self, h, B), tasks, {}
+        return GeneratedWeights(self, h, B, tok.clone() if self.geometry.lang_in_policy else None), tasks, {}
 
     # ------------------------------------------------------------------ episode pool
     def create_pool(self, capacity: int) -> GeneratedWeights:
@@ -380,7 +385,13 @@ class HyperVLA:
         if not 1 <= capacity <= self.max_batch:
             raise ValueError(f"pool capacity {capacity} outside [1, max_batch={self.max_batch}]")
         h = self._ctx.weights_alloc(capacity, self._stream())
-        return GeneratedWeights(self, h, capacity)
+        return GeneratedWeights(self, h, capacity, self._empty_tokens(capacity))
+
+    def _empty_tokens(self, rows: int):
+        g = self.geometry
+        if not g.lang_in_policy:
+            return None
+        return _torch().zeros(rows, g.lang_tokens, g.lang_dim, dtype=_torch().float32, device=self.device)
 
     def _slot_map(self, slots, pool: GeneratedWeights):
         """`slots` checked on the host (hypervla.pool.check_slots), then as a device int32 tensor."""
@@ -403,8 +414,127 @@ class HyperVLA:
         if K != len(s):
             raise ValueError(f"{K} tasks for {len(s)} slots")
         self._ctx.generate_slots(pool._h, sd.data_ptr(), K, tok.data_ptr(), mask.data_ptr(), cls.data_ptr(), self._stream())
+        if pool._tokens is not None:
+            pool._tokens[sd.long()] = tok
         torch.cuda.current_stream(self.device).synchronize()      # inputs may be temporaries
         return {"pad_mask_dict": {"language_instruction": np.ones(K, dtype=bool)}, "language_instruction": li}
+
+    # ------------------------------------------------------------------ policies as values
+    def _theta_arg(self, base_params):
+        """`base_params` as a device f32 [B, G] tensor: the reference's nested dict, a numpy [B, G], or a torch tensor already on the
+        model's device, which is used in place."""
+        torch = _torch()
+        G = self._ctx.num_generated
+        if isinstance(base_params, GeneratedWeights):
+            raise TypeError("base_params is already a device handle: step it as it is, or copy_tasks() it")
+        if isinstance(base_params, dict):
+            base_params = theta_from_pytree(self.geometry, base_params)
+        if isinstance(base_params, torch.Tensor):
+            if base_params.device != self.device:
+                raise ValueError(f"a theta tensor must be on the model's device {self.device}, got {base_params.device}")
+            theta = base_params
+        else:
+            theta = torch.as_tensor(np.ascontiguousarray(np.asarray(base_params), dtype=np.float32)).to(self.device)
+        if theta.dim() != 2 or theta.shape[1] != G or theta.shape[0] < 1:
+            raise ValueError(f"theta must be [B, {G}], got {tuple(theta.shape)}")
+        if theta.dtype != torch.float32 or not theta.is_contiguous():
+            theta = theta.to(torch.float32).contiguous()
+        return theta
+
+    def _import_inputs(self, base_params, instruction_dict, context):
+        """(theta [B, G], context [B, C] or None, token embeddings [B, T, lang_dim] or None) on the device, shapes checked."""
+        torch = _torch()
+        g = self.geometry
+        theta = self._theta_arg(base_params)
+        B = theta.shape[0]
+        ctx = None
+        if context is not None:
+            ctx = self._dev(context, torch.float32)
+            if tuple(ctx.shape) != (B, g.ctx_dim):
+                raise ValueError(f"context must be [{B}, {g.ctx_dim}], got {tuple(ctx.shape)}")
+        tok = None
+        if g.lang_in_policy:                      # the only thing instruction_dict is read for
+            if instruction_dict is None:
+                raise ValueError("a use_language_token model imports a policy together with the episodes' instruction tokens: "
+                                 "instruction_dict is required (its token embeddings become the rows' language prefix)")
+            li = instruction_dict["language_instruction"]
+            if "token_embedding" not in li and getattr(self, "language_encoder", None) is not None:
+                li = self.encode_instructions(li)
+            tok = self._dev(li["token_embedding"], torch.float32)
+            if tuple(tok.shape) != (B, g.lang_tokens, g.lang_dim):
+                raise ValueError(f"token_embedding must be [{B}, {g.lang_tokens}, {g.lang_dim}], got {tuple(tok.shape)}")
+        return theta, ctx, tok
+
+    def import_tasks(self, base_params, instruction_dict: Dict = None, context=None) -> GeneratedWeights:
+        """A handle for policies that `create_tasks` did not return (`hvla_weights_import`): `base_params` is the reference's nested
+        dict (leaves [B, *shape], or [*shape] for one episode), a numpy [B, G] in reference leaf order, or a torch tensor of that
+        shape on the model's device (used in place).  `context` [B, C] rides along for `export` (default zeros; the policy does not
+        read it).  `instruction_dict` is read only by a use_language_token model, for the token embeddings (bare `input_ids` are
+        encoded by a loaded T5 first).  `export()` of the result returns the vector leaves bit for bit and every matrix element as
+        the sum of its two bf16 halves; an exported theta comes back unchanged."""
+        theta, ctx, tok = self._import_inputs(base_params, instruction_dict, context)
+        B = theta.shape[0]
+        if B > self.max_batch:
+            raise ValueError(f"{B} episodes: more than max_batch={self.max_batch}")
+        h = self._ctx.weights_import(theta.data_ptr(), ctx.data_ptr() if ctx is not None else 0,
+                                     tok.data_ptr() if tok is not None else 0, B, self._stream())
+        _torch().cuda.current_stream(self.device).synchronize()   # inputs may be temporaries
+        return GeneratedWeights(self, h, B, tok.clone() if tok is not None else None)
+
+    def assign_base_params(self, pool: GeneratedWeights, slots, base_params, instruction_dict: Dict = None, context=None) -> None:
+        """`import_tasks` for K policies into slots `slots` of `pool` (`hvla_weights_import_slots`): those slots' weights, context
+        and ensemble counter are replaced -- a slot then steps bitwise as the same row imported alone -- and every other slot is
+        left as it was."""
+        if not isinstance(pool, GeneratedWeights) or pool._model is not self:
+            raise TypeError("pool must be a handle of this model (create_pool / create_tasks / import_tasks)")
+        s, sd = self._slot_map(slots, pool)
+        theta, ctx, tok = self._import_inputs(base_params, instruction_dict, context)
+        if theta.shape[0] != len(s):
+            raise ValueError(f"{theta.shape[0]} policies for {len(s)} slots")
+        self._ctx.weights_import_slots(pool._h, sd.data_ptr(), len(s), theta.data_ptr(), ctx.data_ptr() if ctx is not None else 0,
+                                       tok.data_ptr() if tok is not None else 0, self._stream())
+        if pool._tokens is not None:
+            pool._tokens[sd.long()] = tok
+        _torch().cuda.current_stream(self.device).synchronize()   # inputs may be temporaries
+
+    def copy_tasks(self, dst: GeneratedWeights, dst_slots, src: GeneratedWeights, src_slots=None) -> None:
+        """Rows `src_slots` (None: 0 .. K-1) of `src` into slots `dst_slots` of `dst` (`hvla_weights_copy_slots`): weights, language
+        prefix and context byte for byte -- the copy steps bitwise as its source -- and the destination slots' ensemble counters
+        restarted.  Within one handle the two maps must not share a slot (ValueError)."""
+        from .pool import check_slots
+        for h in (dst, src):
+            if not isinstance(h, GeneratedWeights) or h._model is not self:
+                raise TypeError("dst and src must be handles of this model")
+        d = check_slots(dst_slots, dst.batch)
+        s = check_slots(np.arange(len(d)) if src_slots is None else src_slots, src.batch)
+        if len(s) != len(d):
+            raise ValueError(f"{len(s)} source slots for {len(d)} destination slots")
+        if dst is src and set(d.tolist()) & set(s.tolist()):
+            raise ValueError(f"copy within one handle with overlapping maps: slots {sorted(set(d.tolist()) & set(s.tolist()))} are "
+                             "both read and written")
+        torch = _torch()
+        dd, sd = torch.as_tensor(d).to(self.device), torch.as_tensor(s).to(self.device)
+        self._ctx.weights_copy_slots(dst._h, dd.data_ptr(), src._h, sd.data_ptr(), len(d), self._stream())
+        if dst._tokens is not None:
+            dst._tokens[dd.long()] = src._tokens[sd.long()]
+        torch.cuda.current_stream(self.device).synchronize()      # the maps are temporaries
+
+    def load_tasks(self, path: str) -> GeneratedWeights:
+        """The handle `GeneratedWeights.save(path)` wrote, through `import_tasks`; a file of another geometry's G is refused."""
+        with np.load(path) as z:
+            G = int(z["G"])
+            if G != self._ctx.num_generated:
+                raise ValueError(f"{path} holds policies of G={G} generated parameters, this model's geometry has "
+                                 f"G={self._ctx.num_generated}")
+            theta, context = z["theta"], z["context"]
+            tok = z["token_embedding"] if "token_embedding" in z.files else None
+        ins = None
+        if self.geometry.lang_in_policy:
+            if tok is None:
+                raise ValueError(f"{path} was saved without token embeddings: a use_language_token model cannot build its rows' "
+                                 "language prefix from it")
+            ins = {"language_instruction": {"token_embedding": tok}}
+        return self.import_tasks(theta, ins, context)
 
     def ensemble_actions(self, pool: GeneratedWeights, actions, stats, slots):
         """Un-normalise + temporal ensemble per slot on the device (`hvla_ensemble_slots`): actions [K, horizon, action_dim] of
@@ -452,7 +582,8 @@ class HyperVLA:
             if any(r > 0 for r in rates.values()):
                 raise NotImplementedError(f"train=True with {rates}: dropout / embedding noise are not built (the README run uses 0)")
         if not isinstance(base_params, GeneratedWeights):
-            raise TypeError("base_params must be the handle returned by create_tasks")
+            raise TypeError("base_params must be the handle returned by create_tasks; a pytree or a theta array becomes one "
+                            "through import_tasks (once per episode, not per step)")
         g = self.geometry
         as_torch = isinstance(images, torch.Tensor)
         img = self._dev(images, torch.uint8)

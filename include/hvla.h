@@ -212,6 +212,37 @@ int hvla_step_slots(hvla_ctx* ctx, const hvla_weights* w, const int32_t* slots, 
 int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* actions,
                         const float* mean, const float* std, const uint8_t* mask, float* out, void* stream);
 
+/* Weight arenas as values: the way IN that hvla_weights_export is the way out of.  The reference's create_tasks
+ * returns a plain `base_params` pytree and sample_actions(base_params=...) runs any pytree of that shape (hypervla/model.py:35-137): a
+ * policy kept on disk, the mean of two tasks' policies, a perturbed leaf, one the hypernetwork never produced.  hypervla.model
+ * import_tasks / assign_base_params / copy_tasks / load_tasks drive these.  theta is a DEVICE f32 [K, G] in reference leaf order
+ * (G = hvla_num_generated; what hvla_weights_export writes), context a device f32 [K, ctx_dim] or NULL (zeros: the policy does not read
+ * it), token_embedding a device f32 [K, lang_tokens, lang_dim], required iff the context was created with use_language_token (the
+ * rows' language prefix is then written from it, as hvla_generate does) and refused otherwise.  Matrix elements are split into
+ * hi = bf16(x), lo = bf16(x - hi) exactly as the weight generation splits its f32 results; vector elements are stored as given;
+ * padding is zero.  Hence hvla_weights_export after an import returns theta bit for bit on the vector leaves and float(hi) + float(lo)
+ * on the matrix leaves, and returns an exported theta unchanged -- but the two HALVES of an exported element are not always those
+ * of the arena it came from (0.1 % of elements differ), so a policy re-imported from an export steps close to the original, not
+ * bitwise equal: hvla_weights_copy_slots is the bitwise path.  Every imported or copied slot is bit-batch-invariant: it steps as the
+ * same row imported alone, and a copied row as its source.  None of these calls needs hvla_load_weights to have run; apart from
+ * hvla_weights_import taking an arena (as hvla_generate does: from the ctx's freed arenas when one of that size is parked) none
+ * allocates or synchronises the host, so a pooled loop that imports or copies can be captured in a hipGraph.  HVLA_E_STATE: a NULL
+ * handle; HVLA_E_SHAPE: NULL theta, tokens missing or given without the option, a count outside its range, an arena allocated for
+ * another geometry -- nothing is written then.
+ *
+ * hvla_weights_import: B (1 <= B <= max_batch) rows of theta into a new arena of B episodes, ensemble counters zero.              */
+int hvla_weights_import(hvla_ctx* ctx, const float* theta, const float* context, const float* token_embedding, int32_t B,
+                        hvla_weights** out, void* stream);
+/* Row k of theta (and of context / token_embedding) into slot slots[k] of w, K in [1, B]; slot maps follow the episode pool's rules.
+ * Writes only those rows and zeroes those slots' ensemble counters; every other slot keeps its bytes.                           */
+int hvla_weights_import_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* theta,
+                              const float* context, const float* token_embedding, void* stream);
+/* Slot src_slots[k] of src into slot dst_slots[k] of dst, K in [1, min(B of dst, B of src)]: weights (with the language prefix) and
+ * context byte for byte, the destination's ensemble counter zero; a pair with either entry out of range is skipped.  src and dst may
+ * be the same arena only if no slot is in both maps (hypervla.model.copy_tasks checks; the kernel does not).                     */
+int hvla_weights_copy_slots(hvla_ctx* ctx, hvla_weights* dst, const int32_t* dst_slots, const hvla_weights* src,
+                            const int32_t* src_slots, int32_t K, void* stream);
+
 /* Episode pool post-processing: replaces InferenceWrapper.postprocess (data/utils/hypervla_interface.py:219-304: un-normalisation
  * :219-242, temporal ensemble :250-253 == data/utils/action_ensemble.py:15-27 with temperature 0, euler -> axis-angle :261-267,
  * gripper rules :269-299) for every running episode of a pool at once; hypervla.postprocess.DevicePostprocessor drives it and
