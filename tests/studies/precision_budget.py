@@ -4,7 +4,8 @@
 
 The float64 numpy/torch restatement (oracle/) is run once exactly and once per configuration with the GPU path's
 rounding emulated at the chosen sites (operands rounded to fp16 / bf16, everything else float64), and the predicted
-actions are compared (policy evaluated exactly in both runs, so only the encoder's rounding shows).  Diagnostic tool:
+actions are compared (policy evaluated exactly in both runs, so only the encoder's rounding shows); `--study bias` also
+reports the CLS rows of the hidden state, which the actions do not depend on (hvla_encode_hidden).  Diagnostic tool:
 imports oracle/ and is never imported by the product.
 
 Sites (per encoder layer):  h = LayerNorm outputs (A operand of QKV and fc1),  w = all four weight matrices,
@@ -137,7 +138,9 @@ def encoder(hp, g, enc_shapes, images_u8, sites, kind="f16", layer_kinds=None, l
         a = mm(a, get(L + ("mlp", "fc2", "kernel")), R["w2"], (i, "g")) + get(L + ("mlp", "fc2", "bias"))
         x = x + a * get(L + ("layer_scale2", "lambda1"))
         stats.setdefault("x_absmax", []).append(float(x.abs().max()))
-    return ln(x, get(("layernorm", "scale")), get(("layernorm", "bias")))[:, 1:], stats
+    hidden = ln(x, get(("layernorm", "scale")), get(("layernorm", "bias")))
+    stats["hidden"] = hidden                             # with the CLS row: what hvla_encode_hidden returns
+    return hidden[:, 1:], stats
 
 
 def main():
@@ -179,12 +182,14 @@ def main():
         means = {}
         encoder(hp, g, enc_shapes, cal[:, 0], allsites, a.kind, collect=means)     # calibration run on OTHER images
         for name, corr in ((a.kind + ", no compensation", None), (a.kind + " + static bias corr", means), (a.kind + " + per-image corr", "dynamic")):
-            tok, _ = encoder(hp, g, enc_shapes, im[:, 0], allsites, a.kind, corr=corr)
+            tok, st_ = encoder(hp, g, enc_shapes, im[:, 0], allsites, a.kind, corr=corr)
             act, logit, _ = onp.policy(bp, g, tok.numpy())
             d = np.abs(act[..., :6] - act0[..., :6])
             dt = (tok - tok0).numpy()
+            dc = (st_["hidden"] - stats["hidden"])[:, 0].numpy()         # the CLS rows; tests/test_gpu_hidden_state.py reads the first and last
             print(f"{name:24s} action MAE {d.mean():.2e} max {d.max():.2e} p99 {np.quantile(d, 0.99):.2e} | logit mean {np.abs(logit - logit0).mean():.2e} max {np.abs(logit - logit0).max():.2e} | "
-                  f"token rms {np.sqrt((dt * dt).mean()):.2e} max {np.abs(dt).max():.2e}", flush=True)
+                  f"token rms {np.sqrt((dt * dt).mean()):.2e} max {np.abs(dt).max():.2e} | "
+                  f"CLS row rms {np.sqrt((dc * dc).mean()):.2e} max {np.abs(dc).max():.2e}, first and last image max {np.abs(dc[[0, -1]]).max():.2e}", flush=True)
         return
     if a.study == "hilo":
         # which matrices, kept exact (hi + lo planes, two MFMA passes) on top of the per-image compensation,

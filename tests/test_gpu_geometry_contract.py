@@ -13,12 +13,13 @@ seeded inputs of hypervla.synthetic.  Tolerances are the table at the top of tes
 
 Every case prints its figures before it asserts (DESIGN.md section 16 records one run).  What the contract refuses is asserted too:
 HVLA_E_SHAPE at create, never a crash and never a failure at the first launch."""
-import dataclasses
 import functools
 import gc
 
 import numpy as np
 import pytest
+
+from geometry_cases import ENCODER_P64, ENCODER_P256, _full, _mid
 
 pytestmark = pytest.mark.gpu
 
@@ -28,18 +29,6 @@ torch = pytest.importorskip("torch")
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X; torch.cuda.is_available() is False")
-
-
-def _mid(**kw):
-    """MID (P = 64: policy_kernel<2>, the small-batch encoder forms), every layer count but the encoder's at 1 unless the case says."""
-    from hypervla.config import MID
-    return dataclasses.replace(MID, **{**dict(layers=1, ctx_layers=1), **kw})
-
-
-def _full(**kw):
-    """The README widths (P = 256: policy_kernel<8>, the action row spread over all waves) with one layer of each kind."""
-    from hypervla.config import FULL
-    return dataclasses.replace(FULL, **{**dict(enc_layers=1, layers=1, ctx_layers=1), **kw})
 
 
 @functools.lru_cache(maxsize=2)
@@ -163,23 +152,6 @@ def test_context_edges(edge):
 
 
 # ------------------------------------------------------------------------------------------------ image encoder
-ENCODER_P64 = {
-    "E 256, mlp 640": dict(enc_dim=256, enc_heads=4, enc_mlp=640),
-    "patch 16, image 128": dict(patch=16, image_size=128),
-    "patch 4, image 32 (Kp = 128)": dict(patch=4, image_size=32),
-}
-ENCODER_P256 = {
-    "E 256 (one column tile per image)": (dict(enc_dim=256, enc_heads=4, enc_mlp=1024), "f16"),
-    "E 640, mlp 384": (dict(enc_dim=640, enc_heads=10, enc_mlp=384), "f16"),
-    "E 1024, mlp 1152": (dict(enc_dim=1024, enc_heads=16, enc_mlp=1152, enc_layers=1), "f16"),
-    "E 1024, mlp 1152, bf16": (dict(enc_dim=1024, enc_heads=16, enc_mlp=1152, enc_layers=1), "bf16"),
-    "E 128, mlp 128 (only QKV on the aligned path)": (dict(enc_dim=128, enc_heads=2, enc_mlp=128), "f16"),
-    "patch 8, image 128 (Kp = 384)": (dict(patch=8, image_size=128, enc_layers=1), "f16"),
-    "patch 7, image 112": (dict(patch=7, image_size=112, enc_layers=1), "f16"),
-    "no encoder layers": (dict(enc_layers=0), "f16"),
-}
-
-
 @pytest.mark.parametrize("B", [5, 40])
 @pytest.mark.parametrize("edge", sorted(ENCODER_P64))
 def test_encoder_edges_at_64_patches(edge, B):

@@ -155,6 +155,27 @@ def test_torch_encoder_expresses_every_accepted_mlp_width(widths):
     assert np.abs(got - ref).max() <= 1e-12, np.abs(got - ref).max()
 
 
+def test_hidden_state_bound_sees_a_missing_term_of_the_last_encoder_layer():
+    """tests/test_gpu_hidden_state.py holds the CLS row of hvla_encode_hidden to max |d| <= 2e-2 against this oracle (HIDDEN_F16_MAX
+    of tests/geometry_cases.py).  Nothing but the final LayerNorm reads the last layer's CLS row, so that bound is the only witness of the row's
+    out-projection and fc2 terms: here, at the README widths with two layers, dropping either term moves the oracle's CLS row by
+    at least 10 x the bound (0.79 and 2.65 measured).  A bound loosened past that would no longer see such a defect."""
+    import dataclasses
+    from geometry_cases import HIDDEN_F16_MAX
+    from hypervla.config import FULL
+    g = dataclasses.replace(FULL, enc_layers=2)
+    enc = dict(encoder_leaves(g))
+    P, x = syn.synthetic_params(g), onp.normalize_images(syn.synthetic_images(2, g)[:, 0])
+    ref = onp.dinov2(P, g, enc, x)
+    last = "encoder_image_encoder_encoder_layer_%d_" % (g.enc_layers - 1)
+    for leaf in ("attention_output_dense_kernel", "mlp_fc2_kernel"):
+        without = dict(P)
+        without[last + leaf] = np.zeros_like(P[last + leaf])
+        d = np.abs(onp.dinov2(without, g, enc, x)[:, 0] - ref[:, 0])
+        print("CLS row without the last layer's %s: max |d| %.2f rms %.2f" % (leaf, d.max(), np.sqrt((d * d).mean())))
+        assert d.max() >= 10 * HIDDEN_F16_MAX, (leaf, d.max())
+
+
 def test_t5_restatement_matches_transformers_torch_t5():
     """The float64 T5 encoder restatement against transformers' own torch T5EncoderModel (same architecture as the
     FlaxT5EncoderModel the reference calls) on random weights, incl. padding and the relative-position buckets."""
