@@ -740,6 +740,17 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* logits, const fl
   return HVLA_OK;
 }
 
+int hvla_loss_terms(hvla_ctx* ctx, const float* actions, const float* logits, const float* target, const uint8_t* tmask,
+                    const uint8_t* amask, float* continuous, float* gripper, float* sqerr, int32_t B, void* stream) {
+  if (!ctx) return HVLA_E_STATE;
+  if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
+  if (!actions || !logits || !target || !tmask || !amask || !continuous || !gripper || !sqerr) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, launch_loss_terms(actions, logits, target, tmask, amask, continuous, gripper, sqerr, nullptr, B, ctx->g.horizon,
+                                ctx->g.action_dim, ctx->g.max_action, ctx->g.clip_target != 0, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
 // the selection as an entry with this train_encoder value sees it: the position source is off unless the encoder is trained
 static TrainOptions train_options(const hvla_ctx* ctx, bool train_encoder) {
   TrainOptions o = ctx->train.sel;
@@ -934,6 +945,25 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
   if (!buf->grads || !buf->sqsum || !acc) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
   HIPCHK(ctx, train_accumulate(ctx->train.L, to_tb(buf), acc, inv_k, to_hp(hy), hy->train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
                                train_options(ctx, hy->train_encoder != 0)));
+  return HVLA_OK;
+}
+
+int hvla_train_metrics(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_train_metrics_in* in, float* out, int32_t B,
+                       int32_t train_encoder, void* stream) {
+  if (int rc = train_entry(ctx, buf && in, train_encoder != 0)) return rc;
+  if (in->struct_size != sizeof(hvla_train_metrics_in))
+    FAIL(ctx, HVLA_E_SHAPE, "hvla_train_metrics_in.struct_size %u: this library's is %zu", in->struct_size, sizeof(hvla_train_metrics_in));
+  if (!in->scratch || !out) FAIL(ctx, HVLA_E_SHAPE, "null scratch or out");
+  if (!buf->params || !buf->grads) FAIL(ctx, HVLA_E_SHAPE, "null pointer");
+  if (B < 1 || B > HVLA_TRAIN_METRICS_MAX_BATCH) FAIL(ctx, HVLA_E_SHAPE, "batch %d outside [1, %d]", B, HVLA_TRAIN_METRICS_MAX_BATCH);
+  if (!(in->select & (HVLA_METRICS_PRE | HVLA_METRICS_UPDATE)) || (in->select & ~(HVLA_METRICS_PRE | HVLA_METRICS_UPDATE)))
+    FAIL(ctx, HVLA_E_SHAPE, "select 0x%x: HVLA_METRICS_PRE | HVLA_METRICS_UPDATE", in->select);
+  if ((in->select & HVLA_METRICS_UPDATE) && !in->prev_params) FAIL(ctx, HVLA_E_SHAPE, "HVLA_METRICS_UPDATE needs prev_params");
+  if (in->n_tasks < 0) FAIL(ctx, HVLA_E_SHAPE, "n_tasks %d", in->n_tasks);
+  if (in->task_ids && in->n_tasks == 0) FAIL(ctx, HVLA_E_SHAPE, "task_ids given with n_tasks == 0");
+  if ((uintptr_t)in->scratch % 16 != 0) FAIL(ctx, HVLA_E_SHAPE, "scratch must be 16-byte aligned");
+  HIPCHK(ctx, train_metrics(ctx->g, ctx->train.L, to_tb(buf), *in, out, B, train_encoder != 0, reinterpret_cast<hipStream_t>(stream),
+                            train_options(ctx, train_encoder != 0)));
   return HVLA_OK;
 }
 

@@ -190,6 +190,13 @@ hipError_t launch_loss(const float* actions, const float* logits, const float* t
                        const uint8_t* amask, float* loss, int B, int horizon, int action_dim, float max_action,
                        bool clip_target, hipStream_t st);
 
+// ---------------------------------------------------------------- training metrics (metrics.hip, include/hvla.h hvla_loss_terms;
+// train_metrics, the body of hvla_train_metrics, is declared in train.h next to the structures it reads)
+// continuous / gripper f32 [B]; sqerr f32 [B] and sqerr64 f64 [B] nullable (the same f64 sum, rounded or not)
+hipError_t launch_loss_terms(const float* actions, const float* logits, const float* target, const uint8_t* tmask, const uint8_t* amask,
+                             float* continuous, float* gripper, float* sqerr, double* sqerr64, int B, int horizon, int action_dim,
+                             float max_action, bool clip_target, hipStream_t st);
+
 // ---------------------------------------------------------------- publish (publish.hip, include/hvla.h hvla_train_publish)
 // the flat training vector `params` into the serving buffers; the encoder's three only with train_encoder
 struct PublishArgs {

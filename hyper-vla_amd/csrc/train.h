@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/hvla.h"
 #include "layout.h"
 #include "train_layout.h"
 
@@ -120,5 +121,9 @@ hipError_t train_apply(const TrainLayout& L, const TrainBuffers& tb, const Train
                        const TrainOptions& opt);
 hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float* acc, float inv_k, const TrainHyper& hp,
                             bool train_encoder, hipStream_t st, const TrainOptions& opt);
+// hvla_train_metrics (metrics.hip): launches of its own, none of the three entries above changes by it.  Reads tb and `in`, writes
+// `out` and in.scratch only.  opt.ps / opt.frozen as for train_apply.
+hipError_t train_metrics(const Geom& g, const TrainLayout& L, const TrainBuffers& tb, const hvla_train_metrics_in& in, float* out, int B,
+                         bool train_encoder, hipStream_t st, const TrainOptions& opt);
 
 }  // namespace hvla

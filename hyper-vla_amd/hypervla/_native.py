@@ -27,7 +27,17 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
            "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses",
-           "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots"]
+           "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
+           "hvla_loss_terms", "hvla_train_metrics"]
+# hvla_train_metrics (include/hvla.h): select bits, the slots of its output vector, the size of its scratch
+HVLA_METRICS_PRE, HVLA_METRICS_UPDATE = 1, 2
+(HVLA_METRIC_TRAINING_LOSS, HVLA_METRIC_CONTINUOUS_LOSS, HVLA_METRIC_GRIPPER_LOSS, HVLA_METRIC_MSE, HVLA_METRIC_BASE_PARAMS_NORM,
+ HVLA_METRIC_ATTENTION_ENTROPY, HVLA_METRIC_ATTENTION_ALIGNMENT) = range(7)
+HVLA_METRIC_LOCAL_N = 7
+HVLA_METRIC_GRAD_NORM, HVLA_METRIC_PARAM_NORM, HVLA_METRIC_UPDATE_NORM = 7, 8, 9      # + 2 n_tasks
+HVLA_METRIC_N = 10
+HVLA_TRAIN_METRICS_WORKGROUPS, HVLA_TRAIN_METRICS_MAX_BATCH = 1024, 4096
+HVLA_TRAIN_METRICS_SCRATCH_DOUBLES = 4 * HVLA_TRAIN_METRICS_WORKGROUPS + 8 + 3 * HVLA_TRAIN_METRICS_MAX_BATCH
 HVLA_POST_DIM = 7
 HVLA_NORM_NORMAL, HVLA_NORM_BOUNDS = 0, 1
 HVLA_SETUP_LIBERO, HVLA_SETUP_WIDOWX_BRIDGE, HVLA_SETUP_GOOGLE_ROBOT = 0, 1, 2
@@ -74,6 +84,13 @@ class hvla_train_attention(C.Structure):
     """Options of hvla_train_attention_losses (include/hvla.h): struct_size must be sizeof(hvla_train_attention)."""
     _fields_ = [("struct_size", C.c_uint32), ("entropy_weight", C.c_float), ("alignment_weight", C.c_float),
                 ("reference_map", C.c_void_p), ("entropy", C.c_void_p), ("alignment", C.c_void_p)]
+
+
+class hvla_train_metrics_in(C.Structure):
+    """Inputs of hvla_train_metrics (include/hvla.h): struct_size must be sizeof(hvla_train_metrics_in)."""
+    _fields_ = [("struct_size", C.c_uint32), ("select", C.c_uint32), ("prev_params", C.c_void_p), ("target", C.c_void_p),
+                ("timestep_mask", C.c_void_p), ("action_mask", C.c_void_p), ("task_ids", C.c_void_p), ("n_tasks", C.c_int32),
+                ("entropy", C.c_void_p), ("alignment", C.c_void_p), ("encoder_sqsum", C.c_double), ("scratch", C.c_void_p)]
 
 
 class hvla_post_row(C.Structure):
@@ -145,6 +162,10 @@ def load_library():
     lib.hvla_ensemble.restype = C.c_int
     lib.hvla_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     lib.hvla_loss.restype = C.c_int
+    lib.hvla_loss_terms.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    lib.hvla_loss_terms.restype = C.c_int
+    lib.hvla_train_metrics.argtypes = [vp, C.POINTER(hvla_train_buffers), C.POINTER(hvla_train_metrics_in), vp, i32, i32, vp]
+    lib.hvla_train_metrics.restype = C.c_int
     lib.hvla_train_sizes.argtypes = [vp, i32, i32, C.POINTER(i64)]
     lib.hvla_train_sizes.restype = C.c_int
     lib.hvla_train_step.argtypes = [vp, C.POINTER(hvla_train_buffers), vp, vp, vp, vp, vp, vp, vp, vp, i32,
@@ -396,6 +417,21 @@ class Context:
     def train_accumulate(self, buf, acc_ptr, inv_k, hyper, stream=0):
         self._check(self.lib.hvla_train_accumulate(self.h, C.byref(buf), C.c_void_p(acc_ptr), C.c_float(inv_k), C.byref(hyper),
                                                    C.c_void_p(stream)), "hvla_train_accumulate")
+
+    def loss_terms(self, act_ptr, logit_ptr, target_ptr, tmask_ptr, amask_ptr, cont_ptr, grip_ptr, sqerr_ptr, B, stream=0):
+        """The two halves of hvla_loss per sample and the validation's squared error (device f32 [B] each)."""
+        self._check(self.lib.hvla_loss_terms(self.h, *[C.c_void_p(p or None) for p in (act_ptr, logit_ptr, target_ptr, tmask_ptr, amask_ptr,
+                                                                                       cont_ptr, grip_ptr, sqerr_ptr)],
+                                             B, C.c_void_p(stream)), "hvla_loss_terms")
+
+    def train_metrics(self, buf, select, out_ptr, B, train_encoder, scratch_ptr, prev_params_ptr=0, target_ptr=0, tmask_ptr=0,
+                      amask_ptr=0, task_ids_ptr=0, n_tasks=0, entropy_ptr=0, alignment_ptr=0, encoder_sqsum=0.0, stream=0):
+        """hvla_train_metrics: the reference's `info` of one step into the device vector at `out_ptr` (f32 [HVLA_METRIC_N + 2 n_tasks])."""
+        opts = hvla_train_metrics_in(C.sizeof(hvla_train_metrics_in), int(select), prev_params_ptr or None, target_ptr or None,
+                                     tmask_ptr or None, amask_ptr or None, task_ids_ptr or None, int(n_tasks), entropy_ptr or None,
+                                     alignment_ptr or None, float(encoder_sqsum), scratch_ptr or None)
+        self._check(self.lib.hvla_train_metrics(self.h, C.byref(buf), C.byref(opts), C.c_void_p(out_ptr or None), int(B),
+                                                int(bool(train_encoder)), C.c_void_p(stream)), "hvla_train_metrics")
 
     def train_publish(self, params_ptr, n_params, train_encoder=False, stream=0):
         """Pack the flat training vector at `params_ptr` (device f32 [n_params]) into this context's serving buffers, in place."""

@@ -278,6 +278,71 @@ def check_reference_attention(attention_map_alignment: float, reference_attentio
         raise ValueError(f"reference_attention must be [{batch}, {patches}], got {shape}")
 
 
+# The keys of the reference's `info` (scripts/train.py:506-529) that FineTuner.info() returns, in its order; one
+# `task_loss_<name>` per task follows, and the two attention terms are present only while their coefficient is positive.
+INFO_KEYS = ("training_loss", "grad_norm", "update_norm", "param_norm", "learning_rate", "continuous_loss", "gripper_loss",
+             "base_params_norm", "attention_entropy_loss", "attention_alignment_loss")
+# key -> (slot of hvla_train_metrics' vector, whether the slot is behind the 2 n_tasks task slots: the replicated block)
+_INFO_SLOT = {"training_loss": (_native.HVLA_METRIC_TRAINING_LOSS, False), "grad_norm": (_native.HVLA_METRIC_GRAD_NORM, True),
+              "update_norm": (_native.HVLA_METRIC_UPDATE_NORM, True), "param_norm": (_native.HVLA_METRIC_PARAM_NORM, True),
+              "continuous_loss": (_native.HVLA_METRIC_CONTINUOUS_LOSS, False), "gripper_loss": (_native.HVLA_METRIC_GRIPPER_LOSS, False),
+              "base_params_norm": (_native.HVLA_METRIC_BASE_PARAMS_NORM, False),
+              "attention_entropy_loss": (_native.HVLA_METRIC_ATTENTION_ENTROPY, False),
+              "attention_alignment_loss": (_native.HVLA_METRIC_ATTENTION_ALIGNMENT, False)}
+
+
+def resolve_task_index(task_index, task_names, batch: int) -> np.ndarray:
+    """int32 [batch]: the reference's `task_index` ({name: bool [B]}, scripts/train.py:455-456: one mask per dataset of the mix) as
+    one task id per sample, the position of the name in `task_names`; -1 for a sample no mask claims (counted nowhere).  ValueError: a
+    name that is not in `task_names`, a mask of another length, a sample two masks claim (an id cannot say that)."""
+    names = tuple(task_names)
+    ids = np.full(batch, -1, np.int32)
+    for name, mask in (task_index or {}).items():
+        if name not in names:
+            raise ValueError(f"task_index names {name!r}, task_names are {names!r}")
+        m = np.asarray(mask).astype(bool).reshape(-1)
+        if m.shape[0] != batch:
+            raise ValueError(f"task_index[{name!r}] has {m.shape[0]} entries, the batch has {batch}")
+        if (ids[m] >= 0).any():
+            b = int(np.nonzero(m & (ids >= 0))[0][0])
+            raise ValueError(f"task_index masks overlap: sample {b} is in {names[ids[b]]!r} and in {name!r}")
+        ids[m] = names.index(name)
+    return ids
+
+
+def reduce_info_vector(vec, n_tasks: int, world: int):
+    """The cross-rank half of the reference's `info` (scripts/train.py:498, 522-528), in place on hvla_train_metrics' vector (a device
+    or a CPU tensor, f32 [HVLA_METRIC_N + 2 n_tasks]): ONE all_reduce(SUM) over the rank-local means and the task sums and counts, then
+    the means divided by `world` (pmean; the sums and counts stay sums: psum).  The replicated block (grad, param and update norm) is
+    not touched: after the gradient all-reduce it is equal on every rank already.  Needs an initialised process group; returns vec."""
+    import torch.distributed as dist
+    local = _native.HVLA_METRIC_LOCAL_N
+    head = vec[:local + 2 * int(n_tasks)]
+    dist.all_reduce(head, op=dist.ReduceOp.SUM)
+    head[:local] /= world
+    return vec
+
+
+def info_from_vector(vec, task_names=(), learning_rate=None, attention_entropy=True, attention_alignment=True) -> Dict[str, object]:
+    """hvla_train_metrics' vector as the reference's `info` dict: 0-d views into `vec` (nothing is copied or synchronised), in
+    INFO_KEYS order, then `task_loss_<name>` = sum / count (NaN for a task without a sample, as the reference's 0 / 0)."""
+    n = len(tuple(task_names))
+    out = {}
+    for key in INFO_KEYS:
+        if key == "learning_rate":
+            if learning_rate is not None:
+                out[key] = learning_rate
+            continue
+        if (key == "attention_entropy_loss" and not attention_entropy) or (key == "attention_alignment_loss" and not attention_alignment):
+            continue
+        slot, replicated = _INFO_SLOT[key]
+        out[key] = vec[slot + (2 * n if replicated else 0)]
+    local = _native.HVLA_METRIC_LOCAL_N
+    for t, name in enumerate(task_names):
+        out[f"task_loss_{name}"] = vec[local + t] / vec[local + n + t]
+    return out
+
+
 class FineTuner:
     """One optimizer state of the fine-tune step.  Defaults are the README run's (README.md:29-31,61 and
     scripts/configs/hypervla_pretrain_config.py:286-321): weight_decay_strategy v5, learning rate 3e-4 (rsqrt) for the
@@ -289,14 +354,18 @@ class FineTuner:
     `attention_entropy`, `attention_map_alignment`: the coefficients of `config.auxiliary_loss` (scripts/train.py:348-373, default 0 =
     off): the entropy of the action token's attention row in the last policy layer, and its squared distance to `reference_attention`
     (forward_backward / step; `model.reference_attention_map(images)`), annealed by 1 - step_count / `num_steps`.  Both are added to
-    every sample's loss; `aux_metrics` holds the un-weighted terms of the last step under the reference's metric names."""
+    every sample's loss; `aux_metrics` holds the un-weighted terms of the last step under the reference's metric names.
+    `metrics=True` (default off: nothing is allocated and step / apply do exactly what they do without it): what the reference logs
+    every step (scripts/train.py:494-529), computed on the device by hvla_train_metrics around the optimizer and read with `info()`;
+    costs one more [n] f32 vector (the snapshot for update_norm).  `task_names`: the datasets of the mix, for `task_loss_<name>`
+    (`forward_backward(task_index=...)`)."""
 
     def __init__(self, model, batch: int, peak_lr: float = 3e-4, weight_decay: float = 0.05, clip: float = 1.0,
                  ema_decay: float = 0.999, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
                  accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
-                 attention_map_alignment: float = 0.0, num_steps=None):
+                 attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=()):
         self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
             attention_entropy, attention_map_alignment, num_steps)
         if getattr(model.geometry, "lang_in_policy", False):
@@ -369,6 +438,44 @@ class FineTuner:
         self.peak_lr, self.base_peak_lr, self.step_count = peak_lr, base_lr, 0
         self.ema_start_step = int(ema_start_step)
         self._bucket_setup()
+        self.metrics = bool(metrics)
+        self.task_names = tuple(task_names)
+        if self.task_names and not self.metrics:
+            raise ValueError("task_names are the names of info()'s task_loss_<name>: they need metrics=True")
+        if len(set(self.task_names)) != len(self.task_names):
+            raise ValueError(f"task_names {self.task_names!r} repeat a name")
+        self.prev_params = None                         # the snapshot for update_norm; validate() borrows it as its gradient sink
+        self._val = None                                # validate()'s outputs and its two hvla_train_buffers, on first use
+        if self.metrics:
+            self._metrics_setup()
+
+    def _metrics_setup(self):
+        """The buffers of hvla_train_metrics: its output vector (NaN until a step fills a slot), its scratch, the snapshot of the
+        parameters, and -- frozen encoder -- the sum of squares of the shared DINOv2 leaves that every sample's dict_base_params
+        carries (scripts/train.py:384), once in float64 from the model's host tensors."""
+        torch, dev = self.torch, self.model.device
+        nt = len(self.task_names)
+        self.metric_vec = torch.full((_native.HVLA_METRIC_N + 2 * nt,), float("nan"), dtype=torch.float32, device=dev)
+        self.metric_reduced = None                      # info(reduce=True) under several ranks: the all-reduced copy
+        self.metric_scratch = torch.empty(_native.HVLA_TRAIN_METRICS_SCRATCH_DOUBLES, dtype=torch.float64, device=dev)
+        self.prev_params = torch.empty(self.n, dtype=torch.float32, device=dev)
+        self.task_ids = None
+        self.encoder_sqsum = 0.0
+        if not self.train_encoder:
+            self.encoder_sqsum = float(sum((np.asarray(self.model.params[shared_name(path)], np.float64) ** 2).sum()
+                                           for path, _ in encoder_leaves(self.g)))
+        self._last_lr = None
+
+    def _metrics_call(self, select):
+        """hvla_train_metrics on this step's buffers (always the micro-batch's own `grads`, also under gradient accumulation)."""
+        tok, msk, cls, obs, tgt, am, tm = self._keep
+        wa_on = "attention_alignment_loss" in self.aux_metrics
+        self.model._ctx.train_metrics(
+            self.buf, select, self.metric_vec.data_ptr(), self.B, self.train_encoder, self.metric_scratch.data_ptr(),
+            prev_params_ptr=self.prev_params.data_ptr(), target_ptr=tgt.data_ptr(), tmask_ptr=tm.data_ptr(), amask_ptr=am.data_ptr(),
+            task_ids_ptr=self.task_ids.data_ptr() if self.task_ids is not None else 0, n_tasks=len(self.task_names),
+            entropy_ptr=self.aux_entropy.data_ptr() if self.aux_entropy is not None else 0,
+            alignment_ptr=self.aux_alignment.data_ptr() if wa_on else 0, encoder_sqsum=self.encoder_sqsum, stream=self.model._stream())
 
     def _select(self, reference=None, attention=False):
         """What every call into the context starts with, in this order (the mask's length depends on the source); in front of a
@@ -440,11 +547,15 @@ class FineTuner:
                                         h["base_weight_decay"], int(self.train_encoder))
 
     def forward_backward(self, instruction_dict, initial_state, tokens_or_images, batch, forward_only=False,
-                         reference_attention=None):
+                         reference_attention=None, task_index=None):
         """loss [B] (device) after writing self.grads = d mean(loss) / d params.  The fourth argument is the frozen
         encoder's patch tokens f32 [B, P, E], or -- with train_encoder -- the uint8 observations [B, (1,) H, W, 3].
-        `reference_attention` (device or host float32 [B, P]; needed iff attention_map_alignment > 0): the alignment term's target."""
+        `reference_attention` (device or host float32 [B, P]; needed iff attention_map_alignment > 0): the alignment term's target.
+        `task_index` (metrics=True): {name: bool [B]} as the reference passes it (scripts/train.py:406, 455-456), names from `task_names`."""
         check_reference_attention(self.attention_map_alignment, reference_attention, self.B, self.g.patches)
+        if task_index is not None and not self.metrics:
+            raise ValueError("task_index feeds info()'s task_loss_<name>: it needs FineTuner(metrics=True, task_names=...)")
+        ids = resolve_task_index(task_index, self.task_names, self.B) if self.metrics and self.task_names else None
         torch, m, g = self.torch, self.model, self.g
         li = instruction_dict["language_instruction"]
         if "token_embedding" not in li:                    # frozen T5 inside the step, as scripts/train.py:407-415
@@ -472,6 +583,8 @@ class FineTuner:
         ref = m._dev(reference_attention, torch.float32) if self.attention_map_alignment > 0 else None
         self._keep = (tok, msk, cls, obs, tgt, am, tm)
         self._keep_reference = ref
+        if self.metrics:
+            self.task_ids = m._dev(ids, torch.int32) if ids is not None else None
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
         wa = self._select(ref, attention=True)
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
@@ -512,8 +625,22 @@ class FineTuner:
     def apply(self, lr=None, base_lr=None):
         """Gradient all-reduce, then the optimizer: chain(clip_by_global_norm, [MultiSteps](adamw)) and the EMA.  With
         grad_accumulation_steps = k the clipped gradient of every micro-batch goes into a running mean and parameters move
-        on every k-th call only (optax.MultiSteps, octo/utils/train_utils.py:420-421); returns True when they moved."""
+        on every k-th call only (optax.MultiSteps, octo/utils/train_utils.py:420-421); returns True when they moved.
+        With metrics=True hvla_train_metrics runs twice round it: everything but update_norm after the all-reduce and before the
+        optimizer (the reference logs param_norm of the parameters before the update), then the snapshot of `params`, the optimizer,
+        and update_norm = |params - snapshot| (zero on a micro-step that moved nothing)."""
         self.all_reduce_gradient()
+        if not self.metrics:
+            return self._optimizer(lr, base_lr)
+        self._select()
+        self._metrics_call(_native.HVLA_METRICS_PRE)
+        self.prev_params.copy_(self.params)
+        self._last_lr = lr_rsqrt(self.step_count, self.peak_lr) if lr is None else lr
+        moved = self._optimizer(lr, base_lr)
+        self._metrics_call(_native.HVLA_METRICS_UPDATE)            # (the optimizer left the context's selection as it is)
+        return moved
+
+    def _optimizer(self, lr=None, base_lr=None):
         ctx, st = self.model._ctx, self.model._stream()
         self._select()
         if self.accum_k > 1:
@@ -537,12 +664,102 @@ class FineTuner:
         self.step_count += 1
         return True
 
-    def step(self, instruction_dict, initial_state, images, batch, lr=None, base_lr=None, reference_attention=None):
+    def step(self, instruction_dict, initial_state, images, batch, lr=None, base_lr=None, reference_attention=None, task_index=None):
         check_reference_attention(self.attention_map_alignment, reference_attention, self.B, self.g.patches)
         obs = images if self.train_encoder else self.model.encode_images(images)
-        loss = self.forward_backward(instruction_dict, initial_state, obs, batch, reference_attention=reference_attention)
+        loss = self.forward_backward(instruction_dict, initial_state, obs, batch, reference_attention=reference_attention,
+                                     task_index=task_index)
         self.apply(lr, base_lr)
         return loss.mean()
+
+    def info(self, reduce: bool = True) -> Dict[str, object]:
+        """The reference's `info` of the last step (scripts/train.py:506-529) under its key names (INFO_KEYS, `task_loss_<name>`):
+        0-d device tensors, views into hvla_train_metrics' vector -- nothing synchronises until the caller reads one, and the next
+        step overwrites them.  With a process group of more than one rank and `reduce`, the rank-local means and the task sums and
+        counts are all-reduced first (reduce_info_vector: one collective, into a copy)."""
+        if not self.metrics:
+            raise RuntimeError("info() needs FineTuner(metrics=True)")
+        import torch.distributed as dist
+        vec = self.metric_vec
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if self.metric_reduced is None:
+                self.metric_reduced = self.torch.empty_like(vec)
+            self.metric_reduced.copy_(vec)
+            vec = reduce_info_vector(self.metric_reduced, len(self.task_names), dist.get_world_size())
+        lr = None if self._last_lr is None else self.torch.full((), float(self._last_lr), dtype=self.torch.float32, device=vec.device)
+        return info_from_vector(vec, self.task_names, lr, self.attention_entropy > 0, self.attention_map_alignment > 0)
+
+    def _validation_buffers(self):
+        """validate()'s own outputs and its two hvla_train_buffers (params / the EMA).  A forward-only hvla_train_step still zeroes the
+        vector `grads` points at: that is the snapshot vector of the metrics (free between two apply calls), so `self.grads` keeps
+        its bits; a tuner without metrics gets that vector here, on the first validation."""
+        if self._val is None:
+            torch, dev = self.torch, self.model.device
+            f32 = dict(dtype=torch.float32, device=dev)
+            if self.prev_params is None:
+                self.prev_params = torch.empty(self.n, **f32)
+            out = dict(loss=torch.zeros(self.B, **f32), actions=torch.zeros(self.B, self.g.horizon, self.g.action_dim, **f32),
+                       logits=torch.zeros(self.B, self.g.horizon, **f32), terms=torch.zeros(3, self.B, **f32))
+            bufs = {}
+            for ema, vec in ((False, self.params), (True, self.ema)):
+                bufs[ema] = _native.hvla_train_buffers(*[t.data_ptr() if t is not None else None for t in (
+                    vec, self.prev_params, self.mu, self.nu, None, self.theta, self.dtheta, self.work, out["loss"], out["actions"],
+                    out["logits"], self.sqsum, self.wd_mask, self.params0)])
+            self._val = (out, bufs)
+        return self._val
+
+    def validate(self, instruction_dict, initial_state, images, batch, ema: bool = False) -> Dict[str, object]:
+        """The reference's `validation_action_loss` (scripts/train.py:546-583) on one batch: {"mse": 0-d device tensor} =
+        mean((predicted - clip(action, -5, 5))^2) * action_dim over every sample, step and dimension, unmasked, the gripper column
+        being the thresholded prediction.  A forward-only step on `params`, or with `ema` on their moving average (what the reference
+        evaluates, data/simpler/evaluate.py:440-444), then hvla_loss_terms.  Writes no gradient, no optimizer state and no counter,
+        and leaves `loss`, `actions`, `logits`, `aux_metrics` and the metrics of the last step alone (the attention terms are off
+        for it: they are no part of the mse); `theta` and the workspace are shared with the step, so call it between steps, not
+        between forward_backward and apply.  Arguments as `step`."""
+        torch, m, g = self.torch, self.model, self.g
+        out, bufs = self._validation_buffers()
+        li = instruction_dict["language_instruction"]
+        if "token_embedding" not in li:
+            li = m.encode_instructions(li)
+        tok = m._dev(li["token_embedding"], torch.float32)
+        msk = m._dev(li["attention_mask"], torch.int64)
+        cls = m._dev(np.asarray(initial_state["patch_embeddings"])[:, 0], torch.float32)
+        if self.train_encoder:
+            img = images if torch.is_tensor(images) else np.asarray(images)
+            if img.ndim == 5:
+                img = img[:, 0]
+            obs = m._dev(img, torch.uint8)
+            assert tuple(obs.shape) == (self.B, g.image_size, g.image_size, 3), obs.shape
+            tkn_ptr, img_ptr = None, obs.data_ptr()
+        else:
+            obs = m.encode_images(images)
+            assert tuple(obs.shape) == (self.B, g.patches, g.enc_dim), obs.shape
+            tkn_ptr, img_ptr = obs.data_ptr(), None
+        tgt = m._dev(np.asarray(batch["action"])[:, 0], torch.float32)
+        am = m._dev(np.asarray(batch["action_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
+        tm = m._dev(np.asarray(batch["timestep_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
+        assert tok.shape[0] == self.B
+        self._select_source()
+        self._select_frozen()
+        m._ctx.train_attention_losses()                 # off; the next step selects its own again
+        ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
+        m._ctx.train_step(bufs[bool(ema)], ptrs, self.B, self._hyper(0.0, True), m._stream())
+        t = out["terms"]
+        m._ctx.loss_terms(out["actions"].data_ptr(), out["logits"].data_ptr(), tgt.data_ptr(), tm.data_ptr(), am.data_ptr(),
+                          t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), self.B, m._stream())
+        return {"mse": (t[2].double().mean() / g.horizon).float()}
+
+    def validate_batches(self, batches, ema: bool = False) -> Dict[str, object]:
+        """`ValidationCallback`'s average over a validation set: `batches` yields (instruction_dict, initial_state, images, batch);
+        the mean of validate()'s metrics over them, accumulated on the device (one tensor per key, read by the caller)."""
+        total, count = {}, 0
+        for instruction_dict, initial_state, images, batch in batches:
+            for k, v in self.validate(instruction_dict, initial_state, images, batch, ema=ema).items():
+                total[k] = v.double() if k not in total else total[k] + v.double()
+            count += 1
+        if not count:
+            raise ValueError("validate_batches: no batch")
+        return {k: (v / count).float() for k, v in total.items()}
 
     def publish(self, ema: bool = False, host_copy: bool = True, audit: bool = False):
         """Serve the fine-tuned weights in place (`hvla_train_publish`): the parameters, or with `ema` their moving average

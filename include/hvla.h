@@ -447,6 +447,89 @@ typedef struct hvla_train_attention {
 } hvla_train_attention;
 int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts);   /* NULL: off */
 
+/* Replaces: the `metrics` of MixActionHead.loss (hypervla/components/action_heads.py:517-521: `continuous_loss`, `gripper_loss`) per
+ * sample, and the numerator of `validation_action_loss` (scripts/train.py:578-581).  Arguments as hvla_loss (actions / gripper_logits
+ * as hvla_train_step, hvla_policy or hvla_step wrote them); all outputs device f32 [B]:
+ *   continuous[b] = (action_dim - 1) * masked-MSE,  gripper[b] = masked sigmoid-BCE  -- the two terms whose sum hvla_loss and
+ *                   hvla_train_step store (same expressions: the 1e-5 floor on the mask means, the target clipped to +-max_action
+ *                   iff hvla_config.clip_target, log1p(exp(-|z|))), summed in the order of the step's own loss kernel;
+ *   sqerr[b]      = sum_{h,a} (actions - clip(target, -5, 5))^2 over every step and dimension, NO mask, the gripper column being the
+ *                   0 / 1 threshold `actions` holds; the clip is the literal +-5 of scripts/train.py:580, not max_action.  Accumulated
+ *                   in f64, rounded once.  `mse` of the reference = mean_b sqerr[b] / horizon (its `.mean() * action_dim`).
+ * No allocation, no host synchronisation, bit-reproducible.  HVLA_E_SHAPE: B < 1, a NULL pointer.                                   */
+int hvla_loss_terms(hvla_ctx* ctx, const float* actions, const float* gripper_logits, const float* target,
+                    const uint8_t* timestep_mask, const uint8_t* action_mask, float* continuous, float* gripper, float* sqerr,
+                    int32_t B, void* stream);
+
+/* Replaces: the `info` dict of `train_step_pmap` (scripts/train.py:494-529: training_loss, grad_norm, update_norm, param_norm, the
+ * per-sample `metrics` of sample_loss_fn :346-384 averaged, `task_loss_<name>` :455-456,522-525) and `param_norm_callable`
+ * (octo/utils/train_utils.py:437-441), computed on the device from the buffers of the step -- nothing is copied to the host.
+ * out (device f32 [HVLA_METRIC_N + 2 n_tasks]), one HVLA_METRIC_* index per slot:
+ *   the rank-local block [0, HVLA_METRIC_LOCAL_N): means over the B samples of this rank --
+ *     TRAINING_LOSS = mean buf->loss;  CONTINUOUS_LOSS, GRIPPER_LOSS = means of hvla_loss_terms' terms on buf->actions / buf->logits;
+ *     MSE = mean_b sqerr[b] / horizon;  BASE_PARAMS_NORM = mean_b sqrt(sum theta_b^2 + enc_sq), enc_sq the sum of squares of the shared
+ *     DINOv2 leaves every sample's dict_base_params carries (scripts/train.py:384): with train_encoder taken from buf->params (the
+ *     position table as its source while hvla_train_position_source is on, else as the baked table), else `encoder_sqsum`;
+ *     ATTENTION_ENTROPY, ATTENTION_ALIGNMENT = means of `entropy` / `alignment`;
+ *   then n_tasks sums  sum_b loss[b] [task_ids[b] == t]  and n_tasks counts (the reference divides after its psum; an id outside
+ *     [0, n_tasks) is counted nowhere, the episode pool's skip rule);
+ *   then the replicated block (equal on every rank after the gradient all-reduce), at HVLA_METRIC_<NAME> + 2 n_tasks:
+ *     GRAD_NORM  = |buf->grads|, EVERY element as it stands (optax.global_norm(grads) of the averaged gradient, before the clip):
+ *                  frozen elements of a computed bucket included.  Deviation: a bucket DECLARED frozen (hvla_train_frozen) was not
+ *                  computed and contributes zeros, where the reference's norm includes its gradient.  The baked position slot's
+ *                  gradient is zero by construction.  buf->sqsum[0], the clip's own sum, is f32 with atomics and over trainable
+ *                  elements only: it differs from GRAD_NORM^2 by that rounding (and by the frozen elements);
+ *     PARAM_NORM = |buf->params| without the elements whose frozen byte is set (param_norm_callable zeroes frozen leaves) and, while
+ *                  the position source is on, without the baked slot (a derived quantity; the source tail is the parameter);
+ *     UPDATE_NORM = |buf->params - prev_params| without the baked slot: optax.global_norm(updates), delta decay included; zero on a
+ *                  micro-step of gradient accumulation that moved nothing.
+ * select: HVLA_METRICS_PRE fills everything but UPDATE_NORM (call it after the gradient all-reduce and before hvla_train_apply: the
+ * reference logs param_norm of the parameters before the update); HVLA_METRICS_UPDATE fills UPDATE_NORM (after hvla_train_apply, with
+ * prev_params the snapshot taken before it).  A slot that is not selected, or whose inputs are NULL (target / masks / buf->actions /
+ * buf->logits for the three loss terms, buf->theta, entropy, alignment, task_ids), is not written.
+ * Every sum runs in a fixed order without atomics, in f64, rounded to f32 once: `out` is a function of the data alone and each value
+ * within one f32 rounding of the exact one.  Allocates nothing, does not synchronise with the host, launches on `stream` only,
+ * writes only `out` and `scratch` (HVLA_TRAIN_METRICS_SCRATCH_DOUBLES doubles, contents undefined between calls); may be captured.
+ * Follows the hvla_train_* rules: the geometry refusal first, the position source and the frozen mask held on the context are
+ * honoured, HVLA_E_STATE while the mask was set for the other train_encoder value.  HVLA_E_SHAPE before any launch: struct_size !=
+ * sizeof(hvla_train_metrics_in), NULL scratch or out, NULL buf->params or buf->grads, B outside [1, HVLA_TRAIN_METRICS_MAX_BATCH],
+ * select without a bit of HVLA_METRICS_PRE | HVLA_METRICS_UPDATE or with another, UPDATE without prev_params, n_tasks < 0, task_ids
+ * given with n_tasks == 0, a scratch that is not 16-byte aligned.                                                                  */
+#define HVLA_METRICS_PRE 1u
+#define HVLA_METRICS_UPDATE 2u
+#define HVLA_METRIC_TRAINING_LOSS 0
+#define HVLA_METRIC_CONTINUOUS_LOSS 1
+#define HVLA_METRIC_GRIPPER_LOSS 2
+#define HVLA_METRIC_MSE 3
+#define HVLA_METRIC_BASE_PARAMS_NORM 4
+#define HVLA_METRIC_ATTENTION_ENTROPY 5
+#define HVLA_METRIC_ATTENTION_ALIGNMENT 6
+#define HVLA_METRIC_LOCAL_N 7              /* the rank-local block; task sums at [7, 7 + n_tasks), counts behind them      */
+#define HVLA_METRIC_GRAD_NORM 7            /* + 2 n_tasks                                                                  */
+#define HVLA_METRIC_PARAM_NORM 8           /* + 2 n_tasks                                                                  */
+#define HVLA_METRIC_UPDATE_NORM 9          /* + 2 n_tasks                                                                  */
+#define HVLA_METRIC_N 10
+#define HVLA_TRAIN_METRICS_WORKGROUPS 1024 /* the norm pass's grid, whatever n_params is                                   */
+#define HVLA_TRAIN_METRICS_MAX_BATCH 4096
+/* partial sums 4 x WORKGROUPS | 8 totals | row sums, squared errors and the two loss terms, MAX_BATCH each                    */
+#define HVLA_TRAIN_METRICS_SCRATCH_DOUBLES (4 * HVLA_TRAIN_METRICS_WORKGROUPS + 8 + 3 * HVLA_TRAIN_METRICS_MAX_BATCH)
+typedef struct hvla_train_metrics_in {
+  uint32_t struct_size;            /* = sizeof(hvla_train_metrics_in): the exact-size rule of hvla_policy_options         */
+  uint32_t select;                 /* HVLA_METRICS_PRE | HVLA_METRICS_UPDATE                                               */
+  const float* prev_params;        /* device f32 [n_params]: params before hvla_train_apply; needed for UPDATE             */
+  const float* target;             /* as given to hvla_train_step, or NULL                                                 */
+  const uint8_t* timestep_mask;
+  const uint8_t* action_mask;
+  const int32_t* task_ids;         /* device i32 [B] in [0, n_tasks), or NULL                                              */
+  int32_t n_tasks;
+  const float* entropy;            /* device f32 [B]: hvla_train_attention_losses' outputs, or NULL                        */
+  const float* alignment;
+  double encoder_sqsum;            /* frozen encoder: sum of squares of the shared DINOv2 leaves; ignored with train_encoder */
+  double* scratch;                 /* device, HVLA_TRAIN_METRICS_SCRATCH_DOUBLES doubles, 16-byte aligned                  */
+} hvla_train_metrics_in;
+int hvla_train_metrics(hvla_ctx* ctx, const hvla_train_buffers* buf, const hvla_train_metrics_in* in, float* out, int32_t B,
+                       int32_t train_encoder, void* stream);
+
 /* Replaces: InferenceWrapper._resize_image (data/utils/hypervla_interface.py:89-121): optionally
  * tf.image.resize_with_pad(image, 256, 320) (bilinear, zero padding; `padded_resize`), then
  * tf.image.resize(lanczos3, antialias=True) to image_size x image_size, optionally the centred sqrt(0.9)
