@@ -62,6 +62,7 @@ struct TrainState {               // what the hvla_train_* entries keep per cont
                                   // table is the parameter), hvla_train_frozen (mask and wholly frozen buckets), hvla_train_attention_losses
   int64_t frozen_n = 0;           // the mask's length, one of the two of hvla_train_sizes when it was set ...
   bool frozen_enc = false;        //   ... namely the one of this train_encoder value
+  bool language_tokens = false;   // hvla_train_language_tokens: the entries serve this use_language_token context
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
 };
@@ -775,9 +776,9 @@ static int frozen_fits(hvla_ctx* ctx, bool train_encoder) {
 // context) and, for the entries that read the frozen mask (frozen_for = their train_encoder value, else -1), that the mask fits.
 static int train_entry(hvla_ctx* ctx, bool args = true, int frozen_for = -1) {
   if (!ctx || !args) return HVLA_E_STATE;
-  if (const char* why = train_refusal(ctx->g)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
   TrainState& t = ctx->train;
+  if (const char* why = train_refusal(ctx->g, t.language_tokens)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!t.have_layout) { t.L = make_train_layout(ctx->g); t.have_layout = true; }
   if (!t.L.policy_ok) FAIL(ctx, HVLA_E_STATE, "the generated policy has no leaf of a name the training path reads");
   return frozen_for < 0 ? HVLA_OK : frozen_fits(ctx, frozen_for != 0);
@@ -851,11 +852,21 @@ int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts)
   if (!ctx) return HVLA_E_STATE;
   if (!opts) { ctx->train.sel.aux = AttnAux(); return HVLA_OK; }
   if (int rc = train_entry(ctx)) return rc;
+  if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the attention terms are not defined with use_language_token: the action row has T + P keys, the reference map P");
   if (opts->struct_size != sizeof(hvla_train_attention)) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_attention.struct_size %u: this library's is %zu", opts->struct_size, sizeof(hvla_train_attention));
   const float we = opts->entropy_weight, wa = opts->alignment_weight;
   if (!std::isfinite(we) || !std::isfinite(wa) || we < 0.f || wa < 0.f) FAIL(ctx, HVLA_E_SHAPE, "attention loss weights (%g, %g) must be finite and >= 0", (double)we, (double)wa);
   if (wa > 0.f && !opts->reference_map) FAIL(ctx, HVLA_E_SHAPE, "alignment_weight %g > 0 needs reference_map [B, P]", (double)wa);
   ctx->train.sel.aux = AttnAux{we, wa, opts->reference_map, opts->entropy, opts->alignment};
+  return HVLA_OK;
+}
+
+int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on) {
+  if (!ctx) return HVLA_E_STATE;
+  if (on == 0) { ctx->train.language_tokens = false; return HVLA_OK; }
+  if (on != 1) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_language_tokens(%d): 0 or 1", on);
+  if (!ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_language_tokens(1) on a context created without use_language_token");
+  ctx->train.language_tokens = true;
   return HVLA_OK;
 }
 

@@ -745,6 +745,29 @@ __global__ void softmax_fwd_kernel(float* __restrict__ p, int nmat, int R, int C
   const float inv = 1.f / sum;
   for (int k = lane; k < Cc; k += 64) pr[k] *= inv;
 }
+// The policy's mask under use_language_token (base_vit.py:209-214) on [nmat][S][S], S = T + P + 1: a language query q < T keeps only
+// the language keys k < T, and no query but the last keeps key S - 1 (T == 0 would be mode 0 above).  The row's arithmetic is the
+// kernel's above; a kernel of its own so that the one above keeps its arguments and its code.
+__global__ void softmax_lang_fwd_kernel(float* __restrict__ p, int nmat, int S, int T, int ld) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nmat * S) return;
+  const int q = row % S;
+  float* pr = p + (long)row * ld;
+  if (lane < ld - S) pr[S + lane] = 0.f;
+  auto keep = [&](int k) { return q < T ? k < T : (q == S - 1 || k < S - 1); };
+  float mx = -3.4e38f;
+  for (int k = lane; k < S; k += 64) if (keep(k)) mx = fmaxf(mx, pr[k]);
+  for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float sum = 0.f;
+  for (int k = lane; k < S; k += 64) {
+    const float e = keep(k) ? __expf(pr[k] - mx) : 0.f;
+    pr[k] = e;
+    sum += e;
+  }
+  for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  const float inv = 1.f / sum;
+  for (int k = lane; k < S; k += 64) pr[k] *= inv;
+}
 
 // ds = p * (dp - sum_k dp p), in place on dp
 __global__ void softmax_bwd_kernel(const float* __restrict__ p, float* __restrict__ dp, int rows, int Cc, int ld) {
@@ -849,7 +872,8 @@ __global__ __launch_bounds__(CSB_WAVES * 64) void colsum4b_kernel(const float* _
   }
 }
 
-// x0 assembly: rows < P already hold tokens.Wp + bp; row P = 0; += pos  (base_vit.py:182-204)
+// x0 assembly: rows < S - 1 already hold the projections (tokens.Wp + bp, under use_language_token tok.Wl + bl in front of them);
+// row S - 1 = 0; += pos  (base_vit.py:159-166,182-204)
 __global__ void x0_finish_kernel(float* __restrict__ x, const float* __restrict__ pos, long pstride, int S, int D, int nb) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)nb * S * D) return;
@@ -1208,7 +1232,7 @@ template <class T> static Blk<T> bind(T* base, const BlockLeaves& y) {
 }
 // block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
 // HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention)
-struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; };
+struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; };     // lang_T > 0: the policy's mask with T language rows in front
 struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y; };
 
 // Y[nb][S][N] (+)= X[nb][S][K] W + bias with W per episode (ws = G) or shared (ws = 0: the batch folds into M, so
@@ -1263,7 +1287,8 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   // products per layer were left with cost 3.6 ms per step)
   const int Sp = (S + 3) & ~3;
   bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
-  KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
+  if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
+  else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
   {
     BG pv{a.p, a.v, a.o, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
     pv.a_padded = 1;
@@ -1382,7 +1407,11 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   if (one) bgemm(st, true, false, BG{h, dqkv[ord[0]], gWm[ord[0]], nullptr, D, D, rows, D, D, D, 0, 0, 0, dys, 0, gws, 0, 3, 1.f, 1, 1, 1}, 1);
   for (int i = 0; i < 3; ++i) {
     if (!one) wgrad(h, D, dqkv[i], D, gWm[i]);
-    bgrad(dqkv[i], D, gBm[i]);
+    // The key bias adds q . bk / sqrt(hd) to every kept score of a query's row, and a softmax row ignores a constant: its gradient is
+    // zero under any mask (sum_k ds[q][k] = 0).  What the column sum of dk gives instead is the operand rounding of ds in dk = ds^T q,
+    // and a language query's few keys carry ds entries of the size of dp: with the language rows the leaf is left at the zero it is
+    // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.
+    if (!(op.lang_T > 0 && i == 1)) bgrad(dqkv[i], D, gBm[i]);
     linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0);                                                         // dh
   }
   ln_bwd(a.x_in, t.g, a.mean0, a.rstd0, w.l0s, gw.l0s, gw.l0b);
@@ -1416,7 +1445,7 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
     b.h = take(nb * s * d); b.h2 = take(nb * s * d); b.g = take(nb * s * f);
     return b;
   };
-  const long S = g.S(), D = g.D, H = g.H, F = g.M, Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;
+  const long S = g.pos_rows(), D = g.D, H = g.H, F = g.M, Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;     // S: the policy's rows, T + P + 1 under use_language_token
   const long Se = g.P() + 1, E = g.E, He = g.enc_heads, Fe = g.enc_mlp;
   pl.cb.resize(g.ctx_layers); pl.pb.resize(g.L); pl.eb.resize(enc ? g.enc_layers : 0);
   for (auto& b : pl.cb) b = take_blk(B, Sc, C, Hc, Fc, false);
@@ -1484,7 +1513,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const PosSource& ps = opt.ps;
   const AttnAux& aux = opt.aux;
   const int frozen_buckets = opt.frozen_buckets;
-  const int S = g.S(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
+  const int Tl = g.lang_in_policy ? g.T : 0;       // use_language_token: the policy's rows are [Tl language | P patches | 1 action]
+  const int S = g.pos_rows(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
   const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
   const bool enc = in.images != nullptr;
@@ -1501,7 +1531,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
   ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
-  const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0}, enc_opt{2, nullptr, 1};
+  const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0, Tl}, enc_opt{2, nullptr, 1};
 
   // =============================== DINOv2 forward in f32, activations kept (HF Dinov2Model; base_vit.py:111-131) =====
   const float* tokens = in.tokens;         // [B][P][E] rows, episode stride tok_stride
@@ -1534,7 +1564,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // =============================== policy forward with per-episode weights ===============================
   const float* TH = tb.theta;
   float* px0 = pb[0].x_in;
-  bgemm(st, false, false, BG{tokens, TH + L.wp, px0, TH + L.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
+  // rows [0, Tl) = token_embedding_b Wl_b + bl_b, every position (base_vit.py:159-166 masks nothing); the patches follow at row Tl
+  if (Tl) bgemm(st, false, false, BG{in.tok, TH + L.wl, px0, TH + L.bl, Tl, D, g.lang_dim, g.lang_dim, D, D, (long)Tl * g.lang_dim, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
+  bgemm(st, false, false, BG{tokens, TH + L.wp, px0 + (long)Tl * D, TH + L.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
   KL(x0_finish_kernel, g1((long)B * S * D), dim3(256), px0, TH + L.pos, G, S, D, B);
   for (int l = 0; l < g.L; ++l)
     block_fwd(st, B, S, D, H, F, G, bind(TH, L.pol[l]), pb[l], l + 1 < g.L ? pb[l + 1].x_in : px_fin, t, pol_opt);
@@ -1554,16 +1586,21 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // =============================== policy backward ===============================
   for (int l = g.L - 1; l >= 0; --l)
     block_bwd(st, B, S, D, H, F, G, G, bind(TH, L.pol[l]), bind(tb.dtheta, L.pol[l]), pb[l], pdx, t, pol_opt, aux.on() && l == g.L - 1 ? &auxp : nullptr);
-  // x0 = [tokens Wp + bp ; 0] + pos : dpos = dx0, dbp = sum_{t<P} dx0, dWp = tokens^T dx0[:P]
+  // x0 = [tok Wl + bl ; tokens Wp + bp ; 0] + pos : dpos = dx0, dbp = sum of the P patch rows of dx0, dWp = tokens^T dx0[Tl : Tl + P]
+  const float* pdx_patch = pdx + (long)Tl * D;
   KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + L.pos, G, pdx, (long)S * D, B);
-  KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx, tb.dtheta + L.bp, G, S, P, D, B);
-  bgemm(st, true, false, BG{tokens, pdx, tb.dtheta + L.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+  KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx_patch, tb.dtheta + L.bp, G, S, P, D, B);
+  bgemm(st, true, false, BG{tokens, pdx_patch, tb.dtheta + L.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+  if (Tl) {     // dbl = sum of the language rows, dWl = tok^T dx0[:Tl]; nothing flows into token_embedding (T5 is frozen)
+    KL(colsum_kernel, dim3((D + 63) / 64, B, (Tl + 63) / 64), dim3(64), pdx, tb.dtheta + L.bl, G, S, Tl, D, B);
+    bgemm(st, true, false, BG{in.tok, pdx, tb.dtheta + L.wl, nullptr, g.lang_dim, D, Tl, g.lang_dim, D, D, (long)Tl * g.lang_dim, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+  }
   // =============================== DINOv2 backward ===============================
   if (enc) {
-    // d tokens_b = dx0_b[:P] Wp_b^T -> rows 1.. of the final-LayerNorm output gradient (CLS row gets none)
+    // d tokens_b = (the patch rows of dx0_b) Wp_b^T -> rows 1.. of the final-LayerNorm output gradient (CLS row gets none)
     float* dh = t.y;                                                      // [B][Se][E]; t.y is free between blocks
     ENQ(hipMemsetAsync, dh, 0, (size_t)B * Se * E * 4, st);
-    bgemm(st, false, true, BG{pdx, TH + L.wp, dh + E, nullptr, P, E, D, D, D, E, (long)S * D, 0, G, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
+    bgemm(st, false, true, BG{pdx_patch, TH + L.wp, dh + E, nullptr, P, E, D, D, D, E, (long)S * D, 0, G, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
     float* edx = pl.edx;
     KL(ln_bwd_kernel, dim3((B * Se + 3) / 4), dim3(256), pl.ex_fin, dh, pl.emean, pl.erstd, Pe + L.e_lns, edx, (float*)nullptr, (float*)nullptr, 0, B * Se, Se, E, 0);
     KL(ln_pgrad_kernel, dim3((E + 63) / 64, (B * Se + 63) / 64), dim3(64), pl.ex_fin, dh, pl.emean, pl.erstd, Ge + L.e_lns, Ge + L.e_lnb, B * Se, E);

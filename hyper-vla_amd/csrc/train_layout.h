@@ -25,13 +25,23 @@ struct TrainLayout {
   BlockLeaves pol[TRAIN_MAX_POLICY_LAYERS];
   bool policy_ok;          // every policy leaf above was found by its name (false beyond TRAIN_MAX_POLICY_LAYERS, which the serving
                            // tables may be built for: they do not read the policy's offsets)
+  long wl, bl;             // encoder_language_token_projection_{kernel,bias} in a row of theta (use_language_token; else -1).  L.pos then
+                           // spans g.pos_rows() = T + P + 1 rows
 };
 
-// nullptr, or why the training path (hvla_train_*) does not serve a geometry hvla_create accepted (HVLA_E_SHAPE with this text)
+// nullptr, or why the training path (hvla_train_*) does not serve a geometry hvla_create accepted (HVLA_E_SHAPE with this text).
+// The first answer is the default: hvla_train_language_tokens(ctx, 1) lifts it for that context (train_entry, api.hip)
 inline const char* train_refusal(const Geom& g) {
   if (g.lang_in_policy) return "the training path does not build use_language_token";
   if (g.ctx_layers > CTX_MAX_LAYERS || g.L > TRAIN_MAX_POLICY_LAYERS || g.enc_layers > ENC_MAX_LAYERS) return "too many layers for the training path";
   return nullptr;
+}
+// ... and the same question for a context whose caller asked for the language prefix (language_tokens): what else stands against it
+inline const char* train_refusal(const Geom& g, bool language_tokens) {
+  if (!language_tokens || !g.lang_in_policy) return train_refusal(g);
+  Geom plain = g;
+  plain.lang_in_policy = 0;
+  return train_refusal(plain);
 }
 inline TrainLayout make_train_layout(const Geom& g) {
   TrainLayout L{};
@@ -76,6 +86,8 @@ inline TrainLayout make_train_layout(const Geom& g) {
   L.nb = f("encoder_Transformer_0_encoder_norm_bias"); L.ns = f("encoder_Transformer_0_encoder_norm_scale");
   L.bp = f("encoder_image_embedding_projection_bias"); L.wp = f("encoder_image_embedding_projection_kernel");
   L.pos = f("encoder_pos_embedding");
+  L.wl = g.lang_in_policy ? f("encoder_language_token_projection_kernel") : -1;
+  L.bl = g.lang_in_policy ? f("encoder_language_token_projection_bias") : -1;
   for (int l = 0; l < g.L && l < TRAIN_MAX_POLICY_LAYERS; ++l) {
     const std::string B = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_", A = B + "MultiHeadDotProductAttention_0_";
     BlockLeaves& y = L.pol[l];

@@ -26,7 +26,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
            "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
-           "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses",
+           "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
            "hvla_loss_terms", "hvla_train_metrics"]
 # hvla_train_metrics (include/hvla.h): select bits, the slots of its output vector, the size of its scratch
@@ -186,6 +186,8 @@ def load_library():
     lib.hvla_train_frozen.restype = C.c_int
     lib.hvla_train_attention_losses.argtypes = [vp, C.POINTER(hvla_train_attention)]
     lib.hvla_train_attention_losses.restype = C.c_int
+    lib.hvla_train_language_tokens.argtypes = [vp, i32]
+    lib.hvla_train_language_tokens.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -469,6 +471,10 @@ class Context:
                                         reference_ptr or None, entropy_ptr or None, alignment_ptr or None)
             rc = self.lib.hvla_train_attention_losses(self.h, C.byref(opts))
         self._check(rc, "hvla_train_attention_losses")
+
+    def train_language_tokens(self, on=False):
+        """Fine-tune a use_language_token context: while on, the hvla_train_* entries serve it (off: they refuse it, the default)."""
+        self._check(self.lib.hvla_train_language_tokens(self.h, int(on)), "hvla_train_language_tokens")
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

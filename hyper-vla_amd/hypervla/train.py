@@ -358,19 +358,31 @@ class FineTuner:
     `metrics=True` (default off: nothing is allocated and step / apply do exactly what they do without it): what the reference logs
     every step (scripts/train.py:494-529), computed on the device by hvla_train_metrics around the optimizer and read with `info()`;
     costs one more [n] f32 vector (the snapshot for update_norm).  `task_names`: the datasets of the mix, for `task_loss_<name>`
-    (`forward_backward(task_index=...)`)."""
+    (`forward_backward(task_index=...)`).
+    `language_tokens=True`: fine-tune a model with `vit_kwargs.use_language_token` (hvla_train_language_tokens): the
+    policy runs with the instruction's token embeddings in front of the patches, as the reference's loop does for such a model; the
+    two heads `output_head_encoder_language_token_projection_{kernel,bias}` train (or freeze, `frozen_keys`) like every other head.
+    Without the keyword such a model is refused; the attention terms are not defined for it."""
 
     def __init__(self, model, batch: int, peak_lr: float = 3e-4, weight_decay: float = 0.05, clip: float = 1.0,
                  ema_decay: float = 0.999, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
                  accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
-                 attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=()):
+                 attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=(), language_tokens: bool = False):
         self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
             attention_entropy, attention_map_alignment, num_steps)
-        if getattr(model.geometry, "lang_in_policy", False):
+        self.language_tokens = bool(language_tokens)
+        if getattr(model.geometry, "lang_in_policy", False) and not self.language_tokens:
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")
+        if self.language_tokens and not getattr(model.geometry, "lang_in_policy", False):
+            raise ValueError("language_tokens=True needs a model with vit_kwargs.use_language_token: this model's policy has no "
+                             "language_token_projection")
+        if self.language_tokens and (self.attention_entropy > 0 or self.attention_map_alignment > 0):
+            raise ValueError("attention_entropy / attention_map_alignment are not defined with language_tokens=True: the reference "
+                             "compares the action token's attention over lang_tokens + P keys with a P-wide DINOv2 map "
+                             "(scripts/train.py:364-368), which does not broadcast; the entropy term is left out with it")
         import torch
         self.torch, self.model, self.g, self.B = torch, model, model.geometry, batch
         self.train_encoder = bool(train_encoder)
@@ -480,9 +492,15 @@ class FineTuner:
     def _select(self, reference=None, attention=False):
         """What every call into the context starts with, in this order (the mask's length depends on the source); in front of a
         step (`attention`) also the attention terms, whose annealed alignment weight it returns."""
+        self._select_language()
         self._select_source()
         self._select_frozen()
         return self._select_attention(reference) if attention else None
+
+    def _select_language(self):
+        """Whether this tuner trains the policy with its language prefix (hvla_train_language_tokens; host-side like the others,
+        and first: the entries below refuse a use_language_token context without it)."""
+        self.model._ctx.train_language_tokens(self.language_tokens)
 
     def _select_source(self):
         """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this
@@ -739,6 +757,7 @@ class FineTuner:
         am = m._dev(np.asarray(batch["action_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
         tm = m._dev(np.asarray(batch["timestep_pad_mask"])[:, 0].astype(np.uint8), torch.uint8)
         assert tok.shape[0] == self.B
+        self._select_language()
         self._select_source()
         self._select_frozen()
         m._ctx.train_attention_losses()                 # off; the next step selects its own again

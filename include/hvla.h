@@ -94,7 +94,8 @@ int hvla_create(const hvla_config* cfg, int device, hvla_ctx** out);
  *                       sequence [lang_tokens language | P patches | 1 action]; language queries see only language keys.
  *                       Needs lang_tokens <= 32 and lang_dim % 64 == 0.  hvla_generate / hvla_generate_slots then also run
  *                       the language tokens through the policy once per episode and keep their K / V of every layer beside
- *                       the episode's weights; the training entry points refuse such a ctx.            */
+ *                       the episode's weights; the training entry points refuse such a ctx until
+ *                       hvla_train_language_tokens(ctx, 1) asks for the policy with its language prefix.              */
 typedef struct hvla_policy_options {
   uint32_t struct_size;                      /* = sizeof(hvla_policy_options)                                           */
   int32_t use_language_token;                /* 0 (default) or 1                                                        */
@@ -305,8 +306,9 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* gripper_logits, 
  * two calls the caller all-reduces `grads` over ranks (RCCL; scripts/train.py:460 `pmean`).
  * Every buffer is DEVICE memory owned by the caller; the flat parameter order is make_train_layout()
  * (csrc/train_layout.h) == hypervla.train.train_param_layout(); sizes from hvla_train_sizes.  Every hvla_train_*
- * entry first asks whether the training path serves the context's geometry: use_language_token, more than 8 context,
- * 16 policy or 24 image-encoder layers are HVLA_E_SHAPE before any other argument is looked at.         */
+ * entry first asks whether the training path serves the context's geometry: use_language_token without
+ * hvla_train_language_tokens(ctx, 1), more than 8 context, 16 policy or 24 image-encoder layers are HVLA_E_SHAPE before any
+ * other argument is looked at.                                                                           */
 typedef struct hvla_train_buffers {
   float* params;           /* [n_params]                                                     */
   float* grads;            /* [n_params]  written by hvla_train_step                          */
@@ -371,7 +373,9 @@ int hvla_train_accumulate(hvla_ctx* ctx, const hvla_train_buffers* buf, float* a
  * Weights generated earlier (hvla_generate) keep their values: they were generated already.  Ordering against work of this
  * context on OTHER streams (a step in flight, a second stream of cfg.streams == 2 is joined by hvla_step itself) is the
  * caller's.  Refused before any launch: not loaded -> HVLA_E_STATE; n_params != hvla_train_sizes(...)[0] for that flag, NULL
- * params, or a use_language_token geometry -> HVLA_E_SHAPE.                                                                 */
+ * params, or a use_language_token geometry without hvla_train_language_tokens(ctx, 1) -> HVLA_E_SHAPE.  With it the columns of
+ * the two language heads go through the same permutation as every other head's, and create_tasks / assign_tasks after the
+ * publish build weights and language prefix from them.                                                                       */
 int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int32_t train_encoder, void* stream);
 
 /* Replaces: FlaxDinov2Embeddings.interpolate_pos_encoding, which resizes HF's n x n DINOv2 position table to
@@ -436,7 +440,9 @@ int hvla_train_frozen(hvla_ctx* ctx, const uint8_t* frozen, int64_t n_params, in
  * policy layer's backward; all sums in a fixed order, no atomics.  With both weights 0, or after opts == NULL (the state of a new
  * context), hvla_train_step launches exactly what it launched.
  * HVLA_E_SHAPE, before anything is stored (the previous setting stays in force): struct_size != sizeof(hvla_train_attention), a
- * negative or non-finite weight, alignment_weight > 0 with a NULL reference_map, a use_language_token context.              */
+ * negative or non-finite weight, alignment_weight > 0 with a NULL reference_map, a use_language_token context -- whatever
+ * hvla_train_language_tokens says: the reference's alignment term compares the action row over lang_tokens + P keys with a P-wide
+ * map (scripts/train.py:364-368), which has no defined value, and the entropy term is left out with it.                      */
 typedef struct hvla_train_attention {
   uint32_t struct_size;
   float entropy_weight;         /* auxiliary_loss.attention_entropy                                   */
@@ -446,6 +452,18 @@ typedef struct hvla_train_attention {
   float* alignment;             /* device f32 [B] out, or NULL                                        */
 } hvla_train_attention;
 int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts);   /* NULL: off */
+/* Fine-tune a use_language_token context (scripts/train.py:326-346 binds whatever dict_base_params the hypernetwork produced;
+ * base_vit.py:159-166,207-214 prepends and masks the projected instruction tokens in training as in inference).  A host-side
+ * setting kept on the context, like hvla_train_frozen: nothing is launched, nothing allocated.  on == 0 (always HVLA_OK) is the
+ * state of a new context: every hvla_train_* entry refuses a use_language_token context with HVLA_E_SHAPE.  on == 1: they serve
+ * it (hvla_train_attention_losses excepted).  The policy then runs on lang_tokens + P + 1 rows per episode: rows [0, lang_tokens)
+ * are hvla_train_step's token_embedding through the generated language_token_projection (padded positions included, as in the
+ * reference), the mask is the serving path's, head and loss read the last row; the vector holds the two heads' columns in W_cat /
+ * b_cat and hvla_train_sizes reports the longer workspace.  Nothing flows into token_embedding (T5 is frozen).
+ * The gradient of the generated policy's key biases, zero under any attention mask, is left at exact zeros in `grads` (the
+ * heads output_head_*_key_bias): with few language keys the column sum that forms it carried only operand rounding.
+ * HVLA_E_SHAPE: on == 1 on a context created without use_language_token; any other value.  NULL ctx: HVLA_E_STATE.           */
+int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on);
 
 /* Replaces: the `metrics` of MixActionHead.loss (hypervla/components/action_heads.py:517-521: `continuous_loss`, `gripper_loss`) per
  * sample, and the numerator of `validation_action_loss` (scripts/train.py:578-581).  Arguments as hvla_loss (actions / gripper_logits
