@@ -7,7 +7,7 @@
 //          h = RMSNorm(x); x += relu(h Wi) Wo2 }
 //   last_hidden_state = RMSNorm(x)
 // Runs once per episode on B x 32 tokens, so it is built from the generic f32-accurate batched GEMM of the fine-tune path
-// (train.hip: split-bf16 on the matrix cores) plus four small kernels; parity target is the float64 restatement at 1e-4.
+// (train_gemm.hip: split-bf16 on the matrix cores) plus four small kernels; parity target is the float64 restatement at 1e-4.
 #include <cmath>
 
 #include "common.h"

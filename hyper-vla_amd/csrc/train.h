@@ -9,7 +9,7 @@
 
 namespace hvla {
 
-// generic batched f32 GEMM on the matrix cores (split-bf16, f32-class accuracy; train.hip):
+// generic batched f32 GEMM on the matrix cores (split-bf16, f32-class accuracy; train_gemm.hip):
 //   C[b0,b1] (+)= alpha * op(A)[b0,b1] * op(B)[b0,b1] (+ bias[b0][n]),  batch = blockIdx.z = b0 * nb1 + b1
 struct BG {
   const float* A;

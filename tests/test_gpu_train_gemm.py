@@ -1,4 +1,4 @@
-"""GPU: the fine-tune step's batched GEMM (csrc/train.hip bgemm(): bgemm3_kernel in 20 instantiations, bgemm_kernel in 4) launch by
+"""GPU: the fine-tune step's batched GEMM (csrc/train_gemm.hip bgemm(): bgemm3_kernel in 20 instantiations, bgemm_kernel in 4) launch by
 launch against float64 -- tools/bgemm_check.py in a fresh process on the bench library, once per module.  The tool's docstring has the
 two input classes and the derivation of the precision class's bound; tests/test_train_gemm_reference.py holds a CPU emulation of the
 kernel to the same criteria on the same table.

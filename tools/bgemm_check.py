@@ -1,4 +1,4 @@
-"""Diagnostic (GPU box): ONE launch of the fine-tune path's batched GEMM (csrc/train.hip bgemm()) per case of a table, every field of
+"""Diagnostic (GPU box): ONE launch of the fine-tune path's batched GEMM (csrc/train_gemm.hip bgemm()) per case of a table, every field of
 the descriptor BG (csrc/train.h) in the table's hands, against float64 (libhvla_bench.so: hvla_debug_bgemm_once launches once, synchronises
 and reports which kernel form bgemm_launch chose).  One line per case, ending in ` ok` or in the failing figures; then the number of
 cases per kernel instantiation.  tests/test_gpu_train_gemm.py runs this file once; tests/test_train_gemm_reference.py runs the same
