@@ -134,17 +134,37 @@ struct hvla_ctx {
 
 extern "C" {
 
-const char* hvla_last_error(const hvla_ctx* ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
+// why this thread's last hvla_create_with_v2 refused, where it had a text (there is no ctx to hold it); else null
+static thread_local const char* create_refusal = nullptr;
+
+const char* hvla_last_error(const hvla_ctx* ctx) { return ctx ? ctx->err.c_str() : (create_refusal ? create_refusal : "null ctx"); }
 
 int hvla_create(const hvla_config* c, int device, hvla_ctx** out) { return hvla_create_with(c, nullptr, device, out); }
 
 int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int device, hvla_ctx** out) {
   if (!c || !out) return HVLA_E_SHAPE;
   *out = nullptr;
+  create_refusal = nullptr;
+  if (opts && opts->struct_size != sizeof(hvla_policy_options)) return HVLA_E_SHAPE;   // hvla_config's rule for the options: never read past the caller's struct
+  const hvla_policy_options_v2 v2{sizeof(hvla_policy_options_v2), opts ? opts->use_language_token : 0, 0};
+  return hvla_create_with_v2(c, opts ? &v2 : nullptr, device, out);
+}
+
+int hvla_create_with_v2(const hvla_config* c, const hvla_policy_options_v2* opts, int device, hvla_ctx** out) {
+  if (!c || !out) return HVLA_E_SHAPE;
+  *out = nullptr;
+  create_refusal = nullptr;
   if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
-  if (opts && opts->struct_size != sizeof(hvla_policy_options)) return HVLA_E_SHAPE;   // the same rule for the options
+  if (opts && opts->struct_size != sizeof(hvla_policy_options_v2)) return HVLA_E_SHAPE;   // the same rule for the options
   const int lang = opts ? opts->use_language_token : 0;
   if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
+  const int mab = opts ? opts->attention_mask_as_bias : 0;
+  if (mab != 0 && mab != 1) return HVLA_E_SHAPE;
+  if (mab && lang) {
+    create_refusal = "attention_mask_as_bias with use_language_token is not built: with the mask added as a bias language queries "
+                     "attend to patch keys, so the language prefix is no per-episode constant";
+    return HVLA_E_SHAPE;
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return HVLA_E_DEVICE;
   hipDeviceProp_t prop;
@@ -158,6 +178,7 @@ int hvla_create_with(const hvla_config* c, const hvla_policy_options* opts, int 
   // which also refuses a context encoder or a policy that does not fit its kernel's LDS here, not at the first hvla_generate / hvla_step
   if (const int verdict = accept_geometry(*c, lang)) return verdict;
   g = geom_of(*c, lang);
+  g.mask_as_bias = mab;
   const int P = g.P();
   if (hipSetDevice(device) != hipSuccess) return HVLA_E_DEVICE;
   ctx->lay = build_layout(g);
@@ -499,7 +520,7 @@ static int policy_range(hvla_ctx* ctx, const hvla_weights* w, const float* token
   if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * (g.P() + lang_T);
   ctx->prof.begin(HVLA_PROF_POLICY, st);
   ++ctx->prof.nlaunch;
-  HIPCHK(ctx, launch_policy(p, st, lang_T, slots ? slots + b0 : nullptr, w->B));
+  HIPCHK(ctx, launch_policy(p, st, lang_T, slots ? slots + b0 : nullptr, w->B, g.mask_as_bias != 0));
   ctx->prof.end(HVLA_PROF_POLICY, st);
   return HVLA_OK;
 }

@@ -151,7 +151,10 @@ struct PolicyParams {
 // wrote (LangLayout::m_lkv), lang_T is the number of language tokens; p.amap is then [B, L, heads, lang_T + P]
 // episode pool, `slots` not null: workgroup b takes its weights from arena row slots[b] (p.wh / wl / vf point at row 0 of an arena of
 // `rows` episodes); tokens, actions, logits and attention rows stay call rows.  Entries outside [0, rows) are skipped.
-hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0, const int32_t* slots = nullptr, int rows = 0);
+// mask_as_bias: return_attention_map (policy_kernel_bias): the mask is added to the scores, patch queries attend to
+// the action token's key one logit below the others; not together with lang_T > 0
+hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0, const int32_t* slots = nullptr, int rows = 0,
+                         bool mask_as_bias = false);
 // use_language_token: the language tokens of K episodes through the policy once (lang_prefix_kernel): K / V of every layer into
 // the episodes' arena rows (LangLayout::m_lkv)
 struct LangPrefixParams {

@@ -36,6 +36,9 @@ struct Geom {
   int C, ctx_layers, ctx_heads, ctx_mlp, T, lang_dim, scale_context;
   int clip_target = 1;       // MixActionHead.loss: clip the action target to +-max_action (action_heads.py:499-500)
   int lang_in_policy = 0;    // vit_kwargs.use_language_token (base_vit.py:159-166,207-212): [T language | P patches | 1 action]
+  int mask_as_bias = 0;      // vit_kwargs.return_attention_map (transformer.py:172-181, multi_head_attetion.py:88-98): the blocks' attention is
+                             // CustomMultiHeadDotProductAttention_0, which adds the 0 / 1 mask to the scores instead of masking
+  const char* attention_name() const { return mask_as_bias ? "CustomMultiHeadDotProductAttention_0_" : "MultiHeadDotProductAttention_0_"; }
   int grid() const { return image_size / patch; }
   int P() const { return grid() * grid(); }
   int S() const { return P() + 1; }
@@ -70,15 +73,18 @@ inline std::vector<LeafInfo> generated_leaves(const Geom& g) {
   add(T + "encoder_norm_scale", {D});
   for (int l = 0; l < g.L; ++l) {
     const std::string B = T + "encoderblock_" + std::to_string(l) + "_";
-    add(B + "LayerNorm_0_bias", {D});
-    add(B + "LayerNorm_0_scale", {D});
-    add(B + "LayerNorm_1_bias", {D});
-    add(B + "LayerNorm_1_scale", {D});
-    add(B + "MlpBlock_0_Dense_0_bias", {M});
-    add(B + "MlpBlock_0_Dense_0_kernel", {D, M});
-    add(B + "MlpBlock_0_Dense_1_bias", {D});
-    add(B + "MlpBlock_0_Dense_1_kernel", {M, D});
-    const std::string A = B + "MultiHeadDotProductAttention_0_";
+    auto rest = [&] {
+      add(B + "LayerNorm_0_bias", {D});
+      add(B + "LayerNorm_0_scale", {D});
+      add(B + "LayerNorm_1_bias", {D});
+      add(B + "LayerNorm_1_scale", {D});
+      add(B + "MlpBlock_0_Dense_0_bias", {M});
+      add(B + "MlpBlock_0_Dense_0_kernel", {D, M});
+      add(B + "MlpBlock_0_Dense_1_bias", {D});
+      add(B + "MlpBlock_0_Dense_1_kernel", {M, D});
+    };
+    if (!g.mask_as_bias) rest();          // sorted keys: "CustomMultiHead..." leads the block, "MultiHead..." ends it
+    const std::string A = B + g.attention_name();
     add(A + "key_bias", {H, hd});
     add(A + "key_kernel", {D, H, hd});
     add(A + "out_bias", {D});
@@ -87,6 +93,7 @@ inline std::vector<LeafInfo> generated_leaves(const Geom& g) {
     add(A + "query_kernel", {D, H, hd});
     add(A + "value_bias", {H, hd});
     add(A + "value_kernel", {D, H, hd});
+    if (g.mask_as_bias) rest();
   }
   add("encoder_image_embedding_projection_bias", {D});
   add("encoder_image_embedding_projection_kernel", {g.E, D});
@@ -251,7 +258,7 @@ inline PackedLayout build_layout(const Geom& g) {
   }
   for (int l = 0; l < g.L; ++l) {
     const std::string Bn = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_";
-    const std::string An = Bn + "MultiHeadDotProductAttention_0_";
+    const std::string An = Bn + g.attention_name();
     const int mb = p.m_layer0 + l * p.m_layer_stride, vb = p.v_layer0 + l * p.v_layer_stride;
     // fused QKV: rows n in [0,D) = query (head-major h*hd+d == flax [D,H,hd] flattened), [D,2D) key,
     // [2D,3D) value

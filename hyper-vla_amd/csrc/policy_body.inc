@@ -7,6 +7,11 @@
 // tokens lead the sequence; their K / V of every layer were written once per episode by lang_prefix_kernel (policy.hip) into the
 // episode's arena row (LangLayout::m_lkv).  Patch queries and the action query attend over one more key tile, the prefix of the
 // current layer and head pair, staged by LDS-DMA into `pre` at the q tile of the pair; its keys >= lang_T are masked.  Undefined = 0.
+// HVLA_POLICY_BIAS 1 (policy_kernel_bias / policy_kernel_slots_bias, DESIGN.md §20): return_attention_map.  The mask of
+// base_vit.py:209-214 is ADDED to the scores (multi_head_attetion.py:88-98), so a patch query has one more key, the action token's
+// own k / v of the layer and head (ka / va: f32 in LDS, visible behind the barrier pair in front of the attention), one logit --
+// log2 e in the kernel's log2 domain -- below the patch keys.  It is one VALU key per patch lane in both softmax passes; the action
+// row (every key + 1: a constant the softmax row ignores) and the last layer (no patch rows) are untouched.  Undefined = 0.
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #if HVLA_POLICY_LANG
   constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 10;          // NP: <= 8 waves + the language prefix + the own key
@@ -493,7 +498,7 @@
           };
 #endif
           // pass 1: row maximum (scores are in the log2 domain: q carries 1/sqrt(hd) log2 e).  Patches cannot see the
-          // action token (base_vit.py:209-214): structural, its key is in no tile.
+          // action token (base_vit.py:209-214): structural, its key is in no tile.  (HVLA_POLICY_BIAS: they do, below.)
           float m2 = -1e30f;
 #if HVLA_POLICY_LANG
           // (rolled in this variant: unrolled, the lane's addresses of the eight key tiles are hoisted out of the layer loop into
@@ -513,6 +518,23 @@
           }
 #endif
           m2 = fmaxf(m2, __shfl_xor(m2, 32, 64));
+#if HVLA_POLICY_BIAS
+          // the action token's key: this lane's 8 of the query's 16 values (the B fragment's hi + lo, the order of act_attend's
+          // q0 / q1) against ka in f32, the other 8 from lane ^ 32; the mask's 0 against the patch keys' 1 is - log2 e here
+          float sa;
+          {
+            const int ln = opaque((int)(threadIdx.x & 63));
+            const float* kv = ((SPREAD && ph) ? qkv1 : qa) + 32 + hl * 16 + 4 * (ln >> 5);
+            const f32x4 k0 = *reinterpret_cast<const f32x4*>(kv), k1 = *reinterpret_cast<const f32x4*>(kv + 8);
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = fmaf((float)qf[hl].hi[j] + (float)qf[hl].lo[j], k0[j], s);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = fmaf((float)qf[hl].hi[4 + j] + (float)qf[hl].lo[4 + j], k1[j], s);
+            sa = s + __shfl_xor(s, 32, 64) - 1.4426950408889634f;
+          }
+          m2 = fmaxf(m2, sa);
+#endif
           // pass 2: p = exp2(s - max) straight out of the accumulator (initialised to -max); P = hi + lo in fp16 against
           // V = [hi | lo x 2^10] in fp16: four MFMAs per key tile, all four hi / lo cross terms
           float lsum = 0.f;
@@ -565,10 +587,28 @@
             }
           }
 #endif
+#if HVLA_POLICY_BIAS
+          const float ea = __builtin_amdgcn_exp2f(sa - m2);
+          lsum = fmaf(ea, 0.5f, lsum);                // both halves hold the same ea and are summed below: once per query (no lane mask,
+                                                      // which would be one more loop-invariant SGPR pair)
+#endif
           const float inv = 1.f / wave_xor_sum32(lsum);
           float ov[8];
+#if HVLA_POLICY_BIAS
+          {                                           // + e va, f32: ov[j] is d = 8 (j >> 2) + 4 half + (j & 3) of the head
+            const int ln = opaque((int)(threadIdx.x & 63));
+            const float* vv = ((SPREAD && ph) ? qkv1 : qa) + 64 + hl * 16 + 4 * (ln >> 5);
+            const f32x4 v0 = *reinterpret_cast<const f32x4*>(vv), v1 = *reinterpret_cast<const f32x4*>(vv + 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              ov[j] = fmaf(ea, v0[j], fmaf(O[8 + j], 1.f / 1024.f, O[j])) * inv;
+              ov[4 + j] = fmaf(ea, v1[j], fmaf(O[12 + j], 1.f / 1024.f, O[4 + j])) * inv;
+            }
+          }
+#else
 #pragma unroll
           for (int j = 0; j < 8; ++j) ov[j] = fmaf(O[8 + j], 1.f / 1024.f, O[j]) * inv;     // V_hi.P + V_lo.P (lo stored x 2^10)
+#endif
           of[hl] = split8(ov);
         }
         if (ph == 0) {                        // phase A's outputs wait in LDS (wave-private, lane-linear) for the out-projection

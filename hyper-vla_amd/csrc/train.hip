@@ -314,6 +314,31 @@ __global__ void softmax_lang_fwd_kernel(float* __restrict__ p, int nmat, int S, 
   softmax_row(p + (long)row * ld, S, ld, lane, [=](int k) { return q < T ? k < T : (q == S - 1 || k < S - 1); });
 }
 
+// The policy's attention under return_attention_map: CustomMultiHeadDotProductAttention adds the 0 / 1 mask of
+// base_vit.py:209-214 to the scaled scores (multi_head_attetion.py:88-98) and masks nothing.  Per row only differences count: the
+// action row q = S - 1 (every key + 1) is a plain softmax, a patch row sees key S - 1 one logit below the others.  A kernel of its
+// own, as above; p stays [S][ld] dense, so the backward, the four products and attention_aux_kernel read it as they are.
+__global__ void softmax_bias_fwd_kernel(float* __restrict__ p, int nmat, int S, int ld) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nmat * S) return;
+  float* pr = p + (long)row * ld;
+  const float drop = row % S < S - 1 ? 1.f : 0.f;
+  const auto score = [=](int k) { return k == S - 1 ? pr[k] - drop : pr[k]; };
+  if (lane < ld - S) pr[S + lane] = 0.f;
+  float mx = -3.4e38f;
+  for (int k = lane; k < S; k += 64) mx = fmaxf(mx, score(k));
+  for (int o = 32; o; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float sum = 0.f;
+  for (int k = lane; k < S; k += 64) {
+    const float e = __expf(score(k) - mx);
+    pr[k] = e;
+    sum += e;
+  }
+  for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  const float inv = 1.f / sum;
+  for (int k = lane; k < S; k += 64) pr[k] *= inv;
+}
+
 // ds = p * (dp - sum_k dp p), in place on dp
 __global__ void softmax_bwd_kernel(const float* __restrict__ p, float* __restrict__ dp, int rows, int Cc, int ld) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -766,7 +791,8 @@ template <class T> static Blk<T> bind(T* base, const BlockLeaves& y) {
 }
 // block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
 // HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention)
-struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; };     // lang_T > 0: the policy's mask with T language rows in front
+struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; int mask_as_bias = 0; };     // lang_T > 0: the policy's mask with T language rows in front;
+                                                                                                              // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel)
 struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y; };
 
 // Y[nb][S][N] (+)= X[nb][S][K] W + bias with W per episode (ws = G) or shared (ws = 0: the batch folds into M, so
@@ -822,6 +848,7 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   const int Sp = (S + 3) & ~3;
   bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
   if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
+  else if (op.mask_as_bias) KL(softmax_bias_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, Sp);
   else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
   {
     BG pv{a.p, a.v, a.o, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
@@ -944,8 +971,10 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     // The key bias adds q . bk / sqrt(hd) to every kept score of a query's row, and a softmax row ignores a constant: its gradient is
     // zero under any mask (sum_k ds[q][k] = 0).  What the column sum of dk gives instead is the operand rounding of ds in dk = ds^T q,
     // and a language query's few keys carry ds entries of the size of dp: with the language rows the leaf is left at the zero it is
-    // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.
-    if (!(op.lang_T > 0 && i == 1)) bgrad(dqkv[i], D, gBm[i]);
+    // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.  With the mask added as a
+    // bias every query has every key, the constant is still one per row, and the leaf is left at zero in the same way:
+    // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.
+    if (!((op.lang_T > 0 || op.mask_as_bias) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
     linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0);                                                         // dh
   }
   ln_bwd(a.x_in, t.g, a.mean0, a.rstd0, w.l0s, gw.l0s, gw.l0b);
@@ -1065,7 +1094,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
   ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
-  const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0, Tl}, enc_opt{2, nullptr, 1};
+  const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0, Tl, g.mask_as_bias}, enc_opt{2, nullptr, 1};
 
   // =============================== DINOv2 forward in f32, activations kept (HF Dinov2Model; base_vit.py:111-131) =====
   const float* tokens = in.tokens;         // [B][P][E] rows, episode stride tok_stride

@@ -89,7 +89,7 @@ inline TrainLayout make_train_layout(const Geom& g) {
   L.wl = g.lang_in_policy ? f("encoder_language_token_projection_kernel") : -1;
   L.bl = g.lang_in_policy ? f("encoder_language_token_projection_bias") : -1;
   for (int l = 0; l < g.L && l < TRAIN_MAX_POLICY_LAYERS; ++l) {
-    const std::string B = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_", A = B + "MultiHeadDotProductAttention_0_";
+    const std::string B = "encoder_Transformer_0_encoderblock_" + std::to_string(l) + "_", A = B + g.attention_name();
     BlockLeaves& y = L.pol[l];
     y.ln0_b = f(B + "LayerNorm_0_bias"); y.ln0_s = f(B + "LayerNorm_0_scale"); y.ln1_b = f(B + "LayerNorm_1_bias"); y.ln1_s = f(B + "LayerNorm_1_scale");
     y.b1 = f(B + "MlpBlock_0_Dense_0_bias"); y.w1 = f(B + "MlpBlock_0_Dense_0_kernel");

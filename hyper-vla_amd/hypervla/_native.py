@@ -25,7 +25,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
-           "hvla_create_with", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
+           "hvla_create_with", "hvla_create_with_v2", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
            "hvla_loss_terms", "hvla_train_metrics"]
@@ -58,6 +58,11 @@ class hvla_config(C.Structure):
 class hvla_policy_options(C.Structure):
     """Model options outside hvla_config (include/hvla.h): struct_size must be sizeof(hvla_policy_options)."""
     _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32)]
+
+
+class hvla_policy_options_v2(C.Structure):
+    """hvla_policy_options with attention_mask_as_bias, for hvla_create_with_v2 (include/hvla.h): struct_size must be its sizeof."""
+    _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32), ("attention_mask_as_bias", C.c_int32)]
 
 
 class hvla_tensor_desc(C.Structure):
@@ -120,6 +125,8 @@ def load_library():
     lib.hvla_create.restype = C.c_int
     lib.hvla_create_with.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options), C.c_int, C.POINTER(vp)]
     lib.hvla_create_with.restype = C.c_int
+    lib.hvla_create_with_v2.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options_v2), C.c_int, C.POINTER(vp)]
+    lib.hvla_create_with_v2.restype = C.c_int
     lib.hvla_destroy.argtypes = [vp]
     lib.hvla_destroy.restype = None
     lib.hvla_last_error.argtypes = [vp]
@@ -255,14 +262,20 @@ class Context:
                                int(getattr(g, "clip_target", True)))
         self.geometry, self.device, self.max_batch, self.enc_dtype = g, device, max_batch, enc_dtype
         h = C.c_void_p()
-        if getattr(g, "lang_in_policy", False):       # use_language_token: the options struct (hvla_config's size is ABI)
+        lang, mab = bool(getattr(g, "lang_in_policy", False)), bool(getattr(g, "mask_as_bias", False))
+        if mab:               # return_attention_map: the larger options struct has an entry of its own (both sizes are ABI)
+            self.options = hvla_policy_options_v2(C.sizeof(hvla_policy_options_v2), int(lang), 1)
+            rc = self.lib.hvla_create_with_v2(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
+        elif lang:            # use_language_token: the options struct (hvla_config's size is ABI)
             self.options = hvla_policy_options(C.sizeof(hvla_policy_options), 1)
             rc = self.lib.hvla_create_with(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
         else:
             rc = self.lib.hvla_create(C.byref(self.cfg), device, C.byref(h))
         if rc != 0:
-            raise NativeError(f"hvla_create failed: {_ERRORS.get(rc, rc)} (geometry outside the hand-written "
-                              f"kernels' specialisation, or device {device} is not a gfx950 GPU)")
+            why = self.lib.hvla_last_error(None)
+            why = why.decode() if why and why != b"null ctx" else ("geometry outside the hand-written kernels' specialisation, "
+                                                                   f"or device {device} is not a gfx950 GPU")
+            raise NativeError(f"hvla_create failed: {_ERRORS.get(rc, rc)} ({why})")
         self.h = h
 
     def _check(self, rc: int, what: str):

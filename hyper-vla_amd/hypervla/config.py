@@ -51,6 +51,19 @@ class Geometry:
     # base_net_kwargs.vit_kwargs.use_language_token (base_vit.py:159-166,207-212): the T5 token embeddings, projected to D,
     # lead the policy's sequence [T language | P patches | 1 action]; language queries see only language keys
     lang_in_policy: bool = False
+    # base_net_kwargs.vit_kwargs.return_attention_map (transformer.py:172-181): the block's attention is
+    # CustomMultiHeadDotProductAttention, which hands the boolean mask to dot_product_attention_weights as `bias=`
+    # (multi_head_attetion.py:88-98): 1 is added to every allowed score and nothing is masked
+    mask_as_bias: bool = False
+
+    def __post_init__(self):
+        if self.mask_as_bias and self.lang_in_policy:
+            raise ValueError("return_attention_map together with use_language_token is not built: with the mask added as a bias "
+                             "language queries attend to patch keys, so the language prefix is no per-episode constant")
+
+    @property
+    def attention_name(self) -> str:   # flax auto-name of the policy blocks' attention module
+        return "CustomMultiHeadDotProductAttention_0" if self.mask_as_bias else "MultiHeadDotProductAttention_0"
 
     @property
     def grid(self) -> int:
@@ -159,7 +172,8 @@ class Leaf:
 
 def generated_leaves(g: Geometry) -> List[Leaf]:
     """The 73 HN-generated leaves in jax pytree order (dict keys sorted at every level); 75 with ``lang_in_policy``, which adds
-    ``encoder/language_token_projection`` (base_vit.py:162-165) between the image projection and the position embedding.
+    ``encoder/language_token_projection`` (base_vit.py:162-165) between the image projection and the position embedding.  With
+    ``mask_as_bias`` the eight attention leaves of a block are named ``CustomMultiHeadDotProductAttention_0`` and lead the block.
 
     ``shared_modules=("image_encoder",)`` removes the DINOv2 leaves (hypervla/model.py:439-451);
     ``share_layer_index=True`` makes every leaf read context token 0 (model.py:400-402).
@@ -175,17 +189,19 @@ def generated_leaves(g: Geometry) -> List[Leaf]:
     items += [(T + ("encoder_norm", "bias"), (D,)), (T + ("encoder_norm", "scale"), (D,))]
     for l in range(g.layers):
         B = T + (f"encoderblock_{l}",)
-        items += [(B + ("LayerNorm_0", "bias"), (D,)), (B + ("LayerNorm_0", "scale"), (D,)),
-                  (B + ("LayerNorm_1", "bias"), (D,)), (B + ("LayerNorm_1", "scale"), (D,)),
-                  (B + ("MlpBlock_0", "Dense_0", "bias"), (M,)),
-                  (B + ("MlpBlock_0", "Dense_0", "kernel"), (D, M)),
-                  (B + ("MlpBlock_0", "Dense_1", "bias"), (D,)),
-                  (B + ("MlpBlock_0", "Dense_1", "kernel"), (M, D))]
-        A_ = B + ("MultiHeadDotProductAttention_0",)
-        items += [(A_ + ("key", "bias"), (H, hd)), (A_ + ("key", "kernel"), (D, H, hd)),
-                  (A_ + ("out", "bias"), (D,)), (A_ + ("out", "kernel"), (H, hd, D)),
-                  (A_ + ("query", "bias"), (H, hd)), (A_ + ("query", "kernel"), (D, H, hd)),
-                  (A_ + ("value", "bias"), (H, hd)), (A_ + ("value", "kernel"), (D, H, hd))]
+        rest = [(B + ("LayerNorm_0", "bias"), (D,)), (B + ("LayerNorm_0", "scale"), (D,)),
+                (B + ("LayerNorm_1", "bias"), (D,)), (B + ("LayerNorm_1", "scale"), (D,)),
+                (B + ("MlpBlock_0", "Dense_0", "bias"), (M,)),
+                (B + ("MlpBlock_0", "Dense_0", "kernel"), (D, M)),
+                (B + ("MlpBlock_0", "Dense_1", "bias"), (D,)),
+                (B + ("MlpBlock_0", "Dense_1", "kernel"), (M, D))]
+        A_ = B + (g.attention_name,)
+        attn = [(A_ + ("key", "bias"), (H, hd)), (A_ + ("key", "kernel"), (D, H, hd)),
+                (A_ + ("out", "bias"), (D,)), (A_ + ("out", "kernel"), (H, hd, D)),
+                (A_ + ("query", "bias"), (H, hd)), (A_ + ("query", "kernel"), (D, H, hd)),
+                (A_ + ("value", "bias"), (H, hd)), (A_ + ("value", "kernel"), (D, H, hd))]
+        # sorted keys: "CustomMultiHead..." comes before "LayerNorm_0", "MultiHead..." after "MlpBlock_0"
+        items += attn + rest if g.mask_as_bias else rest + attn
     items += [(("encoder", "image_embedding_projection", "bias"), (D,)),
               (("encoder", "image_embedding_projection", "kernel"), (E, D))]
     if g.lang_in_policy:
@@ -303,7 +319,7 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
                             num_layers=g.layers, num_heads=g.heads, mlp_dim=g.mlp,
                             dropout_rate=0.0, use_language_token=bool(g.lang_in_policy),
                             fine_tune_pretrained_image_encoder=True, image_embedding_noise=0.0,
-                            use_differential_transformer=False, return_attention_map=False,
+                            use_differential_transformer=False, return_attention_map=bool(g.mask_as_bias),
                             add_positional_embedding=True, include_class_token=False),
             action_head_kwargs=dict(token_per_horizon=False, squash_continuous_action=True,
                                     tanh_scaling_factor=g.tanh_scale, clip_target=g.clip_target,
@@ -333,6 +349,11 @@ def geometry_from_config(cfg: Dict) -> Geometry:
     if a.get("token_per_horizon") or a.get("hidden_dims"):
         raise ValueError("token_per_horizon / hidden_dims action heads are not built")
     lang_in_policy = bool(v.get("use_language_token", False))
+    mask_as_bias = bool(v.get("return_attention_map", False))
+    if mask_as_bias and lang_in_policy:
+        raise ValueError("base_net_kwargs.vit_kwargs.return_attention_map together with use_language_token is not built: "
+                         "CustomMultiHeadDotProductAttention adds the mask as a bias (multi_head_attetion.py:88-98), so language "
+                         "queries attend to patch keys and the language prefix is no per-episode constant")
     for key, want in (("include_class_token", False), ("add_positional_embedding", True),
                       ("use_differential_transformer", False)):
         if bool(v.get(key, want)) != want:
@@ -357,7 +378,7 @@ def geometry_from_config(cfg: Dict) -> Geometry:
         ctx_dim=h["context_embedding_dim"], ctx_layers=ce["num_layers"],
         ctx_heads=ce["num_attention_heads"], ctx_mlp=ce["mlp_dim"],
         lang_tokens=ge.get("lang_tokens", 32), lang_dim=ge.get("lang_dim", 768),
-        scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy)
+        scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy, mask_as_bias=mask_as_bias)
 
 
 # --------------------------------------------------------------------------------------

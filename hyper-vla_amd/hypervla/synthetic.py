@@ -8,6 +8,7 @@ that a dropped bias or a swapped scale shows up in parity tests.
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Dict, Tuple
 
 import numpy as np
@@ -85,11 +86,15 @@ def synthetic_params(g: Geometry = FULL, seed: int = SEED_WEIGHTS) -> Dict[str, 
 
     # 73 output heads: bias = a standard init of the base net, kernel = context-dependent delta
     k_scale = 0.5 / np.sqrt(C) if g.scale_context else 0.5 / C
-    for lf in generated_leaves(g):
+    # (drawn in the leaf order of the model without return_attention_map: a mask_as_bias checkpoint holds the same tensors, its
+    # attention heads under the variant's names -- the two models then differ by their function alone)
+    plain = dataclasses.replace(g, mask_as_bias=False) if g.mask_as_bias else g
+    for lf in generated_leaves(plain):
         std, mean = _leaf_natural(lf.path, lf.shape, g)
-        p[lf.head_name + "/bias"] = normal((lf.size,), std, mean)
+        head = lf.head_name.replace(plain.attention_name, g.attention_name)
+        p[head + "/bias"] = normal((lf.size,), std, mean)
         # ctx = LN(.)/sqrt(C) has |ctx|~1 => delta ~ 0.5*std of the leaf's own scale
-        p[lf.head_name + "/kernel"] = normal((C, lf.size), k_scale * std * np.sqrt(C))
+        p[head + "/kernel"] = normal((C, lf.size), k_scale * std * np.sqrt(C))
 
     # shared DINOv2 leaves (flat vectors)
     for path, shape in encoder_leaves(g):

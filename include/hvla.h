@@ -103,6 +103,30 @@ typedef struct hvla_policy_options {
 
 /* hvla_create with options; opts == NULL is hvla_create (the same ctx, byte for byte).                               */
 int hvla_create_with(const hvla_config* cfg, const hvla_policy_options* opts, int device, hvla_ctx** out);
+
+/* hvla_policy_options with one more field.  The size of hvla_policy_options is part of the ABI (its exact-size rule refuses any
+ * other), so the field travels in a struct and an entry of its own; the same rule holds here for sizeof(hvla_policy_options_v2).
+ *   use_language_token      as above
+ *   attention_mask_as_bias  base_net_kwargs.vit_kwargs.return_attention_map (hypervla/components/transformer.py:172-181): the
+ *                       policy blocks' attention is CustomMultiHeadDotProductAttention, which hands the boolean mask of
+ *                       base_vit.py:209-214 to dot_product_attention_weights as `bias=` (multi_head_attetion.py:88-98): the
+ *                       mask's 1 / 0 is ADDED to the scaled scores and nothing is masked, so a patch query also attends to the
+ *                       action token's key, one logit below every other key; the action row is the masked model's formula.
+ *                       The generated leaves of the attention are then named `..._CustomMultiHeadDotProductAttention_0_...`
+ *                       and lead their block in the parameter order (hvla_load_weights, hvla_weights_import / _export, the
+ *                       training vector).  Served, fine-tuned and published like any other context.  Not
+ *                       built together with use_language_token (language queries would attend to patch keys, so the language
+ *                       prefix would be no per-episode constant): HVLA_E_SHAPE, hvla_last_error(NULL) says why.            */
+typedef struct hvla_policy_options_v2 {
+  uint32_t struct_size;                      /* = sizeof(hvla_policy_options_v2)                                        */
+  int32_t use_language_token;                /* 0 (default) or 1                                                        */
+  int32_t attention_mask_as_bias;            /* 0 (default) or 1                                                        */
+} hvla_policy_options_v2;
+
+/* hvla_create_with for hvla_policy_options_v2: opts == NULL, or attention_mask_as_bias 0, is hvla_create_with of the same
+ * use_language_token (the same ctx, byte for byte).  A refusal leaves *out NULL; where it has more to say than its code,
+ * hvla_last_error(NULL) returns the text until this thread's next hvla_create / hvla_create_with / hvla_create_with_v2.  */
+int hvla_create_with_v2(const hvla_config* cfg, const hvla_policy_options_v2* opts, int device, hvla_ctx** out);
 void hvla_destroy(hvla_ctx* ctx);
 const char* hvla_last_error(const hvla_ctx* ctx);
 
