@@ -1,5 +1,5 @@
 // accept.h -- which geometries hvla_create serves (no HIP types): ONE predicate from (hvla_config, use_language_token) to
-// HVLA_OK / HVLA_E_SHAPE / HVLA_E_DTYPE, and next to it the two dynamic-LDS formulas it refuses by.  The launchers
+// HVLA_OK / HVLA_E_SHAPE / HVLA_E_DTYPE, and next to it the two dynamic-LDS descriptions it refuses by.  The launchers
 // (launch_ctx_encoder in hypernet.hip, launch_policy_nw in policy.hip) size their launches with the same functions, so a geometry
 // the predicate lets through cannot fail its first launch for LDS.  A CPU test walks the predicate over every edge of the contract
 // and checks the launch-side preconditions of everything it accepts (tests/native/accept_check.cpp, built with g++ under ASan /
@@ -46,14 +46,42 @@ inline size_t ctx_encoder_lds_bytes(int T, int C, int F, int E) {
   return ((size_t)2 * (T + 2) * (C + 4) + ctx_big_elems(T, C, F, E) + 64) * sizeof(float);   // x, h, big, the key mask
 }
 
-// ---- generated policy: the dynamic LDS of policy_kernel<NW> (NW = P / 32 waves; policy_body.inc lays it out).  layer_vec_floats =
-// PolicyLayout::Gv - v_layer0, the per-layer vectors + encoder_norm + head bias the kernel copies to LDS once.
-inline size_t policy_lds_bytes(int NW, bool lang, int layer_vec_floats) {
+// ---- generated policy: the dynamic LDS of policy_kernel<NW> (NW = P / 32 waves) and of its language-token form, THE description:
+// policy_lds_bytes takes its total from it and the kernel body (policy_body.inc) is held to it by static_asserts.  What each buffer
+// holds is told where the kernel uses it.  Byte offsets from the start of the dynamic LDS, in the order of the buffers.
+struct PolicyLds {
+  int nhr;          // heads resident in K / V^T at a time
+  int np;           // rows of the action row's partial table per head: <= 8 waves (+ the language prefix) + the own key
+  int spx;          // keys of the attention-map export: the patches (+ the prefix tile)
+  int act_floats;   // the action token's scratch: xa .. ga [384] | part [2][np][20] | pbuf [NW][32] | pexp [2][spx] | qkv1 [96] | hpriv [NW][64]
+  int act_bytes;    // ... rounded up to 1 KiB; the scratch sits at offset 0
+  int ring;         // [PRING][8 KiB] staged weight tiles
+  int kh, kl;       // [nhr][P / 32][2][32][8] bf16 each
+  int vt;           // [nhr][hi d 0-15 | lo d 0-15][P + 8] fp16
+  int pre;          // [LANG_PAIR_BYTES] the resident head pair's language prefix (lang only: else empty)
+  int park;         // [NW][4 KiB] phase A's attention outputs
+  int vlds;         // [layer_vec_floats] f32, to the end
+};
+constexpr PolicyLds policy_lds(int NW, bool lang) {
   const int SP = NW * 32, VLD = SP + 8;
-  const int NP = lang ? 10 : 9, SPX = SP + (lang ? 32 : 0);   // policy_body.inc: partial table, attention-map keys
-  return (size_t)PRING * 8192 + ((size_t)2 * 2 * SP * 16 + (size_t)2 * 32 * VLD) * 2 /* 16-bit K and V^T */ + (size_t)NW * 4096 +
-         (lang ? (size_t)LANG_PAIR_BYTES : 0) + (size_t)layer_vec_floats * sizeof(float) +
-         (size_t)(((384 + 2 * NP * 20 + NW * 32 + 2 * SPX + 96 + NW * 64) * 4 + 1023) & ~1023);
+  PolicyLds d{};
+  d.nhr = 2;
+  d.np = lang ? 10 : 9;
+  d.spx = SP + (lang ? 32 : 0);
+  d.act_floats = 384 + 2 * d.np * 20 + NW * 32 + 2 * d.spx + 96 + NW * 64;
+  d.act_bytes = (d.act_floats * 4 + 1023) & ~1023;
+  d.ring = d.act_bytes;
+  d.kh = d.ring + PRING * 8192;
+  d.kl = d.kh + d.nhr * SP * 16 * 2;
+  d.vt = d.kl + d.nhr * SP * 16 * 2;
+  d.pre = d.vt + d.nhr * 32 * VLD * 2;
+  d.park = d.pre + (lang ? LANG_PAIR_BYTES : 0);
+  d.vlds = d.park + NW * 4096;
+  return d;
+}
+// layer_vec_floats = PolicyLayout::Gv - v_layer0, the per-layer vectors + encoder_norm + head bias the kernel copies to LDS once.
+inline size_t policy_lds_bytes(int NW, bool lang, int layer_vec_floats) {
+  return (size_t)policy_lds(NW, lang).vlds + (size_t)layer_vec_floats * sizeof(float);
 }
 
 inline Geom geom_of(const hvla_config& c, int lang) {
@@ -87,7 +115,7 @@ inline int accept_geometry(const hvla_config& c, int lang) {
   if (c.enc_layers < 0 || c.enc_layers > ENC_MAX_LAYERS) return HVLA_E_SHAPE;
   if (c.patch < 1 || c.image_size < 1 || c.image_size % c.patch != 0) return HVLA_E_SHAPE;
   const int64_t grid = c.image_size / c.patch, P = grid * grid;
-  if (P != 256 && P != 64) return HVLA_E_SHAPE;     // (32 patches are no square: policy_kernel<1> cannot be reached)
+  if (P != 256 && P != 64) return HVLA_E_SHAPE;     // (32 patches are no square: no policy_kernel<1> is built)
   // context encoder
   if (c.ctx_dim != 128 && c.ctx_dim != 64 && c.ctx_dim != 32) return HVLA_E_SHAPE;
   if (c.ctx_heads < 1 || c.ctx_dim % c.ctx_heads != 0 || (c.ctx_dim / c.ctx_heads) % 4 != 0) return HVLA_E_SHAPE;

@@ -1,5 +1,5 @@
-// policy_body.inc -- the body of policy_kernel (policy.hip), included twice: by policy_kernel itself (HVLA_POLICY_SLOTS 0) and by
-// policy_kernel_slots (HVLA_POLICY_SLOTS 1), the episode-pool form, where the workgroup of call row b reads its weights from arena
+// policy_body.inc -- the body of the six policy kernels (policy.hip), included once by each: by policy_kernel itself (HVLA_POLICY_SLOTS
+// 0) and by policy_kernel_slots (HVLA_POLICY_SLOTS 1), the episode-pool form, where the workgroup of call row b reads its weights from arena
 // row slots[b] (one wave-uniform load at entry; a row outside [0, p.B), the arena's rows, is skipped) and writes tokens / actions / logits /
 // attention at call row b as always.  With HVLA_POLICY_SLOTS 0 the preprocessor hands the compiler the kernel's text as it was
 // before the pool existed, so policy_kernel<8, 2> compiles to the same code (DESIGN.md §10).
@@ -16,10 +16,12 @@
 #if HVLA_POLICY_LANG
   constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 10;          // NP: <= 8 waves + the language prefix + the own key
   constexpr int NPART = NW + 1, SPX = SP + 32;                         // partials before the own key; keys of the attention-map export
+  constexpr bool lds_lang = true;                                      // the form of accept.h's policy_lds() this body is held to, below
   static_assert(NW + 2 <= NP, "partial table");
 #else
   constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 9;           // NHR heads resident in LDS at a time; NP: partials per head (<= 8 waves + the own key)
   constexpr int NPART = NW, SPX = SP;
+  constexpr bool lds_lang = false;
   static_assert(NW + 1 <= NP, "partial table");
 #endif
   // the action token's scratch sits at the START of the dynamic LDS (compile-time addresses: every access is an immediate
@@ -68,6 +70,14 @@
 #else
   float* vlds = reinterpret_cast<float*>(reinterpret_cast<char*>(Vt + NHR * 32 * VLD) + NW * 4096);
 #endif
+  // accept.h's policy_lds() is what hvla_create and launch_policy_nw size this LDS by: the chain of pointers above is held to it.
+  // (Taking every pointer as smem + its offset from that table instead changes the instruction streams of all twelve kernels:
+  // profiles/policy_weightgen_template_isa.txt.)
+  constexpr PolicyLds T = policy_lds(NW, lds_lang);
+  static_assert(T.nhr == NHR && T.np == NP && T.spx == SPX && T.act_floats == ACT_FLOATS && T.ring == ACT_BYTES, "accept.h: action scratch");
+  static_assert(T.kh == T.ring + PRING * 8192 && T.kl == T.kh + NHR * SP * 16 * 2 && T.vt == T.kl + NHR * SP * 16 * 2 &&
+                T.pre == T.vt + NHR * 32 * VLD * 2 && T.park == T.pre + (lds_lang ? LANG_PAIR_BYTES : 0) && T.vlds == T.park + NW * 4096,
+                "accept.h: ring, K, V^T, prefix, park, vectors");
   const int lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
   const int P = NW * 32;
   const int token = wave * 32 + col;
