@@ -63,6 +63,7 @@ struct TrainState {               // what the hvla_train_* entries keep per cont
   int64_t frozen_n = 0;           // the mask's length, one of the two of hvla_train_sizes when it was set ...
   bool frozen_enc = false;        //   ... namely the one of this train_encoder value
   bool language_tokens = false;   // hvla_train_language_tokens: the entries serve this use_language_token context
+  bool noise_set = false;         // hvla_train_noise_set holds a setting (sel.noise, by value; all rates 0 is a setting too)
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
 };
@@ -810,7 +811,7 @@ int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t ou
   if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
   const TrainLayout& L = ctx->train.L;
   out[0] = train_vector_elems(L, ctx->train.sel.ps, train_encoder != 0); out[1] = L.G;
-  out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0); out[3] = L.total;
+  out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0, ctx->train.sel.noise); out[3] = L.total;
   return HVLA_OK;
 }
 
@@ -891,6 +892,41 @@ int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on) {
   return HVLA_OK;
 }
 
+int hvla_train_noise_set(hvla_ctx* ctx, const hvla_train_noise* opts) {
+  if (!ctx) return HVLA_E_STATE;
+  if (!opts) { ctx->train.sel.noise = TrainNoise(); ctx->train.noise_set = false; return HVLA_OK; }
+  if (int rc = train_entry(ctx)) return rc;
+  if (opts->struct_size != sizeof(hvla_train_noise)) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_noise.struct_size %u: this library's is %zu", opts->struct_size, sizeof(hvla_train_noise));
+  const float rates[3] = {opts->policy_dropout, opts->context_dropout, opts->image_dropout};
+  for (float r : rates)
+    if (!std::isfinite(r) || r < 0.f || r >= 1.f) FAIL(ctx, HVLA_E_SHAPE, "dropout rate %g outside [0, 1)", (double)r);
+  const float sg = opts->image_embedding_noise;
+  if (!std::isfinite(sg) || sg < 0.f) FAIL(ctx, HVLA_E_SHAPE, "image_embedding_noise %g must be finite and >= 0", (double)sg);
+  const Geom& g = ctx->g;      // one Philox block is four consecutive elements of a row (accept.h admits no other widths)
+  if (g.D % 4 != 0 || g.M % 4 != 0 || g.E % 4 != 0 || g.C % 4 != 0) FAIL(ctx, HVLA_E_SHAPE, "a noise site's width is no multiple of 4");
+  TrainNoise nz;
+  nz.policy_dropout = rates[0]; nz.sigma = sg; nz.context_dropout = rates[1]; nz.image_dropout = rates[2];
+  nz.key.k0 = (uint32_t)opts->seed; nz.key.k1 = (uint32_t)(opts->seed >> 32);
+  nz.key.draw = opts->draw; nz.key.sample0 = (long)opts->sample_offset;
+  ctx->train.sel.noise = nz;
+  ctx->train.noise_set = true;
+  return HVLA_OK;
+}
+
+int hvla_train_noise_probe(hvla_ctx* ctx, uint32_t site, int64_t sample_id, int64_t n, float* out, void* stream) {
+  if (int rc = train_entry(ctx)) return rc;
+  if (!ctx->train.noise_set) FAIL(ctx, HVLA_E_STATE, "hvla_train_noise_probe without a hvla_train_noise_set setting");
+  const uint32_t kind = site & 0xffu;
+  if (kind < 1 || kind > 7) FAIL(ctx, HVLA_E_SHAPE, "site 0x%x: kinds are 1..7", site);
+  if (!out || n < 1 || n > (1 << 24)) FAIL(ctx, HVLA_E_SHAPE, "n %lld outside [1, 2^24] or null out", (long long)n);
+  const TrainNoise& nz = ctx->train.sel.noise;
+  NoiseKey key = nz.key;
+  key.site = site; key.sample0 = (long)sample_id;
+  const float rate = kind <= NOISE_MLP_OUT ? nz.policy_dropout : kind == NOISE_CONTEXT ? nz.context_dropout : kind == NOISE_IMAGE_CLS ? nz.image_dropout : 0.f;
+  HIPCHK(ctx, train_noise_probe(key, rate, kind == NOISE_TOKENS, n, out, reinterpret_cast<hipStream_t>(stream)));
+  return HVLA_OK;
+}
+
 static TrainBuffers to_tb(const hvla_train_buffers* b) {
   return TrainBuffers{b->params, b->grads, reinterpret_cast<__bf16*>(b->mu), b->nu, b->ema, b->theta, b->dtheta, b->work,
                       b->loss, b->actions, b->logits, b->sqsum, b->wd_mask, b->params0};
@@ -911,6 +947,8 @@ int hvla_train_step(hvla_ctx* ctx, const hvla_train_buffers* buf, const float* t
   if ((tokens != nullptr) == (images != nullptr)) FAIL(ctx, HVLA_E_SHAPE, "pass exactly one of tokens (frozen encoder) / images (trained encoder)");
   if ((images != nullptr) != (hy->train_encoder != 0)) FAIL(ctx, HVLA_E_STATE, "hyper.train_encoder does not match the inputs");
   TrainState& t = ctx->train;
+  if (!hy->forward_only && ((t.sel.noise.sigma > 0.f && tokens && (uintptr_t)tokens % 16 != 0) || (t.sel.noise.image_dropout > 0.f && (uintptr_t)cls % 16 != 0)))
+    FAIL(ctx, HVLA_E_SHAPE, "under hvla_train_noise tokens and cls are read 16 bytes at a time: they must be 16-byte aligned");
   TrainInputs in{tok, mask, cls, tokens, images, target, tmask, amask};
   const TrainHyper hp = to_hp(hy);
   for (hipEvent_t& e : t.ev_bucket)

@@ -5,6 +5,7 @@
 
 #include "../../include/hvla.h"
 #include "layout.h"
+#include "noise.h"
 #include "train_layout.h"
 
 namespace hvla {
@@ -40,7 +41,21 @@ void set_train_gemm_exact(bool on);
 struct BgemmChoice { int tile, vec, ksplit, exact; };
 const BgemmChoice& last_bgemm_choice();
 #endif
-size_t train_workspace_floats(const Geom& g, int B, bool train_encoder);
+// The reference's train=True noise (hvla_train_noise; noise.h).  Off (the default, and every rate 0): train_step
+// launches exactly what it launches without this struct and the workspace has today's size.  On: one element-wise launch per site
+// and pass whose rate is positive; the policy's two residual GEMMs then write the branch into t.y and dropout_fwd_kernel adds it to
+// the residual.  The context encoder's and DINOv2's blocks draw nothing, and neither does a forward_only step.  Workspace: the
+// noisy copy of the frozen encoder's tokens (sigma > 0) and the masked copy of the CLS rows (image_dropout > 0) are taken behind
+// everything else, so every other offset is what it is without noise; the size is asked for AFTER the setting is made.
+struct TrainNoise {
+  float policy_dropout = 0.f, sigma = 0.f, context_dropout = 0.f, image_dropout = 0.f;
+  NoiseKey key;                       // seed, draw, sample_offset (site is filled in per launch)
+  bool on() const { return policy_dropout > 0.f || sigma > 0.f || context_dropout > 0.f || image_dropout > 0.f; }
+};
+size_t train_workspace_floats(const Geom& g, int B, bool train_encoder, const TrainNoise& nz = TrainNoise());
+// hvla_train_noise_probe: out[i] = the multiplier of element i of a dropout site (rate > 0: 0 or 1 / keep_prob) or, with
+// normal, the i-th normal of the site, for the sample whose global index is key.sample0
+hipError_t train_noise_probe(const NoiseKey& key, float rate, bool normal, long n, float* out, hipStream_t st);
 
 struct TrainBuffers {        // all device memory, owned by the caller
   float* params;             // [total]
@@ -109,6 +124,7 @@ struct TrainOptions {
   const uint8_t* frozen = nullptr;    // hvla_train_frozen: the mask of train_apply / train_accumulate ...
   int frozen_buckets = 0;             //   ... and the buckets train_step leaves out
   AttnAux aux;                        // hvla_train_attention_losses
+  TrainNoise noise;                   // hvla_train_noise_set
 };
 // vector length of params / grads / mu / nu: the shared leaves and the position table's source follow the hypernetwork's when
 // the image encoder is trained

@@ -371,6 +371,61 @@ __global__ void gelu_bwd_kernel(const float* __restrict__ u, float* __restrict__
     dg[i] *= erf_form ? dgelu_erf(u[i]) : dgelu_tanh(u[i]);
 }
 
+// ---- the reference's train=True noise (noise.h; hvla_train_noise) ---------------------------------------------
+// A thread owns one Philox block: four consecutive elements of a sample, one 16-byte access per operand.  Samples are blockIdx.y;
+// n4 = the per-sample element count / 4 (every site's width is a multiple of 4 under accept.h), rows 16-byte aligned.
+// out = [res +] drop(x): x / keep_prob where kept, 0 elsewhere.  out may be x (in place); res == null: no residual.
+__global__ void dropout_fwd_kernel(float* out, const float* res, const float* x, int n4, NoiseKey key, uint32_t thr, float keep_prob) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n4) return;
+  const long o = (long)b * n4 + i;
+  const PhiloxWords w = noise_block(key, b, (uint32_t)i);
+  const f32x4 v = reinterpret_cast<const f32x4*>(x)[o];
+  f32x4 y = res ? reinterpret_cast<const f32x4*>(res)[o] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) y[j] += dropout_keep(w.w[j], thr) ? v[j] / keep_prob : 0.f;
+  reinterpret_cast<f32x4*>(out)[o] = y;
+}
+// dx = dy (.) multiplier with the mask regenerated; dx == dy is the in-place form, dx != dy keeps dy (the residual's gradient)
+__global__ void dropout_bwd_kernel(float* dx, const float* dy, int n4, NoiseKey key, uint32_t thr, float keep_prob) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n4) return;
+  const long o = (long)b * n4 + i;
+  const PhiloxWords w = noise_block(key, b, (uint32_t)i);
+  f32x4 v = reinterpret_cast<const f32x4*>(dy)[o];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = dropout_keep(w.w[j], thr) ? v[j] / keep_prob : 0.f;
+  reinterpret_cast<f32x4*>(dx)[o] = v;
+}
+// dst[b] = src[b] + sigma z over [n4 * 4] elements per sample, sample strides in elements (a frozen encoder's tokens into their
+// copy; a trained encoder's patch rows in place behind every sample's CLS row)
+__global__ void token_noise_kernel(float* dst, long dstride, const float* src, long sstride, int n4, NoiseKey key, float sigma) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (i >= n4) return;
+  const PhiloxWords w = noise_block(key, b, (uint32_t)i);
+  f32x4 v = reinterpret_cast<const f32x4*>(src + (long)b * sstride)[i];
+  float z[4];
+  noise_box_muller(w.w[0], w.w[1], z[0], z[1]);
+  noise_box_muller(w.w[2], w.w[3], z[2], z[3]);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = fmaf(sigma, z[j], v[j]);
+  reinterpret_cast<f32x4*>(dst + (long)b * dstride)[i] = v;
+}
+// hvla_train_noise_probe (test instrumentation): element i's multiplier or normal, one element per thread, any n
+__global__ void noise_probe_kernel(float* __restrict__ out, long n, NoiseKey key, uint32_t thr, float keep_prob, int normal) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PhiloxWords w = noise_block(key, 0, (uint32_t)(i >> 2));
+  const int j = (int)(i & 3);
+  if (normal) {
+    float z0, z1;
+    noise_box_muller(w.w[j & 2], w.w[(j & 2) + 1], z0, z1);
+    out[i] = j & 1 ? z1 : z0;
+  } else {
+    out[i] = dropout_keep(w.w[j], thr) ? 1.f / keep_prob : 0.f;
+  }
+}
+
 // column sums: out[b * ostride + n] += sum_{r < rows_used} x[b][r][n]  (bias gradients).  blockIdx.z splits the rows
 // into chunks of 64 that are reduced with one atomic each, so long shared-parameter reductions stay parallel.
 __global__ void colsum_kernel(const float* __restrict__ x, float* __restrict__ out, long ostride, int R, int rows_used,
@@ -791,8 +846,17 @@ template <class T> static Blk<T> bind(T* base, const BlockLeaves& y) {
 }
 // block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
 // HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention)
-struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; int mask_as_bias = 0; };     // lang_T > 0: the policy's mask with T language rows in front;
-                                                                                                              // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel)
+// one dropout rate with its key (noise.h): thr == 0 is off, and nothing is launched
+struct Drop {
+  uint32_t thr = 0; float keep_prob = 1.f; NoiseKey key;
+  Drop() = default;
+  Drop(float rate, const NoiseKey& k) : thr(rate > 0.f ? dropout_threshold(rate) : 0), keep_prob(1.0f - rate), key(k) {}
+  bool on() const { return thr > 0; }
+  NoiseKey at(uint32_t kind, int layer = 0) const { NoiseKey k = key; k.site = kind | (uint32_t)layer << 8; return k; }
+};
+struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; int mask_as_bias = 0;     // lang_T > 0: the policy's mask with T language rows in front;
+                Drop drop; int layer = 0; };                                                             // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel);
+                                                                                                          // drop: vit_kwargs.dropout_rate at the sites of `layer` (the policy only)
 struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y; };
 
 // Y[nb][S][N] (+)= X[nb][S][K] W + bias with W per episode (ws = G) or shared (ws = 0: the batch folds into M, so
@@ -813,9 +877,18 @@ static void scale_add(hipStream_t st, float* out, const float* res, const float*
   else KL(scale_add_kernel, g1(n), dim3(256), out, res, y, ls, n, D);
 }
 
+// out = [res +] drop(x) / dx = dy (.) multiplier over nb samples of n elements each (n % 4 == 0)
+static void dropout_fwd(hipStream_t st, const Drop& d, uint32_t kind, int layer, float* out, const float* res, const float* x, int nb, long n) {
+  KL(dropout_fwd_kernel, dim3((unsigned)((n / 4 + 255) / 256), nb), dim3(256), out, res, x, (int)(n / 4), d.at(kind, layer), d.thr, d.keep_prob);
+}
+static void dropout_bwd(hipStream_t st, const Drop& d, uint32_t kind, int layer, float* dx, const float* dy, int nb, long n) {
+  KL(dropout_bwd_kernel, dim3((unsigned)((n / 4 + 255) / 256), nb), dim3(256), dx, dy, (int)(n / 4), d.at(kind, layer), d.thr, d.keep_prob);
+}
+
 static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long ws, const BlkW& w, const BlkBuf& a,
                       float* x_out, const BlkTmp& t, const BlkOpt& op) {
   const int hd = D / H, rows = nb * S;
+  const Drop& dr = op.drop;
   float* const h = a.h ? a.h : t.h;
   float* const h2 = a.h2 ? a.h2 : t.h;
   float* const gg = a.g ? a.g : t.g;
@@ -858,6 +931,9 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   if (w.ls1) {
     linear(st, nb, S, ws, a.o, w.wo, w.bo, a.y1, D, D, 0);
     scale_add(st, a.x_mid, a.x_in, a.y1, w.ls1, (long)rows * D, D);
+  } else if (dr.on()) {                                                    // the branch into t.y (free in a block without LayerScale), then x_mid = x_in + drop(y)
+    linear(st, nb, S, ws, a.o, w.wo, w.bo, t.y, D, D, 0);
+    dropout_fwd(st, dr, NOISE_ATTN_OUT, op.layer, a.x_mid, a.x_in, t.y, nb, (long)S * D);
   } else {
     ENQ(hipMemcpyAsync, a.x_mid, a.x_in, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
     linear(st, nb, S, ws, a.o, w.wo, w.bo, a.x_mid, D, D, 1);
@@ -865,9 +941,13 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_mid, h2, a.mean1, a.rstd1, w.l1s, w.l1b, ws, rows, S, D);
   linear(st, nb, S, ws, h2, w.w1, w.b1, a.u, D, F, 0);
   KL(gelu_fwd_kernel, g1((long)rows * F), dim3(256), a.u, gg, (long)rows * F, op.gelu_erf);
+  if (dr.on()) dropout_fwd(st, dr, NOISE_MLP_HIDDEN, op.layer, gg, nullptr, gg, nb, (long)S * F);     // g is kept (or recomputed) dropped
   if (w.ls2) {
     linear(st, nb, S, ws, gg, w.w2, w.b2, a.y2, F, D, 0);
     scale_add(st, x_out, a.x_mid, a.y2, w.ls2, (long)rows * D, D);
+  } else if (dr.on()) {
+    linear(st, nb, S, ws, gg, w.w2, w.b2, t.y, F, D, 0);
+    dropout_fwd(st, dr, NOISE_MLP_OUT, op.layer, x_out, a.x_mid, t.y, nb, (long)S * D);
   } else {
     ENQ(hipMemcpyAsync, x_out, a.x_mid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
     linear(st, nb, S, ws, gg, w.w2, w.b2, x_out, F, D, 1);
@@ -917,14 +997,20 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   const float* gg = a.g ? a.g : t.g;
   if (!a.h2) KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_mid, t.h, a.mean1, a.rstd1, w.l1s, w.l1b, ws, rows, S, D);   // recompute h2
   if (!a.g) KL(gelu_fwd_kernel, g1((long)rows * F), dim3(256), a.u, t.g, (long)rows * F, op.gelu_erf);                           // recompute g
+  const Drop& dr = op.drop;
+  if (!a.g && dr.on()) dropout_fwd(st, dr, NOISE_MLP_HIDDEN, op.layer, t.g, nullptr, t.g, nb, (long)S * F);                       //   ... dropped, as block_fwd left it
   const float* dy = dx;
   if (w.ls2) {
     ls_bwd(dx, a.y2, w.ls2, t.y, gw.ls2);
+    dy = t.y;
+  } else if (dr.on()) {                                                                                                 // the branch's gradient into t.y, dx stays the residual's
+    dropout_bwd(st, dr, NOISE_MLP_OUT, op.layer, t.y, dx, nb, (long)S * D);
     dy = t.y;
   }
   wgrad(gg, F, dy, D, gw.w2);
   bgrad(dy, D, gw.b2);
   linear_dx(st, nb, S, ws, dy, w.w2, t.d, F, D, 0);                                                                     // dg = dy W2^T
+  if (dr.on()) dropout_bwd(st, dr, NOISE_MLP_HIDDEN, op.layer, t.d, t.d, nb, (long)S * F);
   KL(gelu_bwd_kernel, g1((long)rows * F), dim3(256), a.u, t.d, (long)rows * F, op.gelu_erf);                           // du
   wgrad(h2, D, t.d, F, gw.w1);
   bgrad(t.d, F, gw.b1);
@@ -935,6 +1021,9 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   dy = dx;
   if (w.ls1) {
     ls_bwd(dx, a.y1, w.ls1, t.y, gw.ls1);
+    dy = t.y;
+  } else if (dr.on()) {
+    dropout_bwd(st, dr, NOISE_ATTN_OUT, op.layer, t.y, dx, nb, (long)S * D);
     dy = t.y;
   }
   wgrad(a.o, D, dy, D, gw.wo);
@@ -973,8 +1062,9 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     // and a language query's few keys carry ds entries of the size of dp: with the language rows the leaf is left at the zero it is
     // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.  With the mask added as a
     // bias every query has every key, the constant is still one per row, and the leaf is left at zero in the same way:
-    // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.
-    if (!((op.lang_T > 0 || op.mask_as_bias) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
+    // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.  Under the policy's
+    // dropout (hvla_train_noise) the kept activations are 1 / keep_prob larger and the same rounding came to 1.5e-3 at MID: left at zero too.
+    if (!((op.lang_T > 0 || op.mask_as_bias || dr.on()) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
     linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0);                                                         // dh
   }
   ln_bwd(a.x_in, t.g, a.mean0, a.rstd0, w.l0s, gw.l0s, gw.l0b);
@@ -986,12 +1076,13 @@ struct Plan {
   float *cx_fin, *cdx, *px_fin, *pdx, *ex_fin, *edx, *eh, *patches;
   BlkTmp t;
   float *cmean, *crstd, *ctx, *dctx, *ctxn, *dxrow, *emean, *erstd;
+  float *ntok, *ncls;        // hvla_train_noise: the frozen encoder's tokens + sigma z, the masked CLS rows (null: not taken)
   long used;
 #ifdef HVLA_TRAIN_TRACE
   std::vector<std::pair<long, long>> taken;      // (offset, floats asked for) of every take(), in order: train_trace_plan prints them
 #endif
 };
-static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
+static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNoise& nz) {
   Plan pl;
   float* ws = base;
 #ifdef HVLA_TRAIN_TRACE
@@ -1032,19 +1123,22 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base) {
   pl.t.y = take(rd);
   pl.cmean = take(B); pl.crstd = take(B); pl.ctx = take(B * C); pl.dctx = take(B * C); pl.ctxn = take(B * C);
   pl.dxrow = take(B * D);
+  // the noise copies come last: every offset above is what it is without noise
+  pl.ntok = nz.sigma > 0.f && !enc ? take((long)B * g.P() * E) : nullptr;
+  pl.ncls = nz.image_dropout > 0.f ? take((long)B * E) : nullptr;
   pl.used = ws - base;
   return pl;
 }
-size_t train_workspace_floats(const Geom& g, int B, bool train_encoder) {
-  return (size_t)make_plan(g, B, train_encoder, nullptr).used + 64;
+size_t train_workspace_floats(const Geom& g, int B, bool train_encoder, const TrainNoise& nz) {
+  return (size_t)make_plan(g, B, train_encoder, nullptr, nz).used + 64;
 }
 #ifdef HVLA_TRAIN_TRACE
 // One line `plan <name> <offset> <floats>` per buffer of make_plan (offsets into `work`, the floats the plan asked for), for
 // tools/train_extent_trace.hip: tests/test_train_workspace_extents.py holds every traced operand to ONE of these buffers.  A buffer
 // make_plan takes without a name below prints as `?`, which that test refuses.
-void train_trace_plan(const Geom& g, int B, bool train_encoder) {
+void train_trace_plan(const Geom& g, int B, bool train_encoder, const TrainNoise& nz) {
   float* const base = static_cast<float*>(train_trace_buffer("work"));
-  const Plan pl = make_plan(g, B, train_encoder, base);
+  const Plan pl = make_plan(g, B, train_encoder, base, nz);
   std::vector<std::string> name(pl.taken.size(), "?");
   auto put = [&](const std::string& n, const float* p) {
     if (!p) return;
@@ -1067,6 +1161,7 @@ void train_trace_plan(const Geom& g, int B, bool train_encoder) {
   put("t.h", pl.t.h); put("t.g", pl.t.g); put("t.d", pl.t.d); put("t.dk", pl.t.dk); put("t.dq", pl.t.dq); put("t.dv", pl.t.dv);
   put("t.dp", pl.t.dp); put("t.y", pl.t.y);
   put("cmean", pl.cmean); put("crstd", pl.crstd); put("ctx", pl.ctx); put("dctx", pl.dctx); put("ctxn", pl.ctxn); put("dxrow", pl.dxrow);
+  put("ntok", pl.ntok); put("ncls", pl.ncls);
   for (size_t i = 0; i < pl.taken.size(); ++i) printf("plan %s %ld %ld\n", name[i].c_str(), pl.taken[i].first, pl.taken[i].second);
 }
 #endif
@@ -1082,7 +1177,10 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
   const bool enc = in.images != nullptr;
   const long G = L.G;
-  const Plan pl = make_plan(g, B, enc, tb.work);
+  // forward_only (validation, train=False) draws nothing; the plan is the setting's, so a step and a validation share offsets
+  const TrainNoise nz = hp.forward_only ? TrainNoise() : opt.noise;
+  const Drop pdrop(nz.policy_dropout, nz.key), cdrop(nz.context_dropout, nz.key), idrop(nz.image_dropout, nz.key);
+  const Plan pl = make_plan(g, B, enc, tb.work, opt.noise);
   const std::vector<BlkBuf>&cb = pl.cb, &pb = pl.pb, &eb = pl.eb;
   float *cx_fin = pl.cx_fin, *cdx = pl.cdx, *px_fin = pl.px_fin, *pdx = pl.pdx;
   float *cmean = pl.cmean, *crstd = pl.crstd, *ctx = pl.ctx, *dctx = pl.dctx, *ctxn = pl.ctxn, *dxrow = pl.dxrow;
@@ -1094,7 +1192,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
   ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
-  const BlkOpt ctx_opt{1, in.attn_mask, 0}, pol_opt{0, nullptr, 0, Tl, g.mask_as_bias}, enc_opt{2, nullptr, 1};
+  const BlkOpt ctx_opt{1, in.attn_mask, 0}, enc_opt{2, nullptr, 1};      // these two draw nothing
+  const BlkOpt pol_opt{0, nullptr, 0, Tl, g.mask_as_bias, pdrop};
+  const auto pol_at = [&](int l) { BlkOpt o = pol_opt; o.layer = l; return o; };      // the dropout sites carry their layer
 
   // =============================== DINOv2 forward in f32, activations kept (HF Dinov2Model; base_vit.py:111-131) =====
   const float* tokens = in.tokens;         // [B][P][E] rows, episode stride tok_stride
@@ -1111,17 +1211,33 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     tokens = pl.eh + E;                    // drop the CLS row through the pointer: rows 1.. of every [Se][E] block
     tok_stride = (long)Se * E;
   }
+  // image_embedding_noise (base_vit.py:123-127): tokens + sigma z, onto the trained encoder's own output (the gradient passes the
+  // addition unchanged) or into the workspace's copy of the frozen encoder's
+  if (nz.sigma > 0.f) {
+    float* const dst = enc ? pl.eh + E : pl.ntok;
+    const long dstride = enc ? tok_stride : (long)P * E;
+    KL(token_noise_kernel, dim3((unsigned)((P * E / 4 + 255) / 256), B), dim3(256), dst, dstride, tokens, tok_stride, P * E / 4, Drop(0.f, nz.key).at(NOISE_TOKENS), nz.sigma);
+    tokens = dst;
+    tok_stride = dstride;
+  }
+  // image_dropout (hypernetwork.py:119-122) on the CLS row the context path reads, into its copy
+  const float* cls = in.cls;
+  if (idrop.on()) {
+    dropout_fwd(st, idrop, NOISE_IMAGE_CLS, 0, pl.ncls, nullptr, in.cls, B, E);
+    cls = pl.ncls;
+  }
 
   // =============================== context encoder forward (hypernetwork.py:99-197) ===============================
   float* cx0 = cb.empty() ? cx_fin : cb[0].x_in;
   // tokens: [B][T][lang] . Wt + bt + pos_t  (rows 0..T-1 of each episode's [Sc][C] block)
   bgemm(st, false, false, BG{in.tok, Pm + L.w_tok, cx0, Pm + L.b_tok, T, C, g.lang_dim, g.lang_dim, C, C, (long)T * g.lang_dim, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
-  bgemm(st, false, false, BG{in.cls, Pm + L.w_img, cx0 + (long)T * C, Pm + L.b_img, 1, C, E, E, C, C, (long)E, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
+  bgemm(st, false, false, BG{cls, Pm + L.w_img, cx0 + (long)T * C, Pm + L.b_img, 1, C, E, E, C, C, (long)E, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
   KL(ctx_rows_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, C);
   for (int l = 0; l < g.ctx_layers; ++l)
     block_fwd(st, B, Sc, C, Hc, Fc, 0, bind(Pm, L.layer[l]), cb[l], l + 1 < g.ctx_layers ? cb[l + 1].x_in : cx_fin, t, ctx_opt);
   // ctx = LN_f(x[:, -1]) (/ sqrt(C)); rows gathered through a stride: x = cx_fin + (Sc-1)*C, row stride Sc*C
   KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+  if (cdrop.on()) dropout_fwd(st, cdrop, NOISE_CONTEXT, 0, ctx, nullptr, ctx, B, C);      // embedding_dropout_rate (hypernetwork.py:193-195)
   // =============================== theta = ctx W_cat + b_cat (hypernetwork.py:205-233) ===============================
   bgemm(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0}, 1);
   // =============================== policy forward with per-episode weights ===============================
@@ -1131,8 +1247,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   if (Tl) bgemm(st, false, false, BG{in.tok, TH + L.wl, px0, TH + L.bl, Tl, D, g.lang_dim, g.lang_dim, D, D, (long)Tl * g.lang_dim, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
   bgemm(st, false, false, BG{tokens, TH + L.wp, px0 + (long)Tl * D, TH + L.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
   KL(x0_finish_kernel, g1((long)B * S * D), dim3(256), px0, TH + L.pos, G, S, D, B);
+  if (pdrop.on()) dropout_fwd(st, pdrop, NOISE_POLICY_INPUT, 0, px0, nullptr, px0, B, (long)S * D);      // base_vit.py:205
   for (int l = 0; l < g.L; ++l)
-    block_fwd(st, B, S, D, H, F, G, bind(TH, L.pol[l]), pb[l], l + 1 < g.L ? pb[l + 1].x_in : px_fin, t, pol_opt);
+    block_fwd(st, B, S, D, H, F, G, bind(TH, L.pol[l]), pb[l], l + 1 < g.L ? pb[l + 1].x_in : px_fin, t, pol_at(l));
   // =============================== head + loss (+ backward seed) ===============================
   ENQ(hipMemsetAsync, pdx, 0, (size_t)B * S * D * 4, st);
   HeadP hpp{px_fin, (long)S * D, TH, tb.dtheta, G, (int)L.wc, (int)L.bc, (int)L.wd, (int)L.bd, (int)L.ns, (int)L.nb, in.target, in.tmask, in.amask,
@@ -1148,8 +1265,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   KL(add_strided_kernel, g1((long)B * D), dim3(256), pdx + (long)(S - 1) * D, (long)S * D, dxrow, (long)D, B);
   // =============================== policy backward ===============================
   for (int l = g.L - 1; l >= 0; --l)
-    block_bwd(st, B, S, D, H, F, G, G, bind(TH, L.pol[l]), bind(tb.dtheta, L.pol[l]), pb[l], pdx, t, pol_opt, aux.on() && l == g.L - 1 ? &auxp : nullptr);
+    block_bwd(st, B, S, D, H, F, G, G, bind(TH, L.pol[l]), bind(tb.dtheta, L.pol[l]), pb[l], pdx, t, pol_at(l), aux.on() && l == g.L - 1 ? &auxp : nullptr);
   // x0 = [tok Wl + bl ; tokens Wp + bp ; 0] + pos : dpos = dx0, dbp = sum of the P patch rows of dx0, dWp = tokens^T dx0[Tl : Tl + P]
+  if (pdrop.on()) dropout_bwd(st, pdrop, NOISE_POLICY_INPUT, 0, pdx, pdx, B, (long)S * D);
   const float* pdx_patch = pdx + (long)Tl * D;
   KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + L.pos, G, pdx, (long)S * D, B);
   KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx_patch, tb.dtheta + L.bp, G, S, P, D, B);
@@ -1192,6 +1310,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     ENQ(hipMemsetAsync, dctx, 0, (size_t)B * C * 4, st);
     // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
     bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
+    if (cdrop.on()) dropout_bwd(st, cdrop, NOISE_CONTEXT, 0, dctx, dctx, B, C);
   }
   if (bucket_done) ENQ(hipEventRecord, bucket_done[1], st);             // W_cat, b_cat are final
   // =============================== context encoder backward ===============================
@@ -1203,7 +1322,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
     KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
     bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
-    bgemm(st, true, false, BG{in.cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
+    bgemm(st, true, false, BG{cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
   }
   if (bucket_done) ENQ(hipEventRecord, bucket_done[2], st);             // the context encoder's leaves: everything is final
   return hipGetLastError();
@@ -1257,6 +1376,13 @@ hipError_t train_accumulate(const TrainLayout& L, const TrainBuffers& tb, float*
   const long n = train_vector_elems(L, opt.ps, train_encoder);
   launch_sqsum(st, tb, opt.frozen, n);
   KL(accumulate_kernel, dim3(2048), dim3(256), acc, tb.grads, n, tb.sqsum, hp.clip, inv_k);
+  return hipGetLastError();
+}
+
+
+hipError_t train_noise_probe(const NoiseKey& key, float rate, bool normal, long n, float* out, hipStream_t st) {
+  const Drop d(rate, key);
+  KL(noise_probe_kernel, g1(n), dim3(256), out, n, key, d.thr, d.keep_prob, normal ? 1 : 0);
   return hipGetLastError();
 }
 

@@ -28,7 +28,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_create_with", "hvla_create_with_v2", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
-           "hvla_loss_terms", "hvla_train_metrics"]
+           "hvla_loss_terms", "hvla_train_metrics", "hvla_train_noise_set", "hvla_train_noise_probe"]
 # hvla_train_metrics (include/hvla.h): select bits, the slots of its output vector, the size of its scratch
 HVLA_METRICS_PRE, HVLA_METRICS_UPDATE = 1, 2
 (HVLA_METRIC_TRAINING_LOSS, HVLA_METRIC_CONTINUOUS_LOSS, HVLA_METRIC_GRIPPER_LOSS, HVLA_METRIC_MSE, HVLA_METRIC_BASE_PARAMS_NORM,
@@ -89,6 +89,13 @@ class hvla_train_attention(C.Structure):
     """Options of hvla_train_attention_losses (include/hvla.h): struct_size must be sizeof(hvla_train_attention)."""
     _fields_ = [("struct_size", C.c_uint32), ("entropy_weight", C.c_float), ("alignment_weight", C.c_float),
                 ("reference_map", C.c_void_p), ("entropy", C.c_void_p), ("alignment", C.c_void_p)]
+
+
+class hvla_train_noise(C.Structure):
+    """Options of hvla_train_noise_set (include/hvla.h): struct_size must be sizeof(hvla_train_noise)."""
+    _fields_ = [("struct_size", C.c_uint32), ("policy_dropout", C.c_float), ("image_embedding_noise", C.c_float),
+                ("context_dropout", C.c_float), ("image_dropout", C.c_float), ("seed", C.c_uint64), ("sample_offset", C.c_int64),
+                ("draw", C.c_uint32)]
 
 
 class hvla_train_metrics_in(C.Structure):
@@ -195,6 +202,10 @@ def load_library():
     lib.hvla_train_attention_losses.restype = C.c_int
     lib.hvla_train_language_tokens.argtypes = [vp, i32]
     lib.hvla_train_language_tokens.restype = C.c_int
+    lib.hvla_train_noise_set.argtypes = [vp, vp]
+    lib.hvla_train_noise_set.restype = C.c_int
+    lib.hvla_train_noise_probe.argtypes = [vp, C.c_uint32, i64, i64, vp, vp]
+    lib.hvla_train_noise_probe.restype = C.c_int
     lib.hvla_train_bucket_ranges.argtypes = [vp, i32, C.POINTER(C.c_int64)]
     lib.hvla_train_bucket_ranges.restype = C.c_int
     lib.hvla_train_wait_bucket.argtypes = [vp, i32, vp]
@@ -484,6 +495,25 @@ class Context:
                                         reference_ptr or None, entropy_ptr or None, alignment_ptr or None)
             rc = self.lib.hvla_train_attention_losses(self.h, C.byref(opts))
         self._check(rc, "hvla_train_attention_losses")
+
+    def train_noise(self, policy_dropout=0.0, image_embedding_noise=0.0, context_dropout=0.0, image_dropout=0.0, seed=0,
+                    sample_offset=0, draw=0, off=False):
+        """The reference's train=True noise for the following train_step calls (hvla_train_noise_set; by value).  `off`: NULL, the
+        state of a new context.  Make the setting before train_sizes: the noisy copies live in the workspace."""
+        if off:
+            rc = self.lib.hvla_train_noise_set(self.h, None)
+        else:
+            opts = hvla_train_noise(C.sizeof(hvla_train_noise), float(policy_dropout), float(image_embedding_noise),
+                                    float(context_dropout), float(image_dropout), int(seed) & (2 ** 64 - 1), int(sample_offset),
+                                    int(draw) & 0xffffffff)
+            rc = self.lib.hvla_train_noise_set(self.h, C.byref(opts))
+        self._check(rc, "hvla_train_noise_set")
+
+    def train_noise_probe(self, site, sample_id, n, out_ptr, stream: int = 0):
+        """Test instrumentation: the n multipliers (kinds 1-4, 6, 7) or normals (kind 5) of `site` = kind | layer << 8 for the sample
+        with global index `sample_id`, under the current setting, into device f32 [n]."""
+        self._check(self.lib.hvla_train_noise_probe(self.h, int(site), int(sample_id), int(n), C.c_void_p(out_ptr), C.c_void_p(stream)),
+                    "hvla_train_noise_probe")
 
     def train_language_tokens(self, on=False):
         """Fine-tune a use_language_token context: while on, the hvla_train_* entries serve it (off: they refuse it, the default)."""

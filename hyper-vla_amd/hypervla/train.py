@@ -278,6 +278,85 @@ def check_reference_attention(attention_map_alignment: float, reference_attentio
         raise ValueError(f"reference_attention must be [{batch}, {patches}], got {shape}")
 
 
+# ---- the train=True noise (hvla_train_noise_set; csrc/noise.h), restated on the host bit for bit -----------------
+# kinds of a noise site; site = kind | layer << 8
+(NOISE_POLICY_INPUT, NOISE_ATTN_OUT, NOISE_MLP_HIDDEN, NOISE_MLP_OUT, NOISE_TOKENS, NOISE_CONTEXT, NOISE_IMAGE_CLS) = range(1, 8)
+
+
+def philox4x32(counter, key, rounds: int = 10) -> np.ndarray:
+    """Philox4x32 (Salmon et al., SC'11; Random123's constants): `counter` uint32 [..., 4] and `key` uint32 [..., 2] (broadcast
+    against each other) -> uint32 [..., 4].  csrc/noise.h's philox4x32_10 word for word."""
+    c = np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    k = np.asarray(key, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).copy() for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).copy() for i in range(2))
+    m32, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(rounds):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m32, (p0 >> s32) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def noise_site(kind: int, layer: int = 0) -> int:
+    return int(kind) | int(layer) << 8
+
+
+def noise_words(seed: int, site: int, sample_id: int, draw: int, n: int) -> np.ndarray:
+    """uint32 [n]: the word of elements [0, n) of `site` for the sample with GLOBAL index `sample_id`: element e is word e & 3 of
+    the block with counter (e >> 2, sample_id, site, draw) under key (seed lo, seed hi)."""
+    blocks = (int(n) + 3) // 4
+    ctr = np.empty((blocks, 4), np.uint32)
+    ctr[:, 0] = np.arange(blocks, dtype=np.uint32)
+    ctr[:, 1], ctr[:, 2], ctr[:, 3] = int(sample_id) & 0xFFFFFFFF, int(site) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFF
+    seed = int(seed) & (2 ** 64 - 1)
+    return philox4x32(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint32)).reshape(-1)[:int(n)]
+
+
+def dropout_threshold(rate: float) -> int:
+    """ceil(rate 2^24) on the float32 rate in double, as the library computes it: P(keep) = 1 - threshold / 2^24."""
+    return int(np.ceil(float(np.float32(rate)) * 2.0 ** 24))
+
+
+def noise_multipliers(rate: float, seed: int, site: int, sample_id: int, draw: int, n: int) -> np.ndarray:
+    """float32 [n]: 1 / keep_prob where (word >> 8) >= threshold, else 0; keep_prob = float32(1) - float32(rate)."""
+    keep = (noise_words(seed, site, sample_id, draw, n) >> np.uint32(8)) >= np.uint32(dropout_threshold(rate))
+    return np.where(keep, np.float32(1.0) / (np.float32(1.0) - np.float32(rate)), np.float32(0.0)).astype(np.float32)
+
+
+def noise_normals(seed: int, site: int, sample_id: int, draw: int, n: int) -> np.ndarray:
+    """float64 [n]: Box-Muller on the word pairs (w0, w1) and (w2, w3) of every block, evaluated in double (the device evaluates
+    the same expression in float32): u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24, z0 = sqrt(-2 ln u1) cos(2 pi u2) for the
+    pair's first element and z1 = sqrt(-2 ln u1) sin(2 pi u2) for its second."""
+    w = noise_words(seed, site, sample_id, draw, (int(n) + 3) // 4 * 4).reshape(-1, 2)
+    u1 = ((w[:, 0] >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    u2 = (w[:, 1] >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
+    r = np.sqrt(-2.0 * np.log(u1))
+    return np.stack([r * np.cos(2.0 * np.pi * u2), r * np.sin(2.0 * np.pi * u2)], axis=-1).reshape(-1)[:int(n)]
+
+
+def train_noise_from_config(config) -> Dict[str, float]:
+    """FineTuner's noise keywords from a reference-shaped config (the dict of `config.model`, or one that holds it under "model"):
+    vit_kwargs.dropout_rate, vit_kwargs.image_embedding_noise, hypernet_kwargs.embedding_dropout_rate, hypernet_kwargs.image_dropout.
+    ValueError, naming the key, for the noise that is not built: a non-zero context_encoder_kwargs.dropout_rate or
+    .attention_dropout_rate, or hypernet_kwargs.final_dropout_rate."""
+    cfg = config.get("model", config)
+    h = cfg.get("hypernet_kwargs", {})
+    v = cfg.get("base_net_kwargs", {}).get("vit_kwargs", {})
+    ce = h.get("context_encoder_kwargs", {})
+    for where, d, key in (("hypernet_kwargs.context_encoder_kwargs", ce, "dropout_rate"),
+                          ("hypernet_kwargs.context_encoder_kwargs", ce, "attention_dropout_rate"),
+                          ("hypernet_kwargs", h, "final_dropout_rate")):
+        if float(d.get(key, 0.0) or 0.0) != 0.0:
+            raise ValueError(f"{where}.{key}={d.get(key)!r} is not built: the fine-tune step draws the policy's dropout, the image "
+                             "embedding noise, embedding_dropout_rate and image_dropout only (DESIGN.md §21)")
+    return dict(dropout_rate=float(v.get("dropout_rate", 0.0) or 0.0),
+                image_embedding_noise=float(v.get("image_embedding_noise", 0.0) or 0.0),
+                embedding_dropout_rate=float(h.get("embedding_dropout_rate", 0.0) or 0.0),
+                image_dropout=float(h.get("image_dropout", 0.0) or 0.0))
+
+
 # The keys of the reference's `info` (scripts/train.py:506-529) that FineTuner.info() returns, in its order; one
 # `task_loss_<name>` per task follows, and the two attention terms are present only while their coefficient is positive.
 INFO_KEYS = ("training_loss", "grad_norm", "update_norm", "param_norm", "learning_rate", "continuous_loss", "gripper_loss",
@@ -362,17 +441,29 @@ class FineTuner:
     `language_tokens=True`: fine-tune a model with `vit_kwargs.use_language_token` (hvla_train_language_tokens): the
     policy runs with the instruction's token embeddings in front of the patches, as the reference's loop does for such a model; the
     two heads `output_head_encoder_language_token_projection_{kernel,bias}` train (or freeze, `frozen_keys`) like every other head.
-    Without the keyword such a model is refused; the attention terms are not defined for it."""
+    Without the keyword such a model is refused; the attention terms are not defined for it.
+    `dropout_rate`, `image_embedding_noise`, `embedding_dropout_rate`, `image_dropout` (all 0 = off, the default; `train_noise_from_config`
+    reads them from a reference-shaped config): the four noise sources the reference's loop switches on with train=True
+    (hvla_train_noise_set), drawn from a counter-based generator keyed by `noise_seed` -- equal to jax's noise in
+    distribution, not in bits.  Every forward_backward that is not forward_only draws afresh (`noise_draw` counts them, micro-batches
+    of a gradient accumulation included); a sample's noise depends on its global index rank * batch + row, not on its row;
+    `validate()` draws nothing."""
 
     def __init__(self, model, batch: int, peak_lr: float = 3e-4, weight_decay: float = 0.05, clip: float = 1.0,
                  ema_decay: float = 0.999, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
                  train_encoder: bool = False, base_lr: float = 3e-5, base_weight_decay: float = 0.0,
                  weight_decay_strategy: str = "v5", ema_start_step: int = 5000, grad_accumulation_steps: int = 1,
                  accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
-                 attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=(), language_tokens: bool = False):
+                 attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=(), language_tokens: bool = False,
+                 dropout_rate: float = 0.0, image_embedding_noise: float = 0.0, embedding_dropout_rate: float = 0.0,
+                 image_dropout: float = 0.0, noise_seed: int = 0):
         self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
             attention_entropy, attention_map_alignment, num_steps)
         self.language_tokens = bool(language_tokens)
+        self.noise = dict(policy_dropout=float(dropout_rate), image_embedding_noise=float(image_embedding_noise),
+                          context_dropout=float(embedding_dropout_rate), image_dropout=float(image_dropout))
+        self.noise_on = any(v != 0.0 for v in self.noise.values())
+        self.noise_seed, self.noise_draw = int(noise_seed), 0
         if getattr(model.geometry, "lang_in_policy", False) and not self.language_tokens:
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")
@@ -495,6 +586,7 @@ class FineTuner:
         self._select_language()
         self._select_source()
         self._select_frozen()
+        self._select_noise()
         return self._select_attention(reference) if attention else None
 
     def _select_language(self):
@@ -514,6 +606,17 @@ class FineTuner:
             self.model._ctx.train_frozen(0, 0, 0)
         else:
             self.model._ctx.train_frozen(self.frozen.data_ptr(), self.frozen.numel(), self.frozen_buckets)
+
+    def _select_noise(self):
+        """... and which noise it trains with (hvla_train_noise_set, by value: the rates, the seed, this rank's first global sample
+        index and the current draw; off for a FineTuner without noise).  In front of train_sizes too: the noisy copies of the tokens
+        and the CLS rows live in the workspace."""
+        if not self.noise_on:
+            self.model._ctx.train_noise(off=True)
+            return
+        import torch.distributed as dist
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        self.model._ctx.train_noise(seed=self.noise_seed, sample_offset=rank * self.B, draw=self.noise_draw, **self.noise)
 
     def _select_attention(self, reference=None):
         """... and which attention terms its loss has (hvla_train_attention_losses; off for a FineTuner without them).  The alignment
@@ -604,6 +707,8 @@ class FineTuner:
         if self.metrics:
             self.task_ids = m._dev(ids, torch.int32) if ids is not None else None
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
+        if self.noise_on and not forward_only:
+            self.noise_draw += 1                           # every differentiated step draws afresh (a forward-only one draws nothing)
         wa = self._select(ref, attention=True)
         m._ctx.train_step(self.buf, ptrs, self.B, self._hyper(0.0, forward_only), m._stream())
         self.aux_metrics = {}
@@ -760,6 +865,7 @@ class FineTuner:
         self._select_language()
         self._select_source()
         self._select_frozen()
+        self._select_noise()                            # (the plan's offsets are the setting's; a forward-only step draws nothing)
         m._ctx.train_attention_losses()                 # off; the next step selects its own again
         ptrs = [tok.data_ptr(), msk.data_ptr(), cls.data_ptr(), tkn_ptr, img_ptr, tgt.data_ptr(), tm.data_ptr(), am.data_ptr()]
         m._ctx.train_step(bufs[bool(ema)], ptrs, self.B, self._hyper(0.0, True), m._stream())

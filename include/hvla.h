@@ -488,6 +488,49 @@ int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts)
  * heads output_head_*_key_bias): with few language keys the column sum that forms it carried only operand rounding.
  * HVLA_E_SHAPE: on == 1 on a context created without use_language_token; any other value.  NULL ctx: HVLA_E_STATE.           */
 int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on);
+/* Replaces: the four noise sources the reference's training loop switches on by running the model with train=True --
+ * vit_kwargs.dropout_rate (base_vit.py:205; transformer.py:67,74,192), vit_kwargs.image_embedding_noise (base_vit.py:123-127),
+ * hypernet_kwargs.embedding_dropout_rate (hypernetwork.py:193-195) and hypernet_kwargs.image_dropout (hypernetwork.py:119-122).
+ * Deviation: the random bits are not jax's threefry bits; the noise is EQUAL IN DISTRIBUTION to the reference's, not bit-equal.
+ * It comes from a counter-based generator with no state and no stored masks (csrc/noise.h): Philox4x32-10 with key = seed and
+ * counter = (element >> 2, sample_offset + b, site, draw), element e taking word e & 3 of its block; the backward pass regenerates
+ * what the forward pass drew, and hypervla.train.philox4x32 restates it on the host bit for bit.
+ *   dropout: keep iff (word >> 8) >= ceil(rate 2^24); y = x / (1.0f - rate) where kept, else 0 (flax divides)
+ *   normals: Box-Muller on the word pairs (w0, w1), (w2, w3): u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24,
+ *            z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2)
+ * site = kind | layer << 8, element index row-major over the per-sample shape:
+ *   1 policy input after + pos_embedding [S, dim] (S includes the language prefix)      policy_dropout
+ *   2 layer l: attention branch behind out-projection and bias [S, dim]                  policy_dropout
+ *   3 layer l: behind the GELU [S, mlp]                                                  policy_dropout
+ *   4 layer l: MLP output in front of the residual add [S, dim]                          policy_dropout
+ *   5 DINOv2 tokens in front of image_embedding_projection, tokens + sigma z [P, enc_dim]  image_embedding_noise
+ *   6 context embedding behind the scale_context division [ctx_dim]                      context_dropout
+ *   7 the initial image's CLS row in front of initial_image_projection [enc_dim]         image_dropout
+ * The context encoder's and DINOv2's blocks draw nothing (context_encoder_kwargs.dropout_rate, attention-probability dropout and
+ * hypernet_kwargs.final_dropout_rate are not built); a forward_only hvla_train_step draws nothing; the serving entries draw nothing.
+ * A sample's noise depends on its GLOBAL index sample_offset + b (low 32 bits), never on its row or on what shares the batch.
+ * `draw` is the caller's: bump it before every hvla_train_step, or two steps draw the same masks.  A captured graph replays the
+ * `draw` (and seed and offset) it was captured with: the values are kernel arguments.
+ * A host-side setting kept BY VALUE on the context, like hvla_train_frozen: nothing is launched.  A site whose rate is 0 launches
+ * nothing; with every rate 0, or after opts == NULL (the state of a new context), hvla_train_step launches exactly what it
+ * launched and hvla_train_sizes returns what it returned.  While image_embedding_noise > 0 with a frozen encoder, or image_dropout
+ * > 0, the step keeps a noisy copy in the workspace and hvla_train_sizes reports the larger size: make the setting BEFORE asking
+ * for sizes.  The step then reads `tokens` / `cls` 16 bytes at a time: a pointer that is not 16-byte aligned is HVLA_E_SHAPE.
+ * While policy_dropout > 0 the gradient of the generated policy's key biases, zero under any mask, is left at exact zeros in
+ * `grads`, as under hvla_train_language_tokens.
+ * HVLA_E_SHAPE, with nothing stored and the previous setting in force: struct_size != sizeof(hvla_train_noise); a dropout rate
+ * outside [0, 1) or non-finite; a negative or non-finite image_embedding_noise.  NULL ctx: HVLA_E_STATE.                      */
+typedef struct hvla_train_noise {
+  uint32_t struct_size;
+  float policy_dropout;         /* vit_kwargs.dropout_rate                                             */
+  float image_embedding_noise;  /* vit_kwargs.image_embedding_noise (sigma)                            */
+  float context_dropout;        /* hypernet_kwargs.embedding_dropout_rate                              */
+  float image_dropout;          /* hypernet_kwargs.image_dropout                                       */
+  uint64_t seed;
+  int64_t sample_offset;        /* global index of row 0 (rank * B under data parallelism)             */
+  uint32_t draw;                /* the caller bumps it before every hvla_train_step                    */
+} hvla_train_noise;
+int hvla_train_noise_set(hvla_ctx* ctx, const hvla_train_noise* opts);   /* NULL: off, the state of a new context */
 
 /* Replaces: the `metrics` of MixActionHead.loss (hypervla/components/action_heads.py:517-521: `continuous_loss`, `gripper_loss`) per
  * sample, and the numerator of `validation_action_loss` (scripts/train.py:578-581).  Arguments as hvla_loss (actions / gripper_logits
@@ -634,6 +677,11 @@ int hvla_box_probe(hvla_ctx* ctx, float out[3], void* stream);
  * site 0 LayerNorm outputs, 1 stored q / k / v, 2 attention outputs, 3 GELU outputs.  maxabs f32 [4] = largest finite
  * |value| per site, nonfinite i32 [4] = number of inf / NaN values (an fp16 overflow shows up here).  HOST pointers.    */
 int hvla_encode_audit(hvla_ctx* ctx, const uint8_t* images, int32_t B, float* maxabs, int32_t* nonfinite, void* stream);
+/* Test instrumentation: what hvla_train_step draws under the current hvla_train_noise_set setting (seed, draw, rates) for the sample
+ * whose global index is sample_id, at `site` = kind | layer << 8: out (DEVICE f32 [n]) receives the multipliers of elements [0, n)
+ * of a dropout site (0 or 1 / keep_prob; all 1 / 1 when the site's rate is 0) or, for kind 5, the n normals z (not sigma z).
+ * HVLA_E_STATE without a setting; HVLA_E_SHAPE for a kind outside 1..7, n outside [1, 2^24] or a NULL out.                         */
+int hvla_train_noise_probe(hvla_ctx* ctx, uint32_t site, int64_t sample_id, int64_t n, float* out, void* stream);
 
 /* Primitive self-check used by tests: runs the MFMA fragment-layout probes on the ctx's device
  * and returns HVLA_OK only if every probe matches its exact integer expectation.                */

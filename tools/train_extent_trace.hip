@@ -62,5 +62,9 @@ int main() {
       }
   for (const Point& p : recorded_sweep())
     if (run(p, true)) return 1;
+  // hvla_train_noise with all four knobs on at MID, encoder frozen and trained (tests/test_train_noise_host.py): the residual
+  // branches go through t.y, the token and CLS copies sit behind the rest of the plan
+  for (int enc = 0; enc < 2; ++enc)
+    if (run(Point{"MID", mid(), 4, enc, 0, 0, 0, 0, 0.f, 0.f, 1}, true)) return 1;
   return 0;
 }

@@ -59,6 +59,11 @@ static void trace_arg(const AuxP& a) {
   TRACE_F(a, w_align); TRACE_F(a, ref); TRACE_F(a, loss); TRACE_F(a, ent); TRACE_F(a, align); TRACE_F(a, gscale);
   printf(" }");
 }
+static void trace_arg(const NoiseKey& k) {
+  printf("NoiseKey{");
+  TRACE_F(k, k0); TRACE_F(k, k1); TRACE_F(k, site); TRACE_F(k, draw); TRACE_F(k, sample0);
+  printf(" }");
+}
 #undef TRACE_F
 #define KL(kernel, grid, block, ...) (printf("%s ", #kernel), trace_list(dim3(grid), dim3(block), __VA_ARGS__), (void)printf("\n"))
 #define ENQ(fn, ...) (printf("%s ", #fn), trace_list(__VA_ARGS__), (void)printf("\n"))

@@ -7,7 +7,7 @@
 
 namespace hvla {
 void* train_trace_buffer(const char* name);
-void train_trace_plan(const Geom& g, int B, bool train_encoder);
+void train_trace_plan(const Geom& g, int B, bool train_encoder, const TrainNoise& nz);
 }
 using namespace hvla;
 
@@ -29,23 +29,30 @@ struct Point {
   int forward_only, frozen_buckets, frozen_mask;
   int aux;               // 0 off, 1 entropy only, 2 both
   float ema_decay, base_wd;
+  int noise = 0;         // 1: hvla_train_noise with all four knobs on (the title then ends in noise=1)
 };
 
 // plan: also print the size of every buffer a launch may point into and the workspace plan (train_trace_plan), and stop behind
 // train_step -- what tests/test_train_workspace_extents.py reads.  Without it: the lines of tests/native/train_step_trace.txt.
 static int run(const Point& p, bool plan = false) {
   const Geom& g = p.g;
-  printf("# %s L=%d ctx_layers=%d enc_layers=%d B=%d enc=%d forward_only=%d frozen_buckets=%d frozen=%d aux=%d ema=%g base_wd=%g\n", p.geom, g.L,
-         g.ctx_layers, g.enc_layers, p.B, p.enc, p.forward_only, p.frozen_buckets, p.frozen_mask, p.aux, (double)p.ema_decay, (double)p.base_wd);
+  printf("# %s L=%d ctx_layers=%d enc_layers=%d B=%d enc=%d forward_only=%d frozen_buckets=%d frozen=%d aux=%d ema=%g base_wd=%g%s\n", p.geom, g.L,
+         g.ctx_layers, g.enc_layers, p.B, p.enc, p.forward_only, p.frozen_buckets, p.frozen_mask, p.aux, (double)p.ema_decay, (double)p.base_wd,
+         p.noise ? " noise=1" : "");
   const bool enc = p.enc != 0;
-  printf("workspace %zu\n", train_workspace_floats(g, p.B, enc));
+  TrainOptions opt;
+  if (p.noise) {
+    opt.noise.policy_dropout = opt.noise.context_dropout = opt.noise.image_dropout = 0.25f;
+    opt.noise.sigma = 0.1f;
+    opt.noise.key.k0 = 7; opt.noise.key.draw = 3; opt.noise.key.sample0 = 8;
+  }
+  printf("workspace %zu\n", train_workspace_floats(g, p.B, enc, opt.noise));
   TrainBuffers tb{buf<float>("params"), buf<float>("grads"), buf<__bf16>("mu"), buf<float>("nu"), buf<float>("ema"), buf<float>("theta"),
                   buf<float>("dtheta"), buf<float>("work"), buf<float>("loss"), buf<float>("actions"), buf<float>("logits"), buf<float>("sqsum"),
                   buf<uint8_t>("wd_mask"), enc ? buf<float>("params0") : nullptr};
   TrainInputs in{buf<float>("tok"), buf<int64_t>("attn_mask"), buf<float>("cls"), enc ? nullptr : buf<float>("tokens"),
                  enc ? buf<uint8_t>("images") : nullptr, buf<float>("target"), buf<uint8_t>("tmask"), buf<uint8_t>("amask")};
   TrainHyper hp{1e-3f, 0.9f, 0.999f, 1e-8f, 0.01f, 1.f, p.ema_decay, 3, p.forward_only, 1e-4f, p.base_wd};
-  TrainOptions opt;
   if (p.enc == 2) { opt.ps.n = 16; opt.ps.w = buf<float>("pos_w"); opt.ps.grid = g.grid(); opt.ps.E = g.E; }
   AttnAux& aux = opt.aux;
   if (p.aux >= 1) { aux.w_ent = 0.25f; aux.ent = buf<float>("aux_ent"); }
@@ -62,7 +69,7 @@ static int run(const Point& p, bool plan = false) {
     const long n = train_vector_elems(L, opt.ps, enc);
     printf("size params %ld\nsize grads %ld\nsize theta %ld\nsize dtheta %ld\n", n, n, (long)p.B * L.G, (long)p.B * L.G);
     printf("size tok %ld\nsize cls %ld\nsize tokens %ld\n", (long)p.B * g.T * g.lang_dim, (long)p.B * g.E, enc ? 0L : (long)p.B * g.P() * g.E);
-    train_trace_plan(g, p.B, enc);
+    train_trace_plan(g, p.B, enc, opt.noise);
   }
   printf("step\n");
   (void)train_step(g, L, tb, in, p.B, hp, st, p.forward_only ? nullptr : ev, opt);
