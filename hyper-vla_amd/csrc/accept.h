@@ -15,6 +15,8 @@
 //              k-steps of the f32 MFMA), ctx_mlp % 16 == 0, 0 <= ctx_layers <= CTX_MAX_LAYERS, 2 <= lang_tokens <= 38,
 //              lang_dim % 4 == 0, and the working set fits the context encoder's LDS (ctx_encoder_lds_bytes <= 160 KiB)
 //   use_language_token   additionally lang_tokens <= 32 (one 32-key tile) and lang_dim % 64 == 0
+//   use_differential_transformer   not with use_language_token; the per-layer vectors are 48 floats longer and the policy kernel keeps
+//              a second table of action-row partials, both inside the same 160 KiB
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -53,7 +55,7 @@ struct PolicyLds {
   int nhr;          // heads resident in K / V^T at a time
   int np;           // rows of the action row's partial table per head: <= 8 waves (+ the language prefix) + the own key
   int spx;          // keys of the attention-map export: the patches (+ the prefix tile)
-  int act_floats;   // the action token's scratch: xa .. ga [384] | part [2][np][20] | pbuf [NW][32] | pexp [2][spx] | qkv1 [96] | hpriv [NW][64]
+  int act_floats;   // the action token's scratch: xa .. ga [384] | part [2][np][20] (differential: [2][2][np][20], one table per softmax) | pbuf [NW][32] | pexp [2][spx] | qkv1 [96] | hpriv [NW][64]
   int act_bytes;    // ... rounded up to 1 KiB; the scratch sits at offset 0
   int ring;         // [PRING][8 KiB] staged weight tiles
   int kh, kl;       // [nhr][P / 32][2][32][8] bf16 each
@@ -62,13 +64,13 @@ struct PolicyLds {
   int park;         // [NW][4 KiB] phase A's attention outputs
   int vlds;         // [layer_vec_floats] f32, to the end
 };
-constexpr PolicyLds policy_lds(int NW, bool lang) {
+constexpr PolicyLds policy_lds(int NW, bool lang, bool diff = false) {
   const int SP = NW * 32, VLD = SP + 8;
   PolicyLds d{};
   d.nhr = 2;
   d.np = lang ? 10 : 9;
   d.spx = SP + (lang ? 32 : 0);
-  d.act_floats = 384 + 2 * d.np * 20 + NW * 32 + 2 * d.spx + 96 + NW * 64;
+  d.act_floats = 384 + 2 * (diff ? 2 : 1) * d.np * 20 + NW * 32 + 2 * d.spx + 96 + NW * 64;
   d.act_bytes = (d.act_floats * 4 + 1023) & ~1023;
   d.ring = d.act_bytes;
   d.kh = d.ring + PRING * 8192;
@@ -80,31 +82,35 @@ constexpr PolicyLds policy_lds(int NW, bool lang) {
   return d;
 }
 // layer_vec_floats = PolicyLayout::Gv - v_layer0, the per-layer vectors + encoder_norm + head bias the kernel copies to LDS once.
-inline size_t policy_lds_bytes(int NW, bool lang, int layer_vec_floats) {
-  return (size_t)policy_lds(NW, lang).vlds + (size_t)layer_vec_floats * sizeof(float);
+inline size_t policy_lds_bytes(int NW, bool lang, int layer_vec_floats, bool diff = false) {
+  return (size_t)policy_lds(NW, lang, diff).vlds + (size_t)layer_vec_floats * sizeof(float);
 }
 
-inline Geom geom_of(const hvla_config& c, int lang) {
-  return Geom{c.image_size, c.patch, c.enc_dim, c.enc_layers, c.enc_heads, c.enc_mlp,
+inline Geom geom_of(const hvla_config& c, int lang, int diff = 0) {
+  Geom g = Geom{c.image_size, c.patch, c.enc_dim, c.enc_layers, c.enc_heads, c.enc_mlp,
               c.dim, c.layers, c.heads, c.mlp, c.horizon, c.action_dim, c.tanh_scale, c.max_action,
               c.ctx_dim, c.ctx_layers, c.ctx_heads, c.ctx_mlp, c.lang_tokens, c.lang_dim, c.scale_context,
               c.clip_target != 0, lang};
+  g.differential = diff;
+  return g;
 }
 
 // the policy kernel's LDS for an ACCEPTED width set (dim 64, mlp % 32 == 0, small layer count: the offsets are ints)
-inline size_t policy_lds_bytes_of(const hvla_config& c, int lang) {
+inline size_t policy_lds_bytes_of(const hvla_config& c, int lang, int diff = 0) {
   PolicyLayout pl{};
   LangLayout ll;
-  policy_offsets(geom_of(c, lang), pl, ll);
+  policy_offsets(geom_of(c, lang, diff), pl, ll);
   const int grid = c.image_size / c.patch;
-  return policy_lds_bytes(grid * grid / 32, lang != 0, pl.Gv - pl.v_layer0);
+  return policy_lds_bytes(grid * grid / 32, lang != 0, pl.Gv - pl.v_layer0, diff != 0);
 }
 
 // HVLA_OK, or why hvla_create refuses the geometry.  Every divisor is checked before it divides and every product is formed in 64
 // bits: the verdict arrives for ANY field values.  (struct_size and the options' struct_size are the caller's.)
-inline int accept_geometry(const hvla_config& c, int lang) {
+// diff: use_differential_transformer (a longer per-layer vector block and a second partial table in the policy kernel's LDS); not with lang
+inline int accept_geometry(const hvla_config& c, int lang, int diff = 0) {
   if (c.enc_dtype != HVLA_ENC_F16 && c.enc_dtype != HVLA_ENC_BF16) return HVLA_E_DTYPE;
   if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
+  if ((diff != 0 && diff != 1) || (diff && lang)) return HVLA_E_SHAPE;
   if (c.max_batch < 1 || c.streams < 0 || c.streams > 2) return HVLA_E_SHAPE;
   // generated policy
   if (c.dim != 64 || c.heads != 4 || c.mlp < 32 || c.mlp % 32 != 0 || c.layers < 1) return HVLA_E_SHAPE;
@@ -127,7 +133,7 @@ inline int accept_geometry(const hvla_config& c, int lang) {
   // a geometry that does not fit is refused here, not at the first hvla_generate / hvla_step
   if (ctx_encoder_lds_bytes(c.lang_tokens, c.ctx_dim, c.ctx_mlp, c.enc_dim) > LDS_LIMIT) return HVLA_E_SHAPE;
   if ((int64_t)c.layers * (9 * 64 + (int64_t)c.mlp) * (int64_t)sizeof(float) > (int64_t)LDS_LIMIT) return HVLA_E_SHAPE;   // (keeps the offsets in int)
-  if (policy_lds_bytes_of(c, lang) > LDS_LIMIT) return HVLA_E_SHAPE;
+  if (policy_lds_bytes_of(c, lang, diff) > LDS_LIMIT) return HVLA_E_SHAPE;
   return HVLA_OK;
 }
 

@@ -155,15 +155,37 @@ int hvla_create_with_v2(const hvla_config* c, const hvla_policy_options_v2* opts
   if (!c || !out) return HVLA_E_SHAPE;
   *out = nullptr;
   create_refusal = nullptr;
-  if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
   if (opts && opts->struct_size != sizeof(hvla_policy_options_v2)) return HVLA_E_SHAPE;   // the same rule for the options
+  const hvla_policy_options_v3 v3{sizeof(hvla_policy_options_v3), opts ? opts->use_language_token : 0,
+                                  opts ? opts->attention_mask_as_bias : 0, 0};
+  return hvla_create_with_v3(c, opts ? &v3 : nullptr, device, out);
+}
+
+int hvla_create_with_v3(const hvla_config* c, const hvla_policy_options_v3* opts, int device, hvla_ctx** out) {
+  if (!c || !out) return HVLA_E_SHAPE;
+  *out = nullptr;
+  create_refusal = nullptr;
+  if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
+  if (opts && opts->struct_size != sizeof(hvla_policy_options_v3)) return HVLA_E_SHAPE;   // the same rule for the options
   const int lang = opts ? opts->use_language_token : 0;
   if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
   const int mab = opts ? opts->attention_mask_as_bias : 0;
   if (mab != 0 && mab != 1) return HVLA_E_SHAPE;
+  const int diff = opts ? opts->differential_attention : 0;
+  if (diff != 0 && diff != 1) return HVLA_E_SHAPE;
   if (mab && lang) {
     create_refusal = "attention_mask_as_bias with use_language_token is not built: with the mask added as a bias language queries "
                      "attend to patch keys, so the language prefix is no per-episode constant";
+    return HVLA_E_SHAPE;
+  }
+  if (diff && lang) {
+    create_refusal = "differential_attention with use_language_token is not built: DifferentialAttention adds the mask as a bias, so "
+                     "language queries attend to patch keys and the language prefix is no per-episode constant";
+    return HVLA_E_SHAPE;
+  }
+  if (diff && mab) {
+    create_refusal = "differential_attention with attention_mask_as_bias: with both vit_kwargs set the reference runs "
+                     "DifferentialAttention (transformer.py:166-172), which is differential_attention alone";
     return HVLA_E_SHAPE;
   }
   int ndev = 0;
@@ -177,8 +199,8 @@ int hvla_create_with_v2(const hvla_config* c, const hvla_policy_options_v2* opts
   Geom& g = ctx->g;
   // what the hand-written kernels are specialised for (anything else is refused, never emulated): the predicate of accept.h,
   // which also refuses a context encoder or a policy that does not fit its kernel's LDS here, not at the first hvla_generate / hvla_step
-  if (const int verdict = accept_geometry(*c, lang)) return verdict;
-  g = geom_of(*c, lang);
+  if (const int verdict = accept_geometry(*c, lang, diff)) return verdict;
+  g = geom_of(*c, lang, diff);
   g.mask_as_bias = mab;
   const int P = g.P();
   if (hipSetDevice(device) != hipSuccess) return HVLA_E_DEVICE;
@@ -518,10 +540,11 @@ static int policy_range(hvla_ctx* ctx, const hvla_weights* w, const float* token
                  nb, g.E, g.P(), g.L, g.M, g.horizon, g.action_dim, g.tanh_scale, g.max_action};
   const LangLayout& ll = ctx->lay.ll;
   const int lang_T = ll.on ? g.T : 0;                           // use_language_token: the head map has lang_T + P keys
+  if (ctx->amap_head && g.differential) FAIL(ctx, HVLA_E_SHAPE, "no attention-map export with differential_attention");   // (hvla_set_attention_outputs refuses it)
   if (ctx->amap_head) p.amap = ctx->amap_head + (size_t)b0 * g.L * g.H * (g.P() + lang_T);
   ctx->prof.begin(HVLA_PROF_POLICY, st);
   ++ctx->prof.nlaunch;
-  HIPCHK(ctx, launch_policy(p, st, lang_T, slots ? slots + b0 : nullptr, w->B, g.mask_as_bias != 0));
+  HIPCHK(ctx, launch_policy(p, st, lang_T, slots ? slots + b0 : nullptr, w->B, g.mask_as_bias != 0, g.differential != 0));
   ctx->prof.end(HVLA_PROF_POLICY, st);
   return HVLA_OK;
 }
@@ -535,6 +558,9 @@ int hvla_policy(hvla_ctx* ctx, const hvla_weights* w, const float* tokens, float
 
 int hvla_set_attention_outputs(hvla_ctx* ctx, float* dino_cls_attention, float* head_attention) {
   if (!ctx) return HVLA_E_STATE;
+  if (head_attention && ctx->g.differential)
+    FAIL(ctx, HVLA_E_SHAPE, "head_attention with differential_attention: DifferentialAttention sows no attention weights "
+         "(transformer.py:166-171), there is no map of the action token to export");
   ctx->amap_dino = dino_cls_attention;
   ctx->amap_head = head_attention;
   return HVLA_OK;
@@ -1329,7 +1355,7 @@ int hvla_debug_policy_stamps(hvla_ctx* ctx, const hvla_weights* w, const float* 
   PolicyParams p{pl, w->wh.as<__bf16>(), w->wl.as<__bf16>(), w->vf.as<float>(), tokens, actions, logits,
                  B, g.E, g.P(), g.L, g.M, g.horizon, g.action_dim, g.tanh_scale, g.max_action};
   p.stamps = st.as<unsigned long long>();
-  for (int i = 0; i < 3; ++i) HIPCHK(ctx, launch_policy(p, nullptr));
+  for (int i = 0; i < 3; ++i) HIPCHK(ctx, launch_policy(p, nullptr, 0, nullptr, 0, false, g.differential != 0));   // (a differential context's layout is its flavour's alone)
   HIPCHK(ctx, hipDeviceSynchronize());
   HIPCHK(ctx, hipMemcpy(out, st.p, (size_t)n * 8, hipMemcpyDeviceToHost));
   return HVLA_OK;

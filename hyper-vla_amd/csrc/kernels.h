@@ -154,7 +154,9 @@ struct PolicyParams {
 // mask_as_bias: return_attention_map (policy_kernel_bias): the mask is added to the scores, patch queries attend to
 // the action token's key one logit below the others; not together with lang_T > 0
 hipError_t launch_policy(const PolicyParams& p, hipStream_t st, int lang_T = 0, const int32_t* slots = nullptr, int rows = 0,
-                         bool mask_as_bias = false);
+                         bool mask_as_bias = false, bool differential = false);
+// differential: use_differential_transformer (policy_kernel_diff); p.pl is then the layout of a Geom with the flag
+// (a longer per-layer vector block); not together with lang_T > 0 or mask_as_bias, and p.amap must be null
 // use_language_token: the language tokens of K episodes through the policy once (lang_prefix_kernel): K / V of every layer into
 // the episodes' arena rows (LangLayout::m_lkv)
 struct LangPrefixParams {

@@ -38,7 +38,12 @@ struct Geom {
   int lang_in_policy = 0;    // vit_kwargs.use_language_token (base_vit.py:159-166,207-212): [T language | P patches | 1 action]
   int mask_as_bias = 0;      // vit_kwargs.return_attention_map (transformer.py:172-181, multi_head_attetion.py:88-98): the blocks' attention is
                              // CustomMultiHeadDotProductAttention_0, which adds the 0 / 1 mask to the scores instead of masking
-  const char* attention_name() const { return mask_as_bias ? "CustomMultiHeadDotProductAttention_0_" : "MultiHeadDotProductAttention_0_"; }
+  int differential = 0;      // vit_kwargs.use_differential_transformer (transformer.py:166-171, differential_transformer.py:99-252): the blocks'
+                             // attention is DifferentialAttention_0 -- two softmaxes over the halves of each head's q / k, A1 - lambda A2,
+                             // an RMSNorm per head; no q / k / v / out bias.  Not with either flag above
+  const char* attention_name() const {
+    return differential ? "DifferentialAttention_0_" : (mask_as_bias ? "CustomMultiHeadDotProductAttention_0_" : "MultiHeadDotProductAttention_0_");
+  }
   int grid() const { return image_size / patch; }
   int P() const { return grid() * grid(); }
   int S() const { return P() + 1; }
@@ -83,6 +88,20 @@ inline std::vector<LeafInfo> generated_leaves(const Geom& g) {
       add(B + "MlpBlock_0_Dense_1_bias", {D});
       add(B + "MlpBlock_0_Dense_1_kernel", {M, D});
     };
+    if (g.differential) {                 // sorted keys: "DifferentialAttention_0" leads the block; hd / 2 = D / (2 H) per softmax
+      const std::string A = B + g.attention_name();
+      add(A + "k_proj_kernel", {D, D});
+      add(A + "lambda_k1", {hd / 2});
+      add(A + "lambda_k2", {hd / 2});
+      add(A + "lambda_q1", {hd / 2});
+      add(A + "lambda_q2", {hd / 2});
+      add(A + "out_proj_kernel", {D, D});
+      add(A + "q_proj_kernel", {D, D});
+      add(A + "subln_weight", {hd});
+      add(A + "v_proj_kernel", {D, D});
+      rest();
+      continue;
+    }
     if (!g.mask_as_bias) rest();          // sorted keys: "CustomMultiHead..." leads the block, "MultiHead..." ends it
     const std::string A = B + g.attention_name();
     add(A + "key_bias", {H, hd});
@@ -119,6 +138,13 @@ struct PolicyLayout {
   int v_ln0_s, v_ln0_b, v_qkv_b, v_out_b, v_ln1_s, v_ln1_b, v_fc1_b, v_fc2_b;  // inside a layer
   int v_norm_s, v_norm_b, v_head_b;
 };
+
+// use_differential_transformer: the floats a layer's vector block grows by, behind v_fc2_b's D floats (offsets inside a layer, natural
+// order): lambda_q1 | lambda_k1 | lambda_q2 | lambda_k2 (hd / 2 each), then subln's weight (hd).  Kept out of PolicyLayout, which the
+// policy kernels take by value: with the flag off every kernel argument is the one of the model without it.
+inline int diff_layer_floats(const Geom& g) { return g.differential ? 4 * (g.hd() / 2) + g.hd() : 0; }
+inline int diff_v_lambda(const PolicyLayout& p, int D) { return p.v_fc2_b + D; }
+inline int diff_v_subln(const PolicyLayout& p, int D, int hd) { return p.v_fc2_b + D + 4 * (hd / 2); }
 
 inline int crow_h(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
@@ -186,7 +212,7 @@ inline void policy_offsets(const Geom& g, PolicyLayout& p, LangLayout& ll) {
   }
   p.v_ln0_s = 0;  p.v_ln0_b = D;  p.v_qkv_b = 2 * D;  p.v_out_b = 5 * D;
   p.v_ln1_s = 6 * D;  p.v_ln1_b = 7 * D;  p.v_fc1_b = 8 * D;  p.v_fc2_b = 8 * D + M;
-  p.v_layer_stride = 9 * D + M;
+  p.v_layer_stride = 9 * D + M + diff_layer_floats(g);
   p.v_layer0 = v;  v += g.L * p.v_layer_stride;
   p.v_norm_s = v;  v += D;
   p.v_norm_b = v;  v += D;
@@ -262,7 +288,10 @@ inline PackedLayout build_layout(const Geom& g) {
     const int mb = p.m_layer0 + l * p.m_layer_stride, vb = p.v_layer0 + l * p.v_layer_stride;
     // fused QKV: rows n in [0,D) = query (head-major h*hd+d == flax [D,H,hd] flattened), [D,2D) key,
     // [2D,3D) value
-    const LeafInfo* W[3] = {&find(An + "query_kernel"), &find(An + "key_kernel"), &find(An + "value_kernel")};
+    // (differential: q_proj / k_proj / v_proj [D, D], the same index arithmetic; no bias leaves, their slots stay padding = zeros)
+    const bool df = g.differential != 0;
+    const LeafInfo* W[3] = {&find(An + (df ? "q_proj_kernel" : "query_kernel")), &find(An + (df ? "k_proj_kernel" : "key_kernel")),
+                            &find(An + (df ? "v_proj_kernel" : "value_kernel"))};
     const LeafInfo* Bq[3] = {&find(An + "query_bias"), &find(An + "key_bias"), &find(An + "value_bias")};
     int f = 0;
     for (int mt = 0; mt < 3 * D / 32; ++mt)
@@ -270,16 +299,22 @@ inline PackedLayout build_layout(const Geom& g) {
         put_frag(mb + p.m_qkv, f, mt, ks, kphi, 0, [&](int k, int n) {
           return (int32_t)(W[n / D]->offset + (int64_t)k * D + (n % D));
         });
-    cvec(vb + p.v_qkv_b, 3 * D / 32, [&](int n) { return (int32_t)(Bq[n / D]->offset + (n % D)); });
+    if (!df) cvec(vb + p.v_qkv_b, 3 * D / 32, [&](int n) { return (int32_t)(Bq[n / D]->offset + (n % D)); });
     // out projection: flax kernel [H, hd, D]; per head one k-step of hd = 16, K order kphi(ks=0)
-    const LeafInfo& Wo = find(An + "out_kernel");
+    const LeafInfo& Wo = find(An + (df ? "out_proj_kernel" : "out_kernel"));
     f = 0;
     for (int hh = 0; hh < H; ++hh)
       for (int mt = 0; mt < TD; ++mt, ++f)
         put_frag(mb + p.m_out, f, mt, 0, kphi, 0, [&](int k, int n) {
           return (int32_t)(Wo.offset + ((int64_t)hh * hd + k) * D + n);
         });
-    cvec(vb + p.v_out_b, TD, [&](int n) { return (int32_t)(find(An + "out_bias").offset + n); });
+    if (!df) cvec(vb + p.v_out_b, TD, [&](int n) { return (int32_t)(find(An + "out_bias").offset + n); });
+    if (df) {
+      const char* lam[4] = {"lambda_q1", "lambda_k1", "lambda_q2", "lambda_k2"};
+      for (int i = 0; i < 4; ++i)
+        for (int d = 0; d < hd / 2; ++d) pv[vb + diff_v_lambda(p, D) + i * (hd / 2) + d] = (int32_t)(find(An + lam[i]).offset + d);
+      for (int d = 0; d < hd; ++d) pv[vb + diff_v_subln(p, D, hd) + d] = (int32_t)(find(An + "subln_weight").offset + d);
+    }
     cvec(vb + p.v_ln0_s, TD, [&](int n) { return (int32_t)(find(Bn + "LayerNorm_0_scale").offset + n); });
     cvec(vb + p.v_ln0_b, TD, [&](int n) { return (int32_t)(find(Bn + "LayerNorm_0_bias").offset + n); });
     cvec(vb + p.v_ln1_s, TD, [&](int n) { return (int32_t)(find(Bn + "LayerNorm_1_scale").offset + n); });

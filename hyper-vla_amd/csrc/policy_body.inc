@@ -1,4 +1,4 @@
-// policy_body.inc -- the body of the six policy kernels (policy.hip), included once by each: by policy_kernel itself (HVLA_POLICY_SLOTS
+// policy_body.inc -- the body of the eight policy kernels (policy.hip), included once by each: by policy_kernel itself (HVLA_POLICY_SLOTS
 // 0) and by policy_kernel_slots (HVLA_POLICY_SLOTS 1), the episode-pool form, where the workgroup of call row b reads its weights from arena
 // row slots[b] (one wave-uniform load at entry; a row outside [0, p.B), the arena's rows, is skipped) and writes tokens / actions / logits /
 // attention at call row b as always.  With HVLA_POLICY_SLOTS 0 the preprocessor hands the compiler the kernel's text as it was
@@ -12,7 +12,19 @@
 // own k / v of the layer and head (ka / va: f32 in LDS, visible behind the barrier pair in front of the attention), one logit --
 // log2 e in the kernel's log2 domain -- below the patch keys.  It is one VALU key per patch lane in both softmax passes; the action
 // row (every key + 1: a constant the softmax row ignores) and the last layer (no patch rows) are untouched.  Undefined = 0.
+// HVLA_POLICY_DIFF 1, with HVLA_POLICY_BIAS 1 (policy_kernel_diff / policy_kernel_slots_diff, DESIGN.md §22): use_differential_transformer.
+// A head's 16 q / k features are two 8-feature parts; each part has its own softmax over all keys (the mask added as under BIAS, no
+// 1 / sqrt(d)), the head's output is (A1 - lambda A2) V, RMS-normalised over its 16 values and scaled by subln's weight and
+// 1 - lambda_init(l).  The K image holds part 0 on elements j < 4 and part 1 on j >= 4 of both lane halves (kphi), so a query fragment
+// with the other part's elements zeroed gives the part's scores from the same MFMAs against the same K fragment: the two-pass softmax
+// runs once per part (a rolled loop: the second copy of the unrolled key loops does not fit the register budget), the action row's
+// partials and their combine likewise.  No q / k / v / out bias: their slots in the arena are padding, i.e. zeros.  Undefined = 0.
   extern __shared__ __attribute__((aligned(16))) char smem[];
+#if HVLA_POLICY_DIFF
+  constexpr int NDP = 2;                                               // softmaxes per head: rows of the partial table per head and wave
+#else
+  constexpr int NDP = 1;
+#endif
 #if HVLA_POLICY_LANG
   constexpr int SP = NW * 32, VLD = SP + 8, NHR = 2, NP = 10;          // NP: <= 8 waves + the language prefix + the own key
   constexpr int NPART = NW + 1, SPX = SP + 32;                         // partials before the own key; keys of the attention-map export
@@ -26,7 +38,7 @@
 #endif
   // the action token's scratch sits at the START of the dynamic LDS (compile-time addresses: every access is an immediate
   // offset from a lane term, instead of a loop-invariant address register per buffer that the allocator then spills)
-  constexpr int ACT_FLOATS = 384 + 2 * NP * 20 + NW * 32 + 2 * SPX + 96 + NW * 64, ACT_BYTES = (ACT_FLOATS * 4 + 1023) & ~1023;
+  constexpr int ACT_FLOATS = 384 + 2 * NDP * NP * 20 + NW * 32 + 2 * SPX + 96 + NW * 64, ACT_BYTES = (ACT_FLOATS * 4 + 1023) & ~1023;
 #if HVLA_POLICY_LANG
   constexpr bool SPREAD = false;               // (the language variant runs the action row's jobs one wave per tile: with act_rows64
                                                // it does not fit policy_kernel's register budget, DESIGN.md §11)
@@ -73,7 +85,7 @@
   // accept.h's policy_lds() is what hvla_create and launch_policy_nw size this LDS by: the chain of pointers above is held to it.
   // (Taking every pointer as smem + its offset from that table instead changes the instruction streams of all twelve kernels:
   // profiles/policy_weightgen_template_isa.txt.)
-  constexpr PolicyLds T = policy_lds(NW, lds_lang);
+  constexpr PolicyLds T = policy_lds(NW, lds_lang, NDP == 2);
   static_assert(T.nhr == NHR && T.np == NP && T.spx == SPX && T.act_floats == ACT_FLOATS && T.ring == ACT_BYTES, "accept.h: action scratch");
   static_assert(T.kh == T.ring + PRING * 8192 && T.kl == T.kh + NHR * SP * 16 * 2 && T.vt == T.kl + NHR * SP * 16 * 2 &&
                 T.pre == T.vt + NHR * 32 * VLD * 2 && T.park == T.pre + (lds_lang ? LANG_PAIR_BYTES : 0) && T.vlds == T.park + NW * 4096,
@@ -89,8 +101,8 @@
   float* qa = xa + 192, *ka = xa + 224, *va = xa + 256;                // [32] q (scaled), k, v of the resident head pair
   float* oa = xa + 288;                                                // [64] attention output, all four heads
   float* ga = xa + 352;                                                // [32] GELU(fc1) of the current hidden tile
-  float* part = xa + 384;                                              // [2][NP][20]: per head and wave (max, sum, P.V[16])
-  float* pbuf = part + 2 * NP * 20;                                    // [NW][32] wave-private: p in V^T column order
+  float* part = xa + 384;                                              // [2][NDP][NP][20]: per head (, part) and wave (max, sum, P.V[16])
+  float* pbuf = part + 2 * NDP * NP * 20;                                   // [NW][32] wave-private: p in V^T column order
   float* pexp = pbuf + NW * 32;                                        // [2][SPX] p per key (attention-map export only; LANG: the prefix at SP)
   float* qkv1 = pexp + 2 * SPX;                                        // [96] q / k / v of head pair 1 (SPREAD: pair 0's are still being combined
                                                                        //      by one wave while every wave writes pair 1's)
@@ -250,7 +262,11 @@
   }
 
   HVLA_STAMP();                                 // 1: projection done
+#if HVLA_POLICY_DIFF
+  const float qscale = 1.4426950408889634f;                   // exp -> exp2 alone: differential_transformer.py:215-216 does not scale the scores
+#else
   const float qscale = rsqrtf(16.f) * 1.4426950408889634f;    // 1/sqrt(hd), and exp -> exp2
+#endif
   const int slot_k = wave * 32 + col;                          // this lane's key slot in LDS
   const int vpos = (wave * 32) | vperm32(col);
 
@@ -259,7 +275,8 @@
     const bool full = !last;                  // do the patch waves need their own rows?  (base_vit.py:226: only the action row is read)
     const float* vl = vtail + L.v_layer0 + l * L.v_layer_stride;    // LDS
     // the action row's attention over this wave's 32 keys for resident head hl: (max, sum, P.V) -> part[hl][wave]
-    auto act_attend = [&](int hl, const float* qbase) {
+    // (HVLA_POLICY_DIFF: for part c of the head, the features 8 c .. 8 c + 7 of q and k -> part[hl][c][wave])
+    auto act_attend = [&](int hl, const float* qbase, int c = 0) {
       const int lane = opaque((int)(threadIdx.x & 63)), col = lane & 31, half = lane >> 5;
       const int slot_k = wave * 32 + col;
       const float* qv = qbase + hl * 16 + 4 * half;
@@ -267,10 +284,21 @@
       const bf16x8 khi = *reinterpret_cast<const bf16x8*>(Kh + kpos(hl * SP + slot_k, half));
       const bf16x8 klo = *reinterpret_cast<const bf16x8*>(Kl + kpos(hl * SP + slot_k, half));
       float s = 0.f;
+#if HVLA_POLICY_DIFF
+      if (c == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s = fmaf((float)khi[j] + (float)klo[j], q0[j], s);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s = fmaf((float)khi[4 + j] + (float)klo[4 + j], q1[j], s);
+      }
+#else
+      (void)c;
 #pragma unroll
       for (int j = 0; j < 4; ++j) s = fmaf((float)khi[j] + (float)klo[j], q0[j], s);
 #pragma unroll
       for (int j = 0; j < 4; ++j) s = fmaf((float)khi[4 + j] + (float)klo[4 + j], q1[j], s);
+#endif
       s += __shfl_xor(s, 32, 64);               // both halves: the score of key `col` (log2 domain)
       const float m = wmax64(s);
       const float pj = __builtin_amdgcn_exp2f(s - m);
@@ -292,7 +320,11 @@
       }
       a += __shfl_xor(a, 32, 64);
       const float od = fmaf(__shfl_xor(a, 16, 64), 1.f / 1024.f, a);     // lanes < 16: hi row d + lo row d
+#if HVLA_POLICY_DIFF
+      float* pp = part + ((hl * NDP + c) * NP + wave) * 20;
+#else
       float* pp = part + (hl * NP + wave) * 20;
+#endif
       if (lane == 0) pp[0] = m, pp[1] = ls;
       if (lane < 16) pp[2 + lane] = od;
     };
@@ -340,6 +372,39 @@
     // combine the partials of head pair `pair` (all waves' keys + the action token's own key, base_vit.py:209-214: the
     // action row sees every token) -> oa[(2 pair + hl) * 16 + d]; run by ONE wave, after the barrier that follows the
     // attention of that pair and before anything overwrites qa / ka / va
+#if HVLA_POLICY_DIFF
+    // ... per part (the action row's mask row is + 1 on every key, its own included: no offset), then (A1 - lambda A2) V, the RMSNorm
+    // over the head's 16 values, subln's weight and 1 - lambda_init (differential_transformer.py:223-247)
+    auto act_combine = [&](int pair) {
+      const int lane = opaque((int)(threadIdx.x & 63));
+      const float* qa = (SPREAD && pair) ? qkv1 : xa + 192;
+      const float *ka = qa + 32, *va = qa + 64;
+      float linit;
+      const float lam = diff_lambda(vl + L.v_fc2_b + 64, l, lane, linit);
+      const float wn = vl[L.v_fc2_b + 96 + (lane & 15)] * (1.f - linit);
+#pragma unroll
+      for (int hl = 0; hl < NHR; ++hl) {
+        float od = 0.f;
+#pragma unroll 1
+        for (int c = 0; c < NDP; ++c) {       // (rolled: two copies of the combine do not fit the q tile's register budget)
+          const float self = wsum64((lane < 16 && (lane >> 3) == c) ? qa[hl * 16 + lane] * ka[hl * 16 + lane] : 0.f);
+          const float* pt = part + (hl * NDP + c) * NP * 20;
+          const float mt = lane < NPART ? pt[lane * 20] : (lane == NPART ? self : -1e30f);
+          const float lt = lane < NPART ? pt[lane * 20 + 1] : (lane == NPART ? 1.f : 0.f);
+          const float M = wmax64(mt);
+          const float f = __builtin_amdgcn_exp2f(mt - M);
+          const float inv = 1.f / wsum64(f * lt);
+          float o = 0.f;
+#pragma unroll
+          for (int t = 0; t < NPART; ++t) o = fmaf(__shfl(f, t, 64), pt[t * 20 + 2 + (lane & 15)], o);
+          o = fmaf(__shfl(f, NPART, 64), va[hl * 16 + (lane & 15)], o) * inv;
+          od = c ? fmaf(-lam, o, od) : o;
+        }
+        const float r = rsqrtf(wsum64(lane < 16 ? od * od : 0.f) * (1.f / 16.f) + 1e-5f);
+        if (lane < 16) oa[(2 * pair + hl) * 16 + lane] = od * r * wn;
+      }
+    };
+#else
     auto act_combine = [&](int pair) {
       const int lane = opaque((int)(threadIdx.x & 63));
       const float* qa = (SPREAD && pair) ? qkv1 : xa + 192;            // [q 32 | k 32 | v 32] of this head pair
@@ -377,6 +442,7 @@
         }
       }
     };
+#endif
     Split8 of[2];                             // attention outputs of the resident head pair as out-projection B fragments
 #pragma unroll
     for (int ph = 0; ph < 2; ++ph) {          // heads 2 ph, 2 ph + 1 resident
@@ -467,8 +533,16 @@
       asm volatile("" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       HVLA_STAMP();                             // 2 + 6 l + 2 ph: q / k / v of the head pair done
+#if HVLA_POLICY_DIFF
+#pragma unroll
+      for (int hl = 0; hl < NHR; ++hl) {
+        act_attend(hl, (SPREAD && ph) ? qkv1 : qa, 0);
+        act_attend(hl, (SPREAD && ph) ? qkv1 : qa, 1);
+      }
+#else
 #pragma unroll
       for (int hl = 0; hl < NHR; ++hl) act_attend(hl, (SPREAD && ph) ? qkv1 : qa);
+#endif
 #if HVLA_POLICY_LANG
       if (wave == NW - 1) {                   // the action row over the language prefix: one more partial
 #pragma unroll
@@ -479,6 +553,20 @@
 #pragma unroll
         for (int hl = 0; hl < NHR; ++hl) {
           __builtin_amdgcn_sched_barrier(0);
+#if HVLA_POLICY_DIFF
+          // part c of the head: the query with the other part's elements zeroed, its own softmax; ovd = A1 V - lambda A2 V
+          float linit;
+          const float lam = diff_lambda(vl + L.v_fc2_b + 64, l, opaque((int)(threadIdx.x & 63)), linit);
+          float ovd[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ovd[j] = 0.f;
+#pragma unroll 1
+          for (int c = 0; c < NDP; ++c) {
+          const Split8 qsel = diff_part(qf[hl], c);
+#else
+          {
+          const Split8& qsel = qf[hl];
+#endif
           auto scores = [&](int kt, float init) {      // S^T tile: keys on the accumulator rows, this lane's query on the lane
             Split8 kf;
             kf.hi = *reinterpret_cast<const bf16x8*>(Kh + kpos(hl * SP + kt * 32 + col, half));
@@ -486,7 +574,7 @@
             f32x16 sc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) sc[r] = init;
-            return mma32_x3p<TIE>(kf, qf[hl], sc);
+            return mma32_x3p<TIE>(kf, qsel, sc);
           };
 #if HVLA_POLICY_LANG
           auto lscores = [&](float init) {             // the language prefix tile, keys >= lang_T masked
@@ -538,9 +626,9 @@
             const f32x4 k0 = *reinterpret_cast<const f32x4*>(kv), k1 = *reinterpret_cast<const f32x4*>(kv + 8);
             float s = 0.f;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s = fmaf((float)qf[hl].hi[j] + (float)qf[hl].lo[j], k0[j], s);
+            for (int j = 0; j < 4; ++j) s = fmaf((float)qsel.hi[j] + (float)qsel.lo[j], k0[j], s);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s = fmaf((float)qf[hl].hi[4 + j] + (float)qf[hl].lo[4 + j], k1[j], s);
+            for (int j = 0; j < 4; ++j) s = fmaf((float)qsel.hi[4 + j] + (float)qsel.lo[4 + j], k1[j], s);
             sa = s + __shfl_xor(s, 32, 64) - 1.4426950408889634f;
           }
           m2 = fmaxf(m2, sa);
@@ -619,7 +707,31 @@
 #pragma unroll
           for (int j = 0; j < 8; ++j) ov[j] = fmaf(O[8 + j], 1.f / 1024.f, O[j]) * inv;     // V_hi.P + V_lo.P (lo stored x 2^10)
 #endif
+#if HVLA_POLICY_DIFF
+          const float coef = c ? -lam : 1.f;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) ovd[j] = fmaf(coef, ov[j], ovd[j]);
+          }
+          {   // RMSNorm over the head's 16 values (8 here, 8 in lane ^ 32), subln's weight (natural order) and 1 - lambda_init
+            float ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ss = fmaf(ovd[j], ovd[j], ss);
+            ss += __shfl_xor(ss, 32, 64);
+            const float r = rsqrtf(ss * (1.f / 16.f) + 1e-5f) * (1.f - linit);
+            const int ln = opaque((int)(threadIdx.x & 63));
+            const float* wv = vl + L.v_fc2_b + 96 + 4 * (ln >> 5);
+            const f32x4 w0 = *reinterpret_cast<const f32x4*>(wv), w1 = *reinterpret_cast<const f32x4*>(wv + 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              ovd[j] *= r * w0[j];
+              ovd[4 + j] *= r * w1[j];
+            }
+          }
+          of[hl] = split8(ovd);
+#else
           of[hl] = split8(ov);
+          }
+#endif
         }
         if (ph == 0) {                        // phase A's outputs wait in LDS (wave-private, lane-linear) for the out-projection
 #pragma unroll

@@ -32,6 +32,7 @@ struct TrainLayout {
 // nullptr, or why the training path (hvla_train_*) does not serve a geometry hvla_create accepted (HVLA_E_SHAPE with this text).
 // The first answer is the default: hvla_train_language_tokens(ctx, 1) lifts it for that context (train_entry, api.hip)
 inline const char* train_refusal(const Geom& g) {
+  if (g.differential) return "the training path does not build use_differential_transformer (DifferentialAttention): serving is";
   if (g.lang_in_policy) return "the training path does not build use_language_token";
   if (g.ctx_layers > CTX_MAX_LAYERS || g.L > TRAIN_MAX_POLICY_LAYERS || g.enc_layers > ENC_MAX_LAYERS) return "too many layers for the training path";
   return nullptr;

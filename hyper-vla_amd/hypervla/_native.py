@@ -25,7 +25,7 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_wait_bucket", "hvla_set_attention_outputs", "hvla_train_profile", "hvla_train_profile_read",
            "hvla_launches", "hvla_box_probe", "hvla_profile_select", "hvla_weights_alloc", "hvla_generate_slots",
            "hvla_step_slots", "hvla_ensemble_slots", "hvla_post_create", "hvla_post_free", "hvla_post_assign", "hvla_post_step",
-           "hvla_create_with", "hvla_create_with_v2", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
+           "hvla_create_with", "hvla_create_with_v2", "hvla_create_with_v3", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
            "hvla_loss_terms", "hvla_train_metrics", "hvla_train_noise_set", "hvla_train_noise_probe"]
@@ -63,6 +63,12 @@ class hvla_policy_options(C.Structure):
 class hvla_policy_options_v2(C.Structure):
     """hvla_policy_options with attention_mask_as_bias, for hvla_create_with_v2 (include/hvla.h): struct_size must be its sizeof."""
     _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32), ("attention_mask_as_bias", C.c_int32)]
+
+
+class hvla_policy_options_v3(C.Structure):
+    """hvla_policy_options_v2 with differential_attention, for hvla_create_with_v3 (include/hvla.h): struct_size must be its sizeof."""
+    _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32), ("attention_mask_as_bias", C.c_int32),
+                ("differential_attention", C.c_int32)]
 
 
 class hvla_tensor_desc(C.Structure):
@@ -134,6 +140,8 @@ def load_library():
     lib.hvla_create_with.restype = C.c_int
     lib.hvla_create_with_v2.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options_v2), C.c_int, C.POINTER(vp)]
     lib.hvla_create_with_v2.restype = C.c_int
+    lib.hvla_create_with_v3.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options_v3), C.c_int, C.POINTER(vp)]
+    lib.hvla_create_with_v3.restype = C.c_int
     lib.hvla_destroy.argtypes = [vp]
     lib.hvla_destroy.restype = None
     lib.hvla_last_error.argtypes = [vp]
@@ -274,7 +282,10 @@ class Context:
         self.geometry, self.device, self.max_batch, self.enc_dtype = g, device, max_batch, enc_dtype
         h = C.c_void_p()
         lang, mab = bool(getattr(g, "lang_in_policy", False)), bool(getattr(g, "mask_as_bias", False))
-        if mab:               # return_attention_map: the larger options struct has an entry of its own (both sizes are ABI)
+        if bool(getattr(g, "differential", False)):   # use_differential_transformer: the newest options struct and its entry
+            self.options = hvla_policy_options_v3(C.sizeof(hvla_policy_options_v3), int(lang), int(mab), 1)
+            rc = self.lib.hvla_create_with_v3(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
+        elif mab:             # return_attention_map: the larger options struct has an entry of its own (both sizes are ABI)
             self.options = hvla_policy_options_v2(C.sizeof(hvla_policy_options_v2), int(lang), 1)
             rc = self.lib.hvla_create_with_v2(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
         elif lang:            # use_language_token: the options struct (hvla_config's size is ABI)

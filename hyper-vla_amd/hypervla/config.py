@@ -55,14 +55,27 @@ class Geometry:
     # CustomMultiHeadDotProductAttention, which hands the boolean mask to dot_product_attention_weights as `bias=`
     # (multi_head_attetion.py:88-98): 1 is added to every allowed score and nothing is masked
     mask_as_bias: bool = False
+    # base_net_kwargs.vit_kwargs.use_differential_transformer (transformer.py:166-171): the block's attention is DifferentialAttention
+    # (differential_transformer.py:99-252): per head two softmaxes over the halves of q / k with the mask added to the unscaled scores,
+    # (A1 - lambda A2) V, an RMSNorm over the head's values; bias-free projections.  Served, not fine-tuned
+    differential: bool = False
 
     def __post_init__(self):
+        if self.differential and self.lang_in_policy:
+            raise ValueError("use_differential_transformer together with use_language_token is not built: DifferentialAttention adds "
+                             "the mask as a bias, so language queries attend to patch keys and the language prefix is no per-episode "
+                             "constant")
+        if self.differential and self.mask_as_bias:
+            raise ValueError("Geometry(differential=True, mask_as_bias=True): with use_differential_transformer the block never reaches "
+                             "the return_attention_map branch (transformer.py:166-172); the one form is differential=True alone")
         if self.mask_as_bias and self.lang_in_policy:
             raise ValueError("return_attention_map together with use_language_token is not built: with the mask added as a bias "
                              "language queries attend to patch keys, so the language prefix is no per-episode constant")
 
     @property
     def attention_name(self) -> str:   # flax auto-name of the policy blocks' attention module
+        if self.differential:
+            return "DifferentialAttention_0"
         return "CustomMultiHeadDotProductAttention_0" if self.mask_as_bias else "MultiHeadDotProductAttention_0"
 
     @property
@@ -174,6 +187,9 @@ def generated_leaves(g: Geometry) -> List[Leaf]:
     """The 73 HN-generated leaves in jax pytree order (dict keys sorted at every level); 75 with ``lang_in_policy``, which adds
     ``encoder/language_token_projection`` (base_vit.py:162-165) between the image projection and the position embedding.  With
     ``mask_as_bias`` the eight attention leaves of a block are named ``CustomMultiHeadDotProductAttention_0`` and lead the block.
+    With ``differential`` a block's attention has nine leaves under ``DifferentialAttention_0``, which leads the block too: four
+    bias-free [D, D] projections, the four lambda vectors [D / (2 H)] and ``subln/weight`` [D / H] (differential_transformer.py:139-156):
+    77 leaves, G = 200 668 at the README geometry.
 
     ``shared_modules=("image_encoder",)`` removes the DINOv2 leaves (hypervla/model.py:439-451);
     ``share_layer_index=True`` makes every leaf read context token 0 (model.py:400-402).
@@ -200,8 +216,14 @@ def generated_leaves(g: Geometry) -> List[Leaf]:
                 (A_ + ("out", "bias"), (D,)), (A_ + ("out", "kernel"), (H, hd, D)),
                 (A_ + ("query", "bias"), (H, hd)), (A_ + ("query", "kernel"), (D, H, hd)),
                 (A_ + ("value", "bias"), (H, hd)), (A_ + ("value", "kernel"), (D, H, hd))]
+        if g.differential:      # sorted keys again; "DifferentialAttention_0" comes before "LayerNorm_0"
+            attn = [(A_ + ("k_proj", "kernel"), (D, D)),
+                    (A_ + ("lambda_k1",), (hd // 2,)), (A_ + ("lambda_k2",), (hd // 2,)),
+                    (A_ + ("lambda_q1",), (hd // 2,)), (A_ + ("lambda_q2",), (hd // 2,)),
+                    (A_ + ("out_proj", "kernel"), (D, D)), (A_ + ("q_proj", "kernel"), (D, D)),
+                    (A_ + ("subln", "weight"), (hd,)), (A_ + ("v_proj", "kernel"), (D, D))]
         # sorted keys: "CustomMultiHead..." comes before "LayerNorm_0", "MultiHead..." after "MlpBlock_0"
-        items += attn + rest if g.mask_as_bias else rest + attn
+        items += attn + rest if (g.mask_as_bias or g.differential) else rest + attn
     items += [(("encoder", "image_embedding_projection", "bias"), (D,)),
               (("encoder", "image_embedding_projection", "kernel"), (E, D))]
     if g.lang_in_policy:
@@ -221,6 +243,8 @@ def total_generated(g: Geometry) -> int:
 
 
 assert total_generated(FULL) == 201_500 and len(generated_leaves(FULL)) == 73
+# use_differential_transformer: per block - 4 biases (4 D) + 4 lambda vectors (4 D / (2 H)) + subln/weight (D / H) = - 208, + 1 leaf
+assert total_generated(Geometry(differential=True)) == 200_668 and len(generated_leaves(Geometry(differential=True))) == 77
 
 
 def pytree_from_theta(g: Geometry, theta, squeeze: bool = False) -> Dict:
@@ -319,7 +343,7 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
                             num_layers=g.layers, num_heads=g.heads, mlp_dim=g.mlp,
                             dropout_rate=0.0, use_language_token=bool(g.lang_in_policy),
                             fine_tune_pretrained_image_encoder=True, image_embedding_noise=0.0,
-                            use_differential_transformer=False, return_attention_map=bool(g.mask_as_bias),
+                            use_differential_transformer=bool(g.differential), return_attention_map=bool(g.mask_as_bias),
                             add_positional_embedding=True, include_class_token=False),
             action_head_kwargs=dict(token_per_horizon=False, squash_continuous_action=True,
                                     tanh_scaling_factor=g.tanh_scale, clip_target=g.clip_target,
@@ -332,7 +356,11 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
 
 
 def geometry_from_config(cfg: Dict) -> Geometry:
-    """Inverse of :func:`default_config` (rejects branches the path does not build)."""
+    """Inverse of :func:`default_config` (rejects branches the path does not build).
+
+    ``use_differential_transformer`` selects ``Geometry.differential``.  A config with both ``use_differential_transformer`` and
+    ``return_attention_map`` maps to ``differential=True, mask_as_bias=False``: Encoder1DBlock tests the first flag first
+    (transformer.py:166-172), so such a model runs DifferentialAttention and never builds CustomMultiHeadDotProductAttention."""
     b, h = cfg["base_net_kwargs"], cfg["hypernet_kwargs"]
     v, a = b["vit_kwargs"], b["action_head_kwargs"]
     ge = cfg.get("geometry", {})
@@ -349,13 +377,17 @@ def geometry_from_config(cfg: Dict) -> Geometry:
     if a.get("token_per_horizon") or a.get("hidden_dims"):
         raise ValueError("token_per_horizon / hidden_dims action heads are not built")
     lang_in_policy = bool(v.get("use_language_token", False))
-    mask_as_bias = bool(v.get("return_attention_map", False))
+    differential = bool(v.get("use_differential_transformer", False))
+    mask_as_bias = bool(v.get("return_attention_map", False)) and not differential
+    if differential and lang_in_policy:
+        raise ValueError("base_net_kwargs.vit_kwargs.use_differential_transformer together with use_language_token is not built: "
+                         "DifferentialAttention adds the mask as a bias (differential_transformer.py:219-221), so language queries "
+                         "attend to patch keys and the language prefix is no per-episode constant")
     if mask_as_bias and lang_in_policy:
         raise ValueError("base_net_kwargs.vit_kwargs.return_attention_map together with use_language_token is not built: "
                          "CustomMultiHeadDotProductAttention adds the mask as a bias (multi_head_attetion.py:88-98), so language "
                          "queries attend to patch keys and the language prefix is no per-episode constant")
-    for key, want in (("include_class_token", False), ("add_positional_embedding", True),
-                      ("use_differential_transformer", False)):
+    for key, want in (("include_class_token", False), ("add_positional_embedding", True)):
         if bool(v.get(key, want)) != want:
             raise ValueError(f"base_net_kwargs.vit_kwargs.{key}={v.get(key)!r} is outside the built path (only {want!r} is built)")
     if b.get("action_token_num", 1) != 1 or v.get("action_token_num", 1) != 1:
@@ -378,7 +410,8 @@ def geometry_from_config(cfg: Dict) -> Geometry:
         ctx_dim=h["context_embedding_dim"], ctx_layers=ce["num_layers"],
         ctx_heads=ce["num_attention_heads"], ctx_mlp=ce["mlp_dim"],
         lang_tokens=ge.get("lang_tokens", 32), lang_dim=ge.get("lang_dim", 768),
-        scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy, mask_as_bias=mask_as_bias)
+        scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy, mask_as_bias=mask_as_bias,
+        differential=differential)
 
 
 # --------------------------------------------------------------------------------------

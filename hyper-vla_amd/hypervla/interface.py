@@ -102,6 +102,10 @@ class InferenceWrapper:
                  crop: bool = False, save_attention_map: bool = False, padded_resize: bool = False):
         if policy_setup not in _DATASET:
             raise ValueError(f"Unknown policy setup: {policy_setup}")
+        if save_attention_map and getattr(getattr(model, "geometry", None), "differential", False):
+            raise ValueError("save_attention_map=True with vit_kwargs.use_differential_transformer: the reference's wrapper reads "
+                             "attention_weights from the intermediates (hypervla_interface.py:213-217), which DifferentialAttention "
+                             "does not sow")
         self.save_attention_map = save_attention_map          # hypervla_interface.py:74,208-217
         self.dino_attention_map = self.head_attention_map = None
         self.model, self.policy_setup = model, policy_setup

@@ -570,6 +570,10 @@ class HyperVLA:
         episodes (kept beside their weights); `instruction_dict` is not read here, as before.
         `slots` (episode pool): step only these K slots of `base_params` (`hvla_step_slots`): images [K, ...] in, every output
         [K, ...] out, row k that of slot slots[k]."""
+        if attention_maps and getattr(self.geometry, "differential", False):
+            raise ValueError("attention_maps=True with vit_kwargs.use_differential_transformer: the reference sows neither "
+                             "attention_weights nor attention_map in that branch (transformer.py:166-171), so there is no head map "
+                             "to return; reference_attention_map (DINOv2's) is available")
         torch = _torch()
         if train:
             # train=True switches on nn.Dropout(dropout_rate) (base_vit.py:205, transformer.py:67,74,192,244) and the

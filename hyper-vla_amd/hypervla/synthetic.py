@@ -36,6 +36,10 @@ def _leaf_natural(path: Tuple[str, ...], shape: Tuple[int, ...], g: Geometry):
         return 0.02, 0.0
     if last == "pos_embedding":
         return 0.02, 0.0
+    if last.startswith("lambda_"):               # DifferentialAttention: nn.initializers.normal(0.1) (differential_transformer.py:148-152)
+        return 0.1, 0.0
+    if last == "weight":                         # its RMSNorm weight: ones, made non-trivial like a LayerNorm scale
+        return 0.05, 1.0
     # kernels: xavier over (fan_in, fan_out) of the logical matmul
     if path[-2] == "out":                       # [H, hd, D]
         fi, fo = shape[0] * shape[1], shape[2]

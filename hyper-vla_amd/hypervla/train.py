@@ -464,6 +464,9 @@ class FineTuner:
                           context_dropout=float(embedding_dropout_rate), image_dropout=float(image_dropout))
         self.noise_on = any(v != 0.0 for v in self.noise.values())
         self.noise_seed, self.noise_draw = int(noise_seed), 0
+        if getattr(model.geometry, "differential", False):
+            raise ValueError("fine-tuning a model with vit_kwargs.use_differential_transformer is not built; serving is "
+                             "(DifferentialAttention has no backward pass in the training kernels, DESIGN.md §22)")
         if getattr(model.geometry, "lang_in_policy", False) and not self.language_tokens:
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")

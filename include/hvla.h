@@ -127,6 +127,33 @@ typedef struct hvla_policy_options_v2 {
  * use_language_token (the same ctx, byte for byte).  A refusal leaves *out NULL; where it has more to say than its code,
  * hvla_last_error(NULL) returns the text until this thread's next hvla_create / hvla_create_with / hvla_create_with_v2.  */
 int hvla_create_with_v2(const hvla_config* cfg, const hvla_policy_options_v2* opts, int device, hvla_ctx** out);
+
+/* hvla_policy_options_v2 with one more field, by the same rule (struct_size must be sizeof(hvla_policy_options_v3)).
+ *   differential_attention  base_net_kwargs.vit_kwargs.use_differential_transformer (hypervla/components/transformer.py:166-171):
+ *                       the policy blocks' attention is DifferentialAttention (differential_transformer.py:99-252).  Each of
+ *                       the `heads` heads splits its dim / heads q and k features into two halves; each half has its own
+ *                       softmax over all P + 1 keys, unscaled, with the mask of base_vit.py:209-214 ADDED to the scores (as under
+ *                       attention_mask_as_bias); the head's output is (A1 - lambda A2) V with lambda = exp(lambda_q1 . lambda_k1)
+ *                       - exp(lambda_q2 . lambda_k2) + lambda_init(layer), RMS-normalised over the head's dim / heads values
+ *                       (eps 1e-5), times subln's weight and 1 - lambda_init(layer).  The generated leaves of the attention are
+ *                       `..._DifferentialAttention_0_{k_proj_kernel, lambda_k1, lambda_k2, lambda_q1, lambda_q2, out_proj_kernel,
+ *                       q_proj_kernel, subln_weight, v_proj_kernel}` (no biases) and lead their block in the parameter order.
+ *                       SERVED only: every hvla_train_* entry that reads the geometry, hvla_train_publish
+ *                       included, returns HVLA_E_SHAPE with a text, and so does hvla_set_attention_outputs with a
+ *                       head_attention buffer (the reference sows no attention weights in this branch); dino_cls_attention
+ *                       alone is accepted.  Not built together with use_language_token or attention_mask_as_bias (with both
+ *                       vit_kwargs set the reference runs DifferentialAttention: pass differential_attention alone):
+ *                       HVLA_E_SHAPE, hvla_last_error(NULL) says why.                                                       */
+typedef struct hvla_policy_options_v3 {
+  uint32_t struct_size;                      /* = sizeof(hvla_policy_options_v3)                                        */
+  int32_t use_language_token;                /* 0 (default) or 1                                                        */
+  int32_t attention_mask_as_bias;            /* 0 (default) or 1                                                        */
+  int32_t differential_attention;            /* 0 (default) or 1                                                        */
+} hvla_policy_options_v3;
+
+/* hvla_create_with_v2 for hvla_policy_options_v3: opts == NULL, or differential_attention 0, is hvla_create_with_v2 of the other
+ * two fields (the same ctx, byte for byte).  Refusals as for hvla_create_with_v2.                                          */
+int hvla_create_with_v3(const hvla_config* cfg, const hvla_policy_options_v3* opts, int device, hvla_ctx** out);
 void hvla_destroy(hvla_ctx* ctx);
 const char* hvla_last_error(const hvla_ctx* ctx);
 
