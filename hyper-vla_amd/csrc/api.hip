@@ -63,6 +63,7 @@ struct TrainState {               // what the hvla_train_* entries keep per cont
   int64_t frozen_n = 0;           // the mask's length, one of the two of hvla_train_sizes when it was set ...
   bool frozen_enc = false;        //   ... namely the one of this train_encoder value
   bool language_tokens = false;   // hvla_train_language_tokens: the entries serve this use_language_token context
+  bool differential = false;      // hvla_train_differential: the entries serve this differential_attention context
   bool noise_set = false;         // hvla_train_noise_set holds a setting (sel.noise, by value; all rates 0 is a setting too)
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
@@ -825,7 +826,7 @@ static int frozen_fits(hvla_ctx* ctx, bool train_encoder) {
 static int train_entry(hvla_ctx* ctx, bool args = true, int frozen_for = -1) {
   if (!ctx || !args) return HVLA_E_STATE;
   TrainState& t = ctx->train;
-  if (const char* why = train_refusal(ctx->g, t.language_tokens)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
+  if (const char* why = train_refusal(ctx->g, t.language_tokens, t.differential)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!t.have_layout) { t.L = make_train_layout(ctx->g); t.have_layout = true; }
   if (!t.L.policy_ok) FAIL(ctx, HVLA_E_STATE, "the generated policy has no leaf of a name the training path reads");
@@ -901,6 +902,8 @@ int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts)
   if (!opts) { ctx->train.sel.aux = AttnAux(); return HVLA_OK; }
   if (int rc = train_entry(ctx)) return rc;
   if (ctx->g.lang_in_policy) FAIL(ctx, HVLA_E_SHAPE, "the attention terms are not defined with use_language_token: the action row has T + P keys, the reference map P");
+  if (ctx->g.differential && (opts->entropy_weight != 0.f || opts->alignment_weight != 0.f))
+    FAIL(ctx, HVLA_E_SHAPE, "the attention terms are not defined with differential_attention: the module's map is the signed A1 - lambda A2, which has no entropy");
   if (opts->struct_size != sizeof(hvla_train_attention)) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_attention.struct_size %u: this library's is %zu", opts->struct_size, sizeof(hvla_train_attention));
   const float we = opts->entropy_weight, wa = opts->alignment_weight;
   if (!std::isfinite(we) || !std::isfinite(wa) || we < 0.f || wa < 0.f) FAIL(ctx, HVLA_E_SHAPE, "attention loss weights (%g, %g) must be finite and >= 0", (double)we, (double)wa);
@@ -918,6 +921,15 @@ int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on) {
   return HVLA_OK;
 }
 
+int hvla_train_differential(hvla_ctx* ctx, int32_t on) {
+  if (!ctx) return HVLA_E_STATE;
+  if (on == 0) { ctx->train.differential = false; return HVLA_OK; }
+  if (on != 1) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_differential(%d): 0 or 1", on);
+  if (!ctx->g.differential) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_differential(1) on a context created without differential_attention");
+  ctx->train.differential = true;
+  return HVLA_OK;
+}
+
 int hvla_train_noise_set(hvla_ctx* ctx, const hvla_train_noise* opts) {
   if (!ctx) return HVLA_E_STATE;
   if (!opts) { ctx->train.sel.noise = TrainNoise(); ctx->train.noise_set = false; return HVLA_OK; }
@@ -929,6 +941,8 @@ int hvla_train_noise_set(hvla_ctx* ctx, const hvla_train_noise* opts) {
   const float sg = opts->image_embedding_noise;
   if (!std::isfinite(sg) || sg < 0.f) FAIL(ctx, HVLA_E_SHAPE, "image_embedding_noise %g must be finite and >= 0", (double)sg);
   const Geom& g = ctx->g;      // one Philox block is four consecutive elements of a row (accept.h admits no other widths)
+  if (g.differential && (rates[0] != 0.f || rates[1] != 0.f || rates[2] != 0.f || sg != 0.f))
+    FAIL(ctx, HVLA_E_SHAPE, "hvla_train_noise with differential_attention is not built: the noise is restated for the other attention modules only");
   if (g.D % 4 != 0 || g.M % 4 != 0 || g.E % 4 != 0 || g.C % 4 != 0) FAIL(ctx, HVLA_E_SHAPE, "a noise site's width is no multiple of 4");
   TrainNoise nz;
   nz.policy_dropout = rates[0]; nz.sigma = sg; nz.context_dropout = rates[1]; nz.image_dropout = rates[2];

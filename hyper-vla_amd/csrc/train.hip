@@ -352,6 +352,160 @@ __global__ void softmax_bwd_kernel(const float* __restrict__ p, float* __restric
   for (int k = lane; k < Cc; k += 64) dr[k] = pr[k] * (dr[k] - s);
 }
 
+// ---- DifferentialAttention of the policy (vit_kwargs.use_differential_transformer; differential_transformer.py:99-252) ----
+// Per head hh two softmaxed tables A1, A2 (sub-heads 2 hh and 2 hh + 1 of p [nb][2 H][S][ld], rows by softmax_bias_fwd_kernel),
+// A = A1 - lambda A2, O = A V, N = O rsqrt(mean_16(O^2) + 1e-5) w (1 - lambda_init).  The kernels below are specialised for what
+// accept.h admits: D = 64, H = 4, so a head has 16 values, a part 8, and a wave's lane is a row's feature.  Kernels of their own,
+// as above: no existing kernel changes its arguments.
+// lambda_1 = exp(sum lambda_q1 lambda_k1) and lambda_2 = exp(sum lambda_q2 lambda_k2) of the episode whose theta row is th, on
+// every lane: lanes 0-7 form the first sum's products, lanes 8-15 the second's, one 16-lane reduction serves both
+__device__ __forceinline__ void diff_lambdas(const float* __restrict__ th, long lq1, long lk1, long lq2, long lk2, int lane, float& l1, float& l2) {
+  float a = 0.f, b = 0.f;
+  if (lane < 8) a = th[lq1 + lane] * th[lk1 + lane];
+  else if (lane < 16) b = th[lq2 + lane - 8] * th[lk2 + lane - 8];
+  for (int o = 8; o; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+  l1 = expf(__shfl(a, 0, 64));
+  l2 = expf(__shfl(b, 0, 64));
+}
+// a[nb][H][S][ld] = A1 - lambda A2 with lambda = lambda_1 - lambda_2 + linit; zeros behind the row (a is the A operand of A V and A^T dO)
+__global__ void diff_combine_fwd_kernel(const float* __restrict__ p, float* __restrict__ a, const float* __restrict__ theta, long G,
+                                        long lq1, long lk1, long lq2, long lk2, float linit, int nb, int H, int S, int ld) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nb * H * S) return;
+  const int mat = row / S, q = row % S;
+  float l1, l2;
+  diff_lambdas(theta + (long)(mat / H) * G, lq1, lk1, lq2, lk2, lane, l1, l2);
+  const float lam = l1 - l2 + linit;
+  const float* p1 = p + ((long)(2 * mat) * S + q) * ld;
+  const float* p2 = p1 + (long)S * ld;
+  float* ar = a + (long)row * ld;
+  for (int k = lane; k < ld; k += 64) ar[k] = k < S ? p1[k] - lam * p2[k] : 0.f;
+}
+// subln (RMSNorm over a head's 16 values, one weight for all heads) and the factor post = 1 - lambda_init: n = o r w post
+__global__ void diff_subln_fwd_kernel(const float* __restrict__ o, float* __restrict__ n, const float* __restrict__ theta, long G,
+                                      long sw, float post, int rows, int S) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float v = o[(long)row * 64 + lane];
+  float s = v * v;
+  for (int x = 8; x; x >>= 1) s += __shfl_xor(s, x, 64);
+  const float r = rsqrtf(s * (1.f / 16.f) + 1e-5f);
+  n[(long)row * 64 + lane] = v * r * theta[(long)(row / S) * G + sw + (lane & 15)] * post;
+}
+// Its backward, one workgroup of four waves per episode: dn holds dN on entry and dO = r (g w - n mean_16(g w n)) on exit, g = post dN,
+// n = o r recomputed; dw[d] = sum_{q, hh} g n in a fixed order (a wave its rows in ascending order, the heads by two shuffles, the
+// waves in ascending order), so the episode's dtheta row does not depend on the batch around it
+__global__ __launch_bounds__(256) void diff_subln_bwd_kernel(const float* __restrict__ o, float* __restrict__ dn, const float* __restrict__ theta,
+                                                             float* __restrict__ dtheta, long G, long sw, float post, int S) {
+  __shared__ float red[4][64];
+  const int b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float w = theta[(long)b * G + sw + (lane & 15)];
+  float acc = 0.f;
+  for (int q = wave; q < S; q += 4) {
+    const long i = ((long)b * S + q) * 64 + lane;
+    const float v = o[i];
+    float s = v * v;
+    for (int x = 8; x; x >>= 1) s += __shfl_xor(s, x, 64);
+    const float r = rsqrtf(s * (1.f / 16.f) + 1e-5f), nn = v * r, g = post * dn[i], gw = g * w;
+    acc = fmaf(g, nn, acc);
+    float m = gw * nn;
+    for (int x = 8; x; x >>= 1) m += __shfl_xor(m, x, 64);
+    dn[i] = r * (gw - nn * (m * (1.f / 16.f)));
+  }
+  acc += __shfl_xor(acc, 16, 64);
+  acc += __shfl_xor(acc, 32, 64);
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (threadIdx.x < 16) dtheta[(long)b * G + sw + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+// Both softmax backwards of a head's row from ONE dp row (dA1 = dp, dA2 = - lambda dp): ds1 = A1 (dp - t1), ds2 = - lambda A2 (dp - t2),
+// t_c = sum_k dp A_c, into ds [nb][2 H][S][ld] next to the tables (zeros behind the rows: ds is the A operand of dq and dk); t2 [nb][H][S]
+// is kept for d lambda = - sum t2
+__global__ void diff_softmax_bwd_kernel(const float* __restrict__ p, const float* __restrict__ dp, float* __restrict__ ds, float* __restrict__ t2,
+                                        const float* __restrict__ theta, long G, long lq1, long lk1, long lq2, long lk2, float linit,
+                                        int nb, int H, int S, int ld) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nb * H * S) return;
+  const int mat = row / S, q = row % S;
+  float l1, l2;
+  diff_lambdas(theta + (long)(mat / H) * G, lq1, lk1, lq2, lk2, lane, l1, l2);
+  const float lam = l1 - l2 + linit;
+  const long o1 = ((long)(2 * mat) * S + q) * ld, o2 = o1 + (long)S * ld;
+  const float* p1 = p + o1;
+  const float* p2 = p + o2;
+  const float* d = dp + (long)row * ld;
+  float* s1 = ds + o1;
+  float* s2 = ds + o2;
+  if (lane < ld - S) s1[S + lane] = s2[S + lane] = 0.f;
+  float a = 0.f, b = 0.f;
+  for (int k = lane; k < S; k += 64) { a = fmaf(d[k], p1[k], a); b = fmaf(d[k], p2[k], b); }
+  for (int x = 32; x; x >>= 1) { a += __shfl_xor(a, x, 64); b += __shfl_xor(b, x, 64); }
+  for (int k = lane; k < S; k += 64) {
+    s1[k] = p1[k] * (d[k] - a);
+    s2[k] = -lam * p2[k] * (d[k] - b);
+  }
+  if (lane == 0) t2[row] = b;
+}
+// d lambda = - sum_{hh, q} t2 of the episode (a lane its entries in ascending order, the lanes by xor-shuffle: a fixed order), then
+// d lambda_q1 = d lambda lambda_1 lambda_k1, d lambda_k1 = d lambda lambda_1 lambda_q1, d lambda_q2 = - d lambda lambda_2 lambda_k2,
+// d lambda_k2 = - d lambda lambda_2 lambda_q2 into the episode's dtheta row.  One wave per episode.
+__global__ void diff_lambda_bwd_kernel(const float* __restrict__ t2, const float* __restrict__ theta, float* __restrict__ dtheta, long G,
+                                       long lq1, long lk1, long lq2, long lk2, int n) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* th = theta + (long)b * G;
+  float* dth = dtheta + (long)b * G;
+  float s = 0.f;
+  for (int i = lane; i < n; i += 64) s += t2[(long)b * n + i];
+  for (int x = 32; x; x >>= 1) s += __shfl_xor(s, x, 64);
+  float l1, l2;
+  diff_lambdas(th, lq1, lk1, lq2, lk2, lane, l1, l2);
+  const float d1 = -s * l1, d2 = s * l2;
+  if (lane < 8) {
+    dth[lq1 + lane] = d1 * th[lk1 + lane];
+    dth[lk1 + lane] = d1 * th[lq1 + lane];
+    dth[lq2 + lane] = d2 * th[lk2 + lane];
+    dth[lk2 + lane] = d2 * th[lq2 + lane];
+  }
+}
+
+// The per-episode reductions of a DifferentialAttention policy's backward without atomics, so that the WHOLE dtheta row of a sample is
+// the same bits in any batch and in every run (the forms above add row chunks with atomics in the order the chunks finish).  One
+// workgroup of four waves per (64 columns, episode): a wave its rows w, w + 4, .. in ascending order, the waves in ascending order.
+// out[b * ostride + n] += sum_{r < rows_used} x[b][r][n]; one writer per element
+__global__ __launch_bounds__(256) void colsum_episode_kernel(const float* __restrict__ x, float* __restrict__ out, long ostride, int R,
+                                                             int rows_used, int N) {
+  __shared__ float red[4][64];
+  const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (n < N)
+    for (int r = wave; r < rows_used; r += 4) s += x[((long)b * R + r) * N + n];
+  red[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && n < N) out[(long)b * ostride + n] += ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+// dscale[b][c] += sum_r dy xhat, dbias[b][c] += sum_r dy over the S rows of episode b (ln_bwd_kernel then runs without its atomics)
+__global__ __launch_bounds__(256) void ln_pgrad_episode_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
+                                                               const float* __restrict__ rstd, float* __restrict__ dscale,
+                                                               float* __restrict__ dbias, long pstride, int S, int D) {
+  __shared__ float red[2][4][64];
+  const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = blockIdx.x * 64 + lane;
+  float sa = 0.f, sb = 0.f;
+  if (c < D)
+    for (int r = wave; r < S; r += 4) {
+      const long row = (long)b * S + r;
+      const float d = dy[row * D + c];
+      sa = fmaf(d, (x[row * D + c] - mean[row]) * rstd[row], sa);
+      sb += d;
+    }
+  red[0][wave][lane] = sa;
+  red[1][wave][lane] = sb;
+  __syncthreads();
+  if (wave == 0 && c < D) {
+    dscale[(long)b * pstride + c] += ((red[0][0][lane] + red[0][1][lane]) + red[0][2][lane]) + red[0][3][lane];
+    dbias[(long)b * pstride + c] += ((red[1][0][lane] + red[1][1][lane]) + red[1][2][lane]) + red[1][3][lane];
+  }
+}
+
 __device__ __forceinline__ float dgelu_tanh(float x) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const float u = k0 * (x + k1 * x * x * x), t = tanhf(u);
@@ -834,7 +988,9 @@ static inline dim3 g1(long n, int bs = 256) { long b = (n + bs - 1) / bs; return
 // the per-episode policy, 0 for the shared context encoder).  Buffers for one layer:
 // h, h2, g (the two LayerNorm outputs and the GELU output): kept per block when the plan has room for them (the backward pass
 // then reads them instead of recomputing them: two LayerNorm passes and one GELU pass per block), else nullptr
-struct BlkBuf { float *x_in, *mean0, *rstd0, *q, *k, *v, *p, *o, *x_mid, *mean1, *rstd1, *u, *y1, *y2, *h, *h2, *g; };
+// pa, oraw (a DifferentialAttention block only, else nullptr): A = A1 - lambda A2 [nb][H][S][Sp] and O = A V [nb][S][D] in front of subln,
+// both kept for the backward; p is then [nb][2 H][S][Sp] and o holds subln's output, the out-projection's input
+struct BlkBuf { float *x_in, *mean0, *rstd0, *q, *k, *v, *p, *o, *x_mid, *mean1, *rstd1, *u, *y1, *y2, *h, *h2, *g, *pa, *oraw; };
 // one block's leaves as pointers (T = const float: weights, T = float: their gradients): BlockLeaves' members, bound to a base
 template <class T> struct Blk { T *l0s, *l0b, *wq, *bq, *wk, *bk, *wv, *bv, *wo, *bo, *l1s, *l1b, *w1, *b1, *w2, *b2, *ls1, *ls2; };
 using BlkW = Blk<const float>;
@@ -855,9 +1011,14 @@ struct Drop {
   NoiseKey at(uint32_t kind, int layer = 0) const { NoiseKey k = key; k.site = kind | (uint32_t)layer << 8; return k; }
 };
 struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; int mask_as_bias = 0;     // lang_T > 0: the policy's mask with T language rows in front;
-                Drop drop; int layer = 0; };                                                             // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel);
+                Drop drop; int layer = 0;                                                                 // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel);
                                                                                                           // drop: vit_kwargs.dropout_rate at the sites of `layer` (the policy only)
-struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y; };
+                int differential = 0; DiffLeaves dif{-1, -1, -1, -1, -1};                                 // differential: DifferentialAttention with the block's five vectors at
+                const float* theta = nullptr; float* dtheta = nullptr;                                    // dif in a row of theta / dtheta (row stride ws), depth `layer`
+                float lambda_init() const { return (float)(0.8 - 0.6 * exp(-0.3 * (double)layer)); } };   // differential_transformer.py:75-79
+// dP, t2 (a DifferentialAttention policy only, else nullptr): dp = dO V^T [nb][H][S][Sp] and the row sums sum_k dp A2 [nb][H][S];
+// dp is then ds [nb][2 H][S][Sp]
+struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y, *dP, *t2; };
 
 // Y[nb][S][N] (+)= X[nb][S][K] W + bias with W per episode (ws = G) or shared (ws = 0: the batch folds into M, so
 // S = 257 does not pay a mostly empty 64-row tile per sample)
@@ -893,40 +1054,57 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   float* const h2 = a.h2 ? a.h2 : t.h;
   float* const gg = a.g ? a.g : t.g;
   KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_in, h, a.mean0, a.rstd0, w.l0s, w.l0b, ws, rows, S, D);
-  {
-    // q, k, v = h Wq, h Wk, h Wv as ONE batched product when weights, biases and outputs are equally spaced in memory order
-    // (shared weights): 3 x 390 tiles in one launch instead of three launches of 198 double tiles that fill 77 % of the chip
-    const float* Wm[3] = {w.wq, w.wk, w.wv};
-    const float* Bm[3] = {w.bq, w.bk, w.bv};
-    float* Ym[3] = {a.q, a.k, a.v};
-    int ord[3] = {0, 1, 2};
-    for (int i = 0; i < 2; ++i)
-      for (int j = 0; j < 2 - i; ++j)
-        if (Wm[ord[j]] > Wm[ord[j + 1]]) { const int tsw = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = tsw; }
-    const long wsd = Wm[ord[1]] - Wm[ord[0]], bsd = Bm[ord[1]] - Bm[ord[0]], ysd = Ym[ord[1]] - Ym[ord[0]];
-    const bool one = ws == 0 && Wm[ord[2]] - Wm[ord[1]] == wsd && Bm[ord[2]] - Bm[ord[1]] == bsd && Ym[ord[2]] - Ym[ord[1]] == ysd &&
-                     wsd % 4 == 0 && ysd % 4 == 0;
-    if (one) {
-      BG g{h, Wm[ord[0]], Ym[ord[0]], Bm[ord[0]], nb * S, D, D, D, D, D, 0, 0, 0, wsd, 0, ysd, 0, 3, 1.f, 0};
-      g.sBias1 = bsd;
-      bgemm(st, false, false, g, 1);
-    } else {
-      for (int i = 0; i < 3; ++i) linear(st, nb, S, ws, h, Wm[i], Bm[i], Ym[i], D, D, 0);
-    }
-  }
-  // scores[b][h] = q_h k_h^T / sqrt(hd)
-  // the S x S attention matrices have row stride Sp = S rounded up to 4 floats, zeros behind every row (written by the softmax
-  // kernels): as A operands they are staged with float4 loads like everything else (S = 257: the all-dword staging these four
-  // products per layer were left with cost 3.6 ms per step)
   const int Sp = (S + 3) & ~3;
-  bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
-  if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
-  else if (op.mask_as_bias) KL(softmax_bias_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, Sp);
-  else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
-  {
-    BG pv{a.p, a.v, a.o, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
+  if (op.differential) {
+    // DifferentialAttention: bias-free q, k, v; 2 H sub-heads of width hd / 2 with stride hd / 2 in q and k, unscaled
+    // scores; softmax_bias_fwd_kernel per sub-head row (the mask is added, as in §20); A = A1 - lambda A2; O = A V; subln into a.o
+    const int hp = hd / 2, H2 = 2 * H;
+    const DiffLeaves& df = op.dif;
+    linear(st, nb, S, ws, h, w.wq, nullptr, a.q, D, D, 0);
+    linear(st, nb, S, ws, h, w.wk, nullptr, a.k, D, D, 0);
+    linear(st, nb, S, ws, h, w.wv, nullptr, a.v, D, D, 0);
+    bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hp, D, D, Sp, (long)S * D, hp, (long)S * D, hp, (long)H2 * S * Sp, (long)S * Sp, 0, H2, 1.f, 0}, nb);
+    KL(softmax_bias_fwd_kernel, dim3((nb * H2 * S + 3) / 4), dim3(256), a.p, nb * H2, S, Sp);
+    KL(diff_combine_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, a.pa, op.theta, ws, df.lq1, df.lk1, df.lq2, df.lk2, op.lambda_init(), nb, H, S, Sp);
+    BG pv{a.pa, a.v, a.oraw, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
     pv.a_padded = 1;
     bgemm(st, false, false, pv, nb);
+    KL(diff_subln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.oraw, a.o, op.theta, ws, df.sw, 1.f - op.lambda_init(), rows, S);
+  } else {
+    {
+      // q, k, v = h Wq, h Wk, h Wv as ONE batched product when weights, biases and outputs are equally spaced in memory order
+      // (shared weights): 3 x 390 tiles in one launch instead of three launches of 198 double tiles that fill 77 % of the chip
+      const float* Wm[3] = {w.wq, w.wk, w.wv};
+      const float* Bm[3] = {w.bq, w.bk, w.bv};
+      float* Ym[3] = {a.q, a.k, a.v};
+      int ord[3] = {0, 1, 2};
+      for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2 - i; ++j)
+          if (Wm[ord[j]] > Wm[ord[j + 1]]) { const int tsw = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = tsw; }
+      const long wsd = Wm[ord[1]] - Wm[ord[0]], bsd = Bm[ord[1]] - Bm[ord[0]], ysd = Ym[ord[1]] - Ym[ord[0]];
+      const bool one = ws == 0 && Wm[ord[2]] - Wm[ord[1]] == wsd && Bm[ord[2]] - Bm[ord[1]] == bsd && Ym[ord[2]] - Ym[ord[1]] == ysd &&
+                       wsd % 4 == 0 && ysd % 4 == 0;
+      if (one) {
+        BG g{h, Wm[ord[0]], Ym[ord[0]], Bm[ord[0]], nb * S, D, D, D, D, D, 0, 0, 0, wsd, 0, ysd, 0, 3, 1.f, 0};
+        g.sBias1 = bsd;
+        bgemm(st, false, false, g, 1);
+      } else {
+        for (int i = 0; i < 3; ++i) linear(st, nb, S, ws, h, Wm[i], Bm[i], Ym[i], D, D, 0);
+      }
+    }
+    // scores[b][h] = q_h k_h^T / sqrt(hd)
+    // the S x S attention matrices have row stride Sp = S rounded up to 4 floats, zeros behind every row (written by the softmax
+    // kernels): as A operands they are staged with float4 loads like everything else (S = 257: the all-dword staging these four
+    // products per layer were left with cost 3.6 ms per step)
+    bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
+    if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
+    else if (op.mask_as_bias) KL(softmax_bias_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, Sp);
+    else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
+    {
+      BG pv{a.p, a.v, a.o, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
+      pv.a_padded = 1;
+      bgemm(st, false, false, pv, nb);
+    }
   }
   if (w.ls1) {
     linear(st, nb, S, ws, a.o, w.wo, w.bo, a.y1, D, D, 0);
@@ -968,6 +1146,7 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   auto bgrad = [&](const float* dY, int N, float* dB) {
     // the 4-column form wins on the narrow matrices of the policy / hypernetwork; on the encoder's 768- and 3072-wide ones
     // its fewer, fatter waves lose to the one-column form (17 vs 23 us)
+    if (op.differential) { KL(colsum_episode_kernel, dim3((N + 63) / 64, nb), dim3(256), dY, dB, gs, S, S, N); return; }      // no atomics
     const bool v4 = N % 4 == 0 && N <= 512 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0;
     if (shared && N % 4 == 0 && N > 512 && rows >= 2048 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0)
       KL(colsum4b_kernel, dim3((N / 4 + 63) / 64, 1, (rows + CSB_WAVES * 8 * CSB_BATCH - 1) / (CSB_WAVES * 8 * CSB_BATCH)), dim3(CSB_WAVES * 64), dY, dB, rows, N);
@@ -977,6 +1156,11 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     else KL(colsum_kernel, dim3((N + 63) / 64, nb, (S + 63) / 64), dim3(64), dY, dB, gs, S, S, N, nb);
   };
   auto ln_bwd = [&](const float* x, const float* dy, const float* mean, const float* rstd, const float* sc, float* gs_, float* gb_) {
+    if (op.differential) {                                                                                              // no atomics
+      KL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), x, dy, mean, rstd, sc, dx, (float*)nullptr, (float*)nullptr, gs, rows, S, D, 1);
+      KL(ln_pgrad_episode_kernel, dim3((D + 63) / 64, nb), dim3(256), x, dy, mean, rstd, gs_, gb_, gs, S, D);
+      return;
+    }
     if (shared && D % 4 == 0 && D <= 1024 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
       KL(ln_bwd_shared_kernel, dim3((rows + 63) / 64), dim3(LNB_WAVES * 64), x, dy, mean, rstd, sc, dx, gs_, gb_, rows, D, 1);
     } else if (shared) {
@@ -1027,19 +1211,34 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     dy = t.y;
   }
   wgrad(a.o, D, dy, D, gw.wo);
-  bgrad(dy, D, gw.bo);
+  if (gw.bo) bgrad(dy, D, gw.bo);                                                                                       // (DifferentialAttention's projections have no bias)
   linear_dx(st, nb, S, ws, dy, w.wo, t.d, D, D, 0);                                                                     // do
   // dp = do_h v_h^T ; dv_h = p^T do_h
   const int Sp = (S + 3) & ~3;                                                                                          // row stride of p / dp (block_fwd)
   const long ss0 = (long)H * S * Sp, ss1 = (long)S * Sp;
   auto padded = [](BG g) { g.a_padded = 1; return g; };
-  bgemm(st, false, true, BG{t.d, a.v, t.dp, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
-  bgemm(st, true, false, padded(BG{a.p, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
-  if (aux) KL(attention_aux_kernel, dim3(nb), dim3(256), *aux);                                                            // dp row S-1 += d aux / dp
-  KL(softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dp, nb * H * S, S, Sp);                             // ds
-  const float sc = 1.f / sqrtf((float)hd);
-  bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);   // dq = ds k / sqrt(hd)
-  bgemm(st, true, false, padded(BG{t.dp, a.q, t.dk, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);    // dk = ds^T q / sqrt(hd)
+  if (op.differential) {
+    // t.d = dN -> dO and dw (subln); dP = dO V^T once per head; dV = A^T dO; both softmax backwards from dP into t.dp = ds [nb][2 H];
+    // d lambda from the kept row sums; dq_c = ds_c k_c, dk_c = ds_c^T q_c over the 2 H sub-heads, scale 1
+    const int hp = hd / 2, H2 = 2 * H;
+    const DiffLeaves& df = op.dif;
+    const long sd0 = (long)H2 * S * Sp;
+    KL(diff_subln_bwd_kernel, dim3(nb), dim3(256), a.oraw, t.d, op.theta, op.dtheta, ws, df.sw, 1.f - op.lambda_init(), S);
+    bgemm(st, false, true, BG{t.d, a.v, t.dP, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
+    bgemm(st, true, false, padded(BG{a.pa, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
+    KL(diff_softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dP, t.dp, t.t2, op.theta, ws, df.lq1, df.lk1, df.lq2, df.lk2, op.lambda_init(), nb, H, S, Sp);
+    KL(diff_lambda_bwd_kernel, dim3(nb), dim3(64), t.t2, op.theta, op.dtheta, ws, df.lq1, df.lk1, df.lq2, df.lk2, H * S);
+    bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hp, S, Sp, D, D, sd0, ss1, (long)S * D, hp, (long)S * D, hp, 0, H2, 1.f, 0}), nb);
+    bgemm(st, true, false, padded(BG{t.dp, a.q, t.dk, nullptr, S, hp, S, Sp, D, D, sd0, ss1, (long)S * D, hp, (long)S * D, hp, 0, H2, 1.f, 0}), nb);
+  } else {
+    bgemm(st, false, true, BG{t.d, a.v, t.dp, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
+    bgemm(st, true, false, padded(BG{a.p, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
+    if (aux) KL(attention_aux_kernel, dim3(nb), dim3(256), *aux);                                                            // dp row S-1 += d aux / dp
+    KL(softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dp, nb * H * S, S, Sp);                             // ds
+    const float sc = 1.f / sqrtf((float)hd);
+    bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);   // dq = ds k / sqrt(hd)
+    bgemm(st, true, false, padded(BG{t.dp, a.q, t.dk, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);    // dk = ds^T q / sqrt(hd)
+  }
   const float* h = a.h ? a.h : t.h;
   if (!a.h) KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_in, t.h, a.mean0, a.rstd0, w.l0s, w.l0b, ws, rows, S, D);      // recompute h
   const float* dqkv[3] = {t.dq, t.dk, t.dv};
@@ -1064,7 +1263,7 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     // bias every query has every key, the constant is still one per row, and the leaf is left at zero in the same way:
     // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.  Under the policy's
     // dropout (hvla_train_noise) the kept activations are 1 / keep_prob larger and the same rounding came to 1.5e-3 at MID: left at zero too.
-    if (!((op.lang_T > 0 || op.mask_as_bias || dr.on()) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
+    if (gBm[i] && !((op.lang_T > 0 || op.mask_as_bias || dr.on()) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
     linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0);                                                         // dh
   }
   ln_bwd(a.x_in, t.g, a.mean0, a.rstd0, w.l0s, gw.l0s, gw.l0b);
@@ -1090,20 +1289,22 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
 #else
   auto take = [&](long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
 #endif
-  auto take_blk = [&](long nb, long s, long d, long h, long f, bool ls) {
+  // diff: a DifferentialAttention block -- p holds 2 h tables, and pa and oraw follow the block's other buffers
+  auto take_blk = [&](long nb, long s, long d, long h, long f, bool ls, bool diff = false) {
     BlkBuf b; b.x_in = take(nb * s * d); b.mean0 = take(nb * s); b.rstd0 = take(nb * s); b.k = take(nb * s * d); b.q = take(nb * s * d);      // k, q, v: the order of the weight leaves (block_fwd batches the three)
-    b.v = take(nb * s * d); b.p = take(nb * h * s * ((s + 3) & ~3L)); b.o = take(nb * s * d); b.x_mid = take(nb * s * d); b.mean1 = take(nb * s);
+    b.v = take(nb * s * d); b.p = take(nb * (diff ? 2 * h : h) * s * ((s + 3) & ~3L)); b.o = take(nb * s * d); b.x_mid = take(nb * s * d); b.mean1 = take(nb * s);
     b.rstd1 = take(nb * s); b.u = take(nb * s * f);
     b.y1 = ls ? take(nb * s * d) : nullptr; b.y2 = ls ? take(nb * s * d) : nullptr;
     // 288 GB of HBM: the LayerNorm and GELU outputs are kept (B = 32 with the encoder trained: 1.8 GB) instead of recomputed
     b.h = take(nb * s * d); b.h2 = take(nb * s * d); b.g = take(nb * s * f);
+    b.pa = diff ? take(nb * h * s * ((s + 3) & ~3L)) : nullptr; b.oraw = diff ? take(nb * s * d) : nullptr;
     return b;
   };
   const long S = g.pos_rows(), D = g.D, H = g.H, F = g.M, Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;     // S: the policy's rows, T + P + 1 under use_language_token
   const long Se = g.P() + 1, E = g.E, He = g.enc_heads, Fe = g.enc_mlp;
   pl.cb.resize(g.ctx_layers); pl.pb.resize(g.L); pl.eb.resize(enc ? g.enc_layers : 0);
   for (auto& b : pl.cb) b = take_blk(B, Sc, C, Hc, Fc, false);
-  for (auto& b : pl.pb) b = take_blk(B, S, D, H, F, false);
+  for (auto& b : pl.pb) b = take_blk(B, S, D, H, F, false, g.differential != 0);
   for (auto& b : pl.eb) b = take_blk(B, Se, E, He, Fe, true);
   pl.cx_fin = take(B * Sc * C); pl.cdx = take(B * Sc * C);
   pl.px_fin = take(B * S * D); pl.pdx = take(B * S * D);
@@ -1117,7 +1318,7 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
   // gradient, du) AND rows x D (dh2 = du W1^T and the three dh products go to t.g, do = dy Wo^T to t.d): the larger of the two,
   // since accept.h admits F < D (policy mlp 32, ctx_mlp 16, enc_mlp 128 under a wider model)
   auto mx = [&](long a, long b, long c) { c = enc ? c : 0; return a > b ? (a > c ? a : c) : (b > c ? b : c); };
-  const long rd = mx(B * S * D, B * Sc * C, B * Se * E), rf = mx(B * S * F, B * Sc * Fc, B * Se * Fe), hss = mx(B * H * S * ((S + 3) & ~3L), B * Hc * Sc * ((Sc + 3) & ~3L), B * He * Se * ((Se + 3) & ~3L));
+  const long rd = mx(B * S * D, B * Sc * C, B * Se * E), rf = mx(B * S * F, B * Sc * Fc, B * Se * Fe), hss = mx(B * (g.differential ? 2 * H : H) * S * ((S + 3) & ~3L), B * Hc * Sc * ((Sc + 3) & ~3L), B * He * Se * ((Se + 3) & ~3L));
   const long rg = rf > rd ? rf : rd;
   pl.t.h = take(rd); pl.t.g = take(rg); pl.t.d = take(rg); pl.t.dk = take(rd); pl.t.dq = take(rd); pl.t.dv = take(rd);      /* k, q, v: the order of the leaves (block_bwd batches the three) */ pl.t.dp = take(hss);
   pl.t.y = take(rd);
@@ -1126,6 +1327,9 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
   // the noise copies come last: every offset above is what it is without noise
   pl.ntok = nz.sigma > 0.f && !enc ? take((long)B * g.P() * E) : nullptr;
   pl.ncls = nz.image_dropout > 0.f ? take((long)B * E) : nullptr;
+  // ... and so do DifferentialAttention's two temporaries (t.dp above holds ds of the 2 H sub-heads)
+  pl.t.dP = g.differential ? take(B * H * S * ((S + 3) & ~3L)) : nullptr;
+  pl.t.t2 = g.differential ? take(B * H * S) : nullptr;
   pl.used = ws - base;
   return pl;
 }
@@ -1152,7 +1356,7 @@ void train_trace_plan(const Geom& g, int B, bool train_encoder, const TrainNoise
       put(pre + "x_in", b.x_in); put(pre + "mean0", b.mean0); put(pre + "rstd0", b.rstd0); put(pre + "k", b.k); put(pre + "q", b.q);
       put(pre + "v", b.v); put(pre + "p", b.p); put(pre + "o", b.o); put(pre + "x_mid", b.x_mid); put(pre + "mean1", b.mean1);
       put(pre + "rstd1", b.rstd1); put(pre + "u", b.u); put(pre + "y1", b.y1); put(pre + "y2", b.y2); put(pre + "h", b.h);
-      put(pre + "h2", b.h2); put(pre + "g", b.g);
+      put(pre + "h2", b.h2); put(pre + "g", b.g); put(pre + "pa", b.pa); put(pre + "oraw", b.oraw);
     }
   };
   put_blk("cb", pl.cb); put_blk("pb", pl.pb); put_blk("eb", pl.eb);
@@ -1161,7 +1365,7 @@ void train_trace_plan(const Geom& g, int B, bool train_encoder, const TrainNoise
   put("t.h", pl.t.h); put("t.g", pl.t.g); put("t.d", pl.t.d); put("t.dk", pl.t.dk); put("t.dq", pl.t.dq); put("t.dv", pl.t.dv);
   put("t.dp", pl.t.dp); put("t.y", pl.t.y);
   put("cmean", pl.cmean); put("crstd", pl.crstd); put("ctx", pl.ctx); put("dctx", pl.dctx); put("ctxn", pl.ctxn); put("dxrow", pl.dxrow);
-  put("ntok", pl.ntok); put("ncls", pl.ncls);
+  put("ntok", pl.ntok); put("ncls", pl.ncls); put("t.dP", pl.t.dP); put("t.t2", pl.t.t2);
   for (size_t i = 0; i < pl.taken.size(); ++i) printf("plan %s %ld %ld\n", name[i].c_str(), pl.taken[i].first, pl.taken[i].second);
 }
 #endif
@@ -1194,7 +1398,12 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
   const BlkOpt ctx_opt{1, in.attn_mask, 0}, enc_opt{2, nullptr, 1};      // these two draw nothing
   const BlkOpt pol_opt{0, nullptr, 0, Tl, g.mask_as_bias, pdrop};
-  const auto pol_at = [&](int l) { BlkOpt o = pol_opt; o.layer = l; return o; };      // the dropout sites carry their layer
+  const auto pol_at = [&](int l) {                                                     // the dropout sites carry their layer
+    BlkOpt o = pol_opt;
+    o.layer = l;
+    if (g.differential) { o.differential = 1; o.dif = L.dif[l]; o.theta = tb.theta; o.dtheta = tb.dtheta; }
+    return o;
+  };
 
   // =============================== DINOv2 forward in f32, activations kept (HF Dinov2Model; base_vit.py:111-131) =====
   const float* tokens = in.tokens;         // [B][P][E] rows, episode stride tok_stride
@@ -1270,7 +1479,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   if (pdrop.on()) dropout_bwd(st, pdrop, NOISE_POLICY_INPUT, 0, pdx, pdx, B, (long)S * D);
   const float* pdx_patch = pdx + (long)Tl * D;
   KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + L.pos, G, pdx, (long)S * D, B);
-  KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx_patch, tb.dtheta + L.bp, G, S, P, D, B);
+  if (g.differential) KL(colsum_episode_kernel, dim3((D + 63) / 64, B), dim3(256), pdx_patch, tb.dtheta + L.bp, G, S, P, D);
+  else KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx_patch, tb.dtheta + L.bp, G, S, P, D, B);
   bgemm(st, true, false, BG{tokens, pdx_patch, tb.dtheta + L.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
   if (Tl) {     // dbl = sum of the language rows, dWl = tok^T dx0[:Tl]; nothing flows into token_embedding (T5 is frozen)
     KL(colsum_kernel, dim3((D + 63) / 64, B, (Tl + 63) / 64), dim3(64), pdx, tb.dtheta + L.bl, G, S, Tl, D, B);

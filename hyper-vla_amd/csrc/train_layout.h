@@ -12,6 +12,10 @@ namespace hvla {
 // tables (serving_layout.h), the same members as offsets into the serving buffers.  ls1 / ls2 (LayerScale): DINOv2 only, else -1.
 struct BlockLeaves { long ln0_s, ln0_b, wq, bq, wk, bk, wv, bv, wo, bo, ln1_s, ln1_b, w1, b1, w2, b2, ls1, ls2; };
 
+// What a DifferentialAttention block (Geom::differential) has besides q_proj / k_proj / v_proj / out_proj, which take
+// wq / wk / wv / wo above with bq = bk = bv = bo = -1: the four lambda vectors [D / (2 H)] and subln/weight [D / H], in a row of theta.
+struct DiffLeaves { long lq1, lk1, lq2, lk2, sw; };
+
 // flat layout of the trainable hypernetwork parameters (float32 elements)
 // `total` = the hypernetwork's own parameters; the shared DINOv2 leaves follow at [total, total + enc_total) when the
 // image encoder is trained too (`fine_tune_pretrained_image_encoder=True`), in hypervla.config.encoder_leaves order.
@@ -27,10 +31,12 @@ struct TrainLayout {
                            // tables may be built for: they do not read the policy's offsets)
   long wl, bl;             // encoder_language_token_projection_{kernel,bias} in a row of theta (use_language_token; else -1).  L.pos then
                            // spans g.pos_rows() = T + P + 1 rows
+  DiffLeaves dif[TRAIN_MAX_POLICY_LAYERS];   // use_differential_transformer: the five leaves a block has besides its four kernels (else all -1)
 };
 
 // nullptr, or why the training path (hvla_train_*) does not serve a geometry hvla_create accepted (HVLA_E_SHAPE with this text).
-// The first answer is the default: hvla_train_language_tokens(ctx, 1) lifts it for that context (train_entry, api.hip)
+// The first two answers are the default: hvla_train_differential(ctx, 1) / hvla_train_language_tokens(ctx, 1) lift them for that
+// context (train_entry, api.hip)
 inline const char* train_refusal(const Geom& g) {
   if (g.differential) return "the training path does not build use_differential_transformer (DifferentialAttention): serving is";
   if (g.lang_in_policy) return "the training path does not build use_language_token";
@@ -43,6 +49,13 @@ inline const char* train_refusal(const Geom& g, bool language_tokens) {
   Geom plain = g;
   plain.lang_in_policy = 0;
   return train_refusal(plain);
+}
+// ... and for a context whose caller asked for DifferentialAttention's backward (differential; hvla_train_differential)
+inline const char* train_refusal(const Geom& g, bool language_tokens, bool differential) {
+  if (!differential || !g.differential) return train_refusal(g, language_tokens);
+  Geom plain = g;
+  plain.differential = 0;
+  return train_refusal(plain, language_tokens);
 }
 inline TrainLayout make_train_layout(const Geom& g) {
   TrainLayout L{};
@@ -95,8 +108,17 @@ inline TrainLayout make_train_layout(const Geom& g) {
     y.ln0_b = f(B + "LayerNorm_0_bias"); y.ln0_s = f(B + "LayerNorm_0_scale"); y.ln1_b = f(B + "LayerNorm_1_bias"); y.ln1_s = f(B + "LayerNorm_1_scale");
     y.b1 = f(B + "MlpBlock_0_Dense_0_bias"); y.w1 = f(B + "MlpBlock_0_Dense_0_kernel");
     y.b2 = f(B + "MlpBlock_0_Dense_1_bias"); y.w2 = f(B + "MlpBlock_0_Dense_1_kernel");
-    y.bk = f(A + "key_bias"); y.wk = f(A + "key_kernel"); y.bo = f(A + "out_bias"); y.wo = f(A + "out_kernel");
-    y.bq = f(A + "query_bias"); y.wq = f(A + "query_kernel"); y.bv = f(A + "value_bias"); y.wv = f(A + "value_kernel");
+    DiffLeaves& d = L.dif[l];
+    d.lq1 = d.lk1 = d.lq2 = d.lk2 = d.sw = -1;
+    if (g.differential) {      // four bias-free Dense(D) and five vectors (differential_transformer.py:139-156)
+      y.wk = f(A + "k_proj_kernel"); y.wo = f(A + "out_proj_kernel"); y.wq = f(A + "q_proj_kernel"); y.wv = f(A + "v_proj_kernel");
+      y.bk = y.bo = y.bq = y.bv = -1;
+      d.lk1 = f(A + "lambda_k1"); d.lk2 = f(A + "lambda_k2"); d.lq1 = f(A + "lambda_q1"); d.lq2 = f(A + "lambda_q2");
+      d.sw = f(A + "subln_weight");
+    } else {
+      y.bk = f(A + "key_bias"); y.wk = f(A + "key_kernel"); y.bo = f(A + "out_bias"); y.wo = f(A + "out_kernel");
+      y.bq = f(A + "query_bias"); y.wq = f(A + "query_kernel"); y.bv = f(A + "value_bias"); y.wv = f(A + "value_kernel");
+    }
     y.ls1 = y.ls2 = -1;
   }
   return L;

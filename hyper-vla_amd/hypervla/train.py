@@ -442,6 +442,10 @@ class FineTuner:
     policy runs with the instruction's token embeddings in front of the patches, as the reference's loop does for such a model; the
     two heads `output_head_encoder_language_token_projection_{kernel,bias}` train (or freeze, `frozen_keys`) like every other head.
     Without the keyword such a model is refused; the attention terms are not defined for it.
+    `differential=True`: fine-tune a model with `vit_kwargs.use_differential_transformer` (hvla_train_differential): every
+    policy block runs DifferentialAttention forward and backward; the heads of the four lambda vectors and of `subln/weight` train (or
+    freeze, `frozen_keys`) like every other head.  Without the keyword such a model is refused; the attention terms and the four noise
+    arguments are refused with it.
     `dropout_rate`, `image_embedding_noise`, `embedding_dropout_rate`, `image_dropout` (all 0 = off, the default; `train_noise_from_config`
     reads them from a reference-shaped config): the four noise sources the reference's loop switches on with train=True
     (hvla_train_noise_set), drawn from a counter-based generator keyed by `noise_seed` -- equal to jax's noise in
@@ -456,17 +460,30 @@ class FineTuner:
                  accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
                  attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=(), language_tokens: bool = False,
                  dropout_rate: float = 0.0, image_embedding_noise: float = 0.0, embedding_dropout_rate: float = 0.0,
-                 image_dropout: float = 0.0, noise_seed: int = 0):
+                 image_dropout: float = 0.0, noise_seed: int = 0, differential: bool = False):
         self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
             attention_entropy, attention_map_alignment, num_steps)
         self.language_tokens = bool(language_tokens)
+        self.differential = bool(differential)
         self.noise = dict(policy_dropout=float(dropout_rate), image_embedding_noise=float(image_embedding_noise),
                           context_dropout=float(embedding_dropout_rate), image_dropout=float(image_dropout))
         self.noise_on = any(v != 0.0 for v in self.noise.values())
         self.noise_seed, self.noise_draw = int(noise_seed), 0
-        if getattr(model.geometry, "differential", False):
+        if getattr(model.geometry, "differential", False) and not self.differential:
             raise ValueError("fine-tuning a model with vit_kwargs.use_differential_transformer is not built; serving is "
-                             "(DifferentialAttention has no backward pass in the training kernels, DESIGN.md §22)")
+                             "(without differential=True the training kernels run no DifferentialAttention, DESIGN.md §23)")
+        if self.differential and not getattr(model.geometry, "differential", False):
+            raise ValueError("differential=True needs a model with vit_kwargs.use_differential_transformer: this model's policy "
+                             "has no DifferentialAttention")
+        if self.differential and self.language_tokens:
+            raise ValueError("differential=True with language_tokens=True: use_differential_transformer together with "
+                             "use_language_token is not built (DESIGN.md §22)")
+        if self.differential and (self.attention_entropy > 0 or self.attention_map_alignment > 0):
+            raise ValueError("attention_entropy / attention_map_alignment are not defined with differential=True: the module's map is "
+                             "the signed A1 - lambda A2, which has no entropy (DESIGN.md §23)")
+        if self.differential and self.noise_on:
+            raise ValueError("dropout_rate / image_embedding_noise / embedding_dropout_rate / image_dropout with differential=True are "
+                             "not built: the noise is restated for the other attention modules only (DESIGN.md §23)")
         if getattr(model.geometry, "lang_in_policy", False) and not self.language_tokens:
             raise ValueError("fine-tuning a model with vit_kwargs.use_language_token is not built: the training kernels run the "
                              "policy without language tokens (serving it is, DESIGN.md §11)")
@@ -596,6 +613,7 @@ class FineTuner:
         """Whether this tuner trains the policy with its language prefix (hvla_train_language_tokens; host-side like the others,
         and first: the entries below refuse a use_language_token context without it)."""
         self.model._ctx.train_language_tokens(self.language_tokens)
+        self.model._ctx.train_differential(self.differential)
 
     def _select_source(self):
         """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this

@@ -138,10 +138,10 @@ int hvla_create_with_v2(const hvla_config* cfg, const hvla_policy_options_v2* op
  *                       (eps 1e-5), times subln's weight and 1 - lambda_init(layer).  The generated leaves of the attention are
  *                       `..._DifferentialAttention_0_{k_proj_kernel, lambda_k1, lambda_k2, lambda_q1, lambda_q2, out_proj_kernel,
  *                       q_proj_kernel, subln_weight, v_proj_kernel}` (no biases) and lead their block in the parameter order.
- *                       SERVED only: every hvla_train_* entry that reads the geometry, hvla_train_publish
- *                       included, returns HVLA_E_SHAPE with a text, and so does hvla_set_attention_outputs with a
- *                       head_attention buffer (the reference sows no attention weights in this branch); dino_cls_attention
- *                       alone is accepted.  Not built together with use_language_token or attention_mask_as_bias (with both
+ *                       Until hvla_train_differential(ctx, 1) asks for its backward pass every
+ *                       hvla_train_* entry that reads the geometry, hvla_train_publish included, returns HVLA_E_SHAPE with
+ *                       a text; so does hvla_set_attention_outputs with a head_attention buffer (the reference sows no
+ *                       attention weights in this branch); dino_cls_attention alone is accepted.  Not built together with use_language_token or attention_mask_as_bias (with both
  *                       vit_kwargs set the reference runs DifferentialAttention: pass differential_attention alone):
  *                       HVLA_E_SHAPE, hvla_last_error(NULL) says why.                                                       */
 typedef struct hvla_policy_options_v3 {
@@ -358,7 +358,7 @@ int hvla_loss(hvla_ctx* ctx, const float* actions, const float* gripper_logits, 
  * Every buffer is DEVICE memory owned by the caller; the flat parameter order is make_train_layout()
  * (csrc/train_layout.h) == hypervla.train.train_param_layout(); sizes from hvla_train_sizes.  Every hvla_train_*
  * entry first asks whether the training path serves the context's geometry: use_language_token without
- * hvla_train_language_tokens(ctx, 1), more than 8 context, 16 policy or 24 image-encoder layers are HVLA_E_SHAPE before any
+ * hvla_train_language_tokens(ctx, 1), differential_attention without hvla_train_differential(ctx, 1), more than 8 context, 16 policy or 24 image-encoder layers are HVLA_E_SHAPE before any
  * other argument is looked at.                                                                           */
 typedef struct hvla_train_buffers {
   float* params;           /* [n_params]                                                     */
@@ -515,6 +515,19 @@ int hvla_train_attention_losses(hvla_ctx* ctx, const hvla_train_attention* opts)
  * heads output_head_*_key_bias): with few language keys the column sum that forms it carried only operand rounding.
  * HVLA_E_SHAPE: on == 1 on a context created without use_language_token; any other value.  NULL ctx: HVLA_E_STATE.           */
 int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on);
+/* Fine-tune a differential_attention context (hvla_create_with_v3; hypervla/components/differential_transformer.py:99-252 runs in
+ * the reference's training loop as it does in inference).  The exact counterpart of hvla_train_language_tokens: a host-side
+ * setting kept on the context, nothing launched, nothing allocated.  on == 0 (always HVLA_OK) is the state of a new context: every
+ * hvla_train_* entry refuses a differential_attention context with HVLA_E_SHAPE.  on == 1: they serve it.  Every policy block
+ * then runs DifferentialAttention forward and backward in f32: the four bias-free projections, the two
+ * unscaled softmaxes per head with the mask added, lambda from the episode's own four vectors and the layer's depth, the RMSNorm
+ * over a head's 16 values; the gradients of lambda_q1 / k1 / q2 / k2 and subln/weight land in the episode's dtheta row and flow
+ * through the output heads like every other leaf, reduced in a fixed order (no floating-point atomics: a sample's loss and dtheta
+ * row do not depend on the batch around it).  hvla_train_sizes reports the longer workspace; hvla_train_publish serves the
+ * trained vector into the running context.  Refused with HVLA_E_SHAPE and a text on such a context: hvla_train_attention_losses
+ * with a weight != 0 (the module's map A1 - lambda A2 is signed: no entropy) and hvla_train_noise_set with a rate or sigma != 0.
+ * HVLA_E_SHAPE: on == 1 on a context created without differential_attention; any other value.  NULL ctx: HVLA_E_STATE.       */
+int hvla_train_differential(hvla_ctx* ctx, int32_t on);
 /* Replaces: the four noise sources the reference's training loop switches on by running the model with train=True --
  * vit_kwargs.dropout_rate (base_vit.py:205; transformer.py:67,74,192), vit_kwargs.image_embedding_noise (base_vit.py:123-127),
  * hypernet_kwargs.embedding_dropout_rate (hypernetwork.py:193-195) and hypernet_kwargs.image_dropout (hypernetwork.py:119-122).

@@ -62,7 +62,7 @@ static int run(const Point& p, bool plan = false) {
   hipEvent_t ev[3];
   for (int i = 0; i < 3; ++i) ev[i] = reinterpret_cast<hipEvent_t>(buf<char>("event") + i);
   hipStream_t st = reinterpret_cast<hipStream_t>(buf<char>("st"));
-  if (train_refusal(g, true)) { printf("refused: %s\n", train_refusal(g, true)); return 1; }     // (a use_language_token point is one that asked)
+  if (train_refusal(g, true, true)) { printf("refused: %s\n", train_refusal(g, true, true)); return 1; }     // (a use_language_token or differential point is one that asked)
   const TrainLayout L = make_train_layout(g);
   if (!L.policy_ok) { printf("a policy leaf was not found\n"); return 1; }
   if (plan) {
