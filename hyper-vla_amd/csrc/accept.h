@@ -15,6 +15,7 @@
 //              k-steps of the f32 MFMA), ctx_mlp % 16 == 0, 0 <= ctx_layers <= CTX_MAX_LAYERS, 2 <= lang_tokens <= 38,
 //              lang_dim % 4 == 0, and the working set fits the context encoder's LDS (ctx_encoder_lds_bytes <= 160 KiB)
 //   use_language_token   additionally lang_tokens <= 32 (one 32-key tile) and lang_dim % 64 == 0
+//   share_layer_index=False   lang_tokens + 1 + NL <= 48 rows (NL = layers + 5, + 1 with use_language_token), the LDS formula with that many
 //   use_differential_transformer   not with use_language_token; the per-layer vectors are 48 floats longer and the policy kernel keeps
 //              a second table of action-row partials, both inside the same 160 KiB
 #pragma once
@@ -35,8 +36,9 @@ constexpr int PRING = 4;              // policy_kernel's ring of staged weight t
 
 // ---- context encoder: floats of its third LDS buffer (q | k | v or the MLP hidden rows; the staged token chunk; the CLS row and
 // the partial sums of its projection), and the dynamic LDS of ctx_encoder_kernel for T task tokens, width C, MLP width F, image width E
-inline size_t ctx_big_elems(int T, int C, int F, int E) {
-  const int S = T + 2;
+// (extra_rows: the layer tokens beyond the first, NL - 1 under share_layer_index=False)
+inline size_t ctx_big_elems(int T, int C, int F, int E, int extra_rows = 0) {
+  const int S = T + 2 + extra_rows;
   const int ldq = 3 * C + 4, ldf = F + 4;
   int bigld = ldq > ldf ? ldq : ldf;
   if (bigld < 132) bigld = 132;
@@ -44,9 +46,10 @@ inline size_t ctx_big_elems(int T, int C, int F, int E) {
   if (big_elems < (size_t)E + CTX_THREADS) big_elems = (size_t)E + CTX_THREADS;
   return big_elems;
 }
-inline size_t ctx_encoder_lds_bytes(int T, int C, int F, int E) {
-  return ((size_t)2 * (T + 2) * (C + 4) + ctx_big_elems(T, C, F, E) + 64) * sizeof(float);   // x, h, big, the key mask
+inline size_t ctx_encoder_lds_bytes(int T, int C, int F, int E, int extra_rows = 0) {
+  return ((size_t)2 * (T + 2 + extra_rows) * (C + 4) + ctx_big_elems(T, C, F, E, extra_rows) + 64) * sizeof(float);   // x, h, big, the key mask
 }
+constexpr int CTX_MAX_ROWS = 48;      // three 16-row MFMA tiles: the context kernels' sequence limit
 
 // ---- generated policy: the dynamic LDS of policy_kernel<NW> (NW = P / 32 waves) and of its language-token form, THE description:
 // policy_lds_bytes takes its total from it and the kernel body (policy_body.inc) is held to it by static_asserts.  What each buffer
@@ -107,7 +110,10 @@ inline size_t policy_lds_bytes_of(const hvla_config& c, int lang, int diff = 0) 
 // HVLA_OK, or why hvla_create refuses the geometry.  Every divisor is checked before it divides and every product is formed in 64
 // bits: the verdict arrives for ANY field values.  (struct_size and the options' struct_size are the caller's.)
 // diff: use_differential_transformer (a longer per-layer vector block and a second partial table in the policy kernel's LDS); not with lang
-inline int accept_geometry(const hvla_config& c, int lang, int diff = 0) {
+// layer_tokens: share_layer_index=False -- NL = layers + 5 (+ 1 with lang) layer tokens; the sequence lang_tokens + 1 + NL must fit
+// CTX_MAX_ROWS and the LDS working set is sized with it
+inline int accept_geometry(const hvla_config& c, int lang, int diff = 0, int layer_tokens = 0) {
+  if (layer_tokens != 0 && layer_tokens != 1) return HVLA_E_SHAPE;
   if (c.enc_dtype != HVLA_ENC_F16 && c.enc_dtype != HVLA_ENC_BF16) return HVLA_E_DTYPE;
   if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
   if ((diff != 0 && diff != 1) || (diff && lang)) return HVLA_E_SHAPE;
@@ -131,7 +137,13 @@ inline int accept_geometry(const hvla_config& c, int lang, int diff = 0) {
   if (lang && (c.lang_tokens > 32 || c.lang_dim % 64 != 0)) return HVLA_E_SHAPE;
   // the context encoder keeps its token block, q / k / v and the MLP hidden rows in LDS, the policy kernel its per-layer vectors:
   // a geometry that does not fit is refused here, not at the first hvla_generate / hvla_step
-  if (ctx_encoder_lds_bytes(c.lang_tokens, c.ctx_dim, c.ctx_mlp, c.enc_dim) > LDS_LIMIT) return HVLA_E_SHAPE;
+  int extra_rows = 0;
+  if (layer_tokens) {
+    const int64_t nl = (int64_t)c.layers + 5 + (lang ? 1 : 0);
+    if ((int64_t)c.lang_tokens + 1 + nl > CTX_MAX_ROWS) return HVLA_E_SHAPE;
+    extra_rows = (int)nl - 1;
+  }
+  if (ctx_encoder_lds_bytes(c.lang_tokens, c.ctx_dim, c.ctx_mlp, c.enc_dim, extra_rows) > LDS_LIMIT) return HVLA_E_SHAPE;
   if ((int64_t)c.layers * (9 * 64 + (int64_t)c.mlp) * (int64_t)sizeof(float) > (int64_t)LDS_LIMIT) return HVLA_E_SHAPE;   // (keeps the offsets in int)
   if (policy_lds_bytes_of(c, lang, diff) > LDS_LIMIT) return HVLA_E_SHAPE;
   return HVLA_OK;

@@ -43,7 +43,7 @@ using hvla::pack::f2h;
 
 struct hvla_weights {
   int B = 0;
-  int Gm = 0, Gv = 0, C = 0;     // the row sizes it was allocated for: an arena of another geometry is refused where rows are written whole
+  int Gm = 0, Gv = 0, C = 0;     // the row sizes it was allocated for (C: the floats of a context row, NL * ctx_dim): an arena of another geometry is refused where rows are written whole
   DevBuf wh, wl, vf, ctx, ring, count;
   DevBuf slot_count;             // int32 [B]: the episode pool's per-row ensemble counters (hvla_ensemble_slots)
 };
@@ -81,6 +81,7 @@ struct hvla_ctx {
   DevBuf hn_f32;                 // context-encoder parameters, natural flax layout
   CtxParams ctxp{};
   DevBuf wcat_hi, wcat_lo, bcat, perm;
+  DevBuf seg_token, tile_segs;   // layer_tokens: wcat_hi / wcat_lo then hold one fragment block per segment (pack.h TokenSegments)
   DevBuf enc16, encd16, encf32;  // encoder matrices (16-bit), their rounding residues x 4096 (16-bit) and vectors (f32)
   EncWeights encw{};
   // workspaces (sized for cfg.max_batch)
@@ -166,8 +167,25 @@ int hvla_create_with_v3(const hvla_config* c, const hvla_policy_options_v3* opts
   if (!c || !out) return HVLA_E_SHAPE;
   *out = nullptr;
   create_refusal = nullptr;
-  if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
   if (opts && opts->struct_size != sizeof(hvla_policy_options_v3)) return HVLA_E_SHAPE;   // the same rule for the options
+  const hvla_policy_options_v4 v4{sizeof(hvla_policy_options_v4), opts ? opts->use_language_token : 0, opts ? opts->attention_mask_as_bias : 0,
+                                  opts ? opts->differential_attention : 0, 0, 0};
+  return hvla_create_with_v4(c, opts ? &v4 : nullptr, device, out);
+}
+
+int hvla_create_with_v4(const hvla_config* c, const hvla_policy_options_v4* opts, int device, hvla_ctx** out) {
+  if (!c || !out) return HVLA_E_SHAPE;
+  *out = nullptr;
+  create_refusal = nullptr;
+  if (c->struct_size != sizeof(hvla_config)) return HVLA_E_SHAPE;   // the caller's header is not this library's: never read past its struct
+  if (opts && opts->struct_size != sizeof(hvla_policy_options_v4)) return HVLA_E_SHAPE;   // the same rule for the options
+  const int ltok = opts ? opts->layer_tokens : 0, shared = opts ? opts->shared_block_heads : 0;
+  if ((ltok != 0 && ltok != 1) || (shared != 0 && shared != 1)) return HVLA_E_SHAPE;
+  if (shared && !ltok) {
+    create_refusal = "shared_block_heads without layer_tokens: with share_TF_output_head and one shared layer token every policy block "
+                     "would receive the same weights";
+    return HVLA_E_SHAPE;
+  }
   const int lang = opts ? opts->use_language_token : 0;
   if (lang != 0 && lang != 1) return HVLA_E_SHAPE;
   const int mab = opts ? opts->attention_mask_as_bias : 0;
@@ -200,9 +218,11 @@ int hvla_create_with_v3(const hvla_config* c, const hvla_policy_options_v3* opts
   Geom& g = ctx->g;
   // what the hand-written kernels are specialised for (anything else is refused, never emulated): the predicate of accept.h,
   // which also refuses a context encoder or a policy that does not fit its kernel's LDS here, not at the first hvla_generate / hvla_step
-  if (const int verdict = accept_geometry(*c, lang, diff)) return verdict;
+  if (const int verdict = accept_geometry(*c, lang, diff, ltok)) return verdict;
   g = geom_of(*c, lang, diff);
   g.mask_as_bias = mab;
+  g.layer_tokens = ltok;
+  g.shared_block_heads = shared;
   const int P = g.P();
   if (hipSetDevice(device) != hipSuccess) return HVLA_E_DEVICE;
   ctx->lay = build_layout(g);
@@ -221,7 +241,7 @@ int hvla_create_with_v3(const hvla_config* c, const hvla_policy_options_v3* opts
   ctx->wsp = WorkspacePlan(P, g.S(), g.E, g.enc_mlp, ctx->Kp, c->max_batch);
   hipError_t e = hipSuccess;
   auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
-  A(ctx->ctx_hi, Bm * g.C * 2); A(ctx->ctx_lo, Bm * g.C * 2); A(ctx->ctx_f32, Bm * g.C * 4);
+  A(ctx->ctx_hi, Bm * g.ctx_row() * 2); A(ctx->ctx_lo, Bm * g.ctx_row() * 2); A(ctx->ctx_f32, Bm * g.ctx_row() * 4);   // [Bm][NL][C]
   A(ctx->tokens, Bm * P * g.E * 4); A(ctx->flags, 64 * sizeof(int));
   for (int i = 0; i < NUM_WS; ++i) A(ctx->ws[i], ctx->wsp.bytes(i));
   if (e != hipSuccess) return HVLA_E_ARENA_FULL;
@@ -247,6 +267,7 @@ void hvla_destroy(hvla_ctx* ctx) {
 }
 
 int64_t hvla_num_generated(const hvla_ctx* ctx) { return ctx ? ctx->lay.pl.G : 0; }
+int32_t hvla_num_layer_tokens(const hvla_ctx* ctx) { return ctx ? ctx->g.NL() : 0; }
 
 int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   if (!ctx) return HVLA_E_STATE;
@@ -270,6 +291,13 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   std::vector<uint16_t> hi, lo;
   std::vector<float> bc;
   pack::pack_wcat(ctx->lay, h.leaves, h.lk, h.lb, g.C, hi, lo, bc);
+  pack::TokenSegments segs;
+  if (g.layer_tokens) {      // one fragment block per (tile, token) segment instead of one per tile (pack.h)
+    segs = pack::build_segments(g, ctx->lay, h.leaves);
+    std::vector<uint16_t> shi, slo;
+    pack::pack_segments(segs, g.C, hi, lo, shi, slo);
+    hi.swap(shi); lo.swap(slo);
+  }
 
   // ---- upload
   auto up = [&](DevBuf& b, const void* src, size_t bytes) {
@@ -280,6 +308,10 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   HIPCHK(ctx, up(ctx->wcat_hi, hi.data(), hi.size() * 2));
   HIPCHK(ctx, up(ctx->wcat_lo, lo.data(), lo.size() * 2));
   HIPCHK(ctx, up(ctx->bcat, bc.data(), bc.size() * 4));
+  if (g.layer_tokens) {
+    HIPCHK(ctx, up(ctx->seg_token, segs.token.data(), segs.token.size() * 4));
+    HIPCHK(ctx, up(ctx->tile_segs, segs.tile_segs.data(), segs.tile_segs.size() * 4));
+  }
   HIPCHK(ctx, up(ctx->enc16, h.enc16.data(), h.enc16.size() * 2));
   HIPCHK(ctx, up(ctx->encd16, h.encd16.data(), h.encd16.size() * 2));
   HIPCHK(ctx, up(ctx->encf32, h.encf.data(), h.encf.size() * 4));
@@ -370,12 +402,12 @@ static int take_arena(hvla_ctx* ctx, int32_t B, std::unique_ptr<hvla_weights>& w
   }
   w.reset(new hvla_weights);
   w->B = B;
-  w->Gm = pl.Gm; w->Gv = pl.Gv; w->C = g.C;
+  w->Gm = pl.Gm; w->Gv = pl.Gv; w->C = g.ctx_row();
   hipError_t e = hipSuccess;
   auto A = [&](DevBuf& b, size_t n) { if (e == hipSuccess) e = b.alloc(n); };
   auto all = [&]() {
     A(w->wh, (size_t)B * pl.Gm * 2); A(w->wl, (size_t)B * pl.Gm * 2); A(w->vf, (size_t)B * pl.Gv * 4);
-    A(w->ctx, (size_t)B * g.C * 4);
+    A(w->ctx, (size_t)B * g.ctx_row() * 4);
     A(w->ring, (size_t)g.horizon * B * g.horizon * g.action_dim * 4); A(w->count, 16); A(w->slot_count, (size_t)B * 4);
   };
   all();
@@ -415,13 +447,18 @@ static int generate_body(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, i
   CtxParams cp = ctx->ctxp;
   cp.tok = tok; cp.attn_mask = mask; cp.cls = cls;
   cp.ctx = slots ? ctx->ctx_f32.as<float>() : w->ctx.as<float>(); cp.ctx_hi = ctx->ctx_hi.as<__bf16>(); cp.ctx_lo = ctx->ctx_lo.as<__bf16>();
-  HIPCHK(ctx, launch_ctx_encoder(cp, K, st));
+  HIPCHK(ctx, launch_ctx_encoder(cp, K, st, g.layer_tokens ? g.NL() : 0));
   WeightGenParams wp{ctx->wcat_hi.as<__bf16>(), ctx->wcat_lo.as<__bf16>(), ctx->bcat.as<float>(),
                      ctx->ctx_hi.as<__bf16>(), ctx->ctx_lo.as<__bf16>(), w->wh.as<__bf16>(), w->wl.as<__bf16>(),
                      w->vf.as<float>(), K, pl.Gm, pl.Gv, (pl.Gm + pl.Gv) / 32};
-  HIPCHK(ctx, launch_weightgen(wp, g.C, st, slots, w->B));
+  if (g.layer_tokens) {
+    const WeightGenTokensParams tp{wp, ctx->seg_token.as<int32_t>(), ctx->tile_segs.as<int32_t>()};
+    HIPCHK(ctx, launch_weightgen_tokens(tp, g.C, st, slots, w->B));
+  } else {
+    HIPCHK(ctx, launch_weightgen(wp, g.C, st, slots, w->B));
+  }
   if (slots)
-    HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.C, w->B, st));
+    HIPCHK(ctx, launch_pool_assign(ctx->ctx_f32.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), slots, K, g.ctx_row(), w->B, st));
   return lang_prefix(ctx, w, tok, K, slots, st);
 }
 
@@ -473,7 +510,7 @@ int hvla_weights_export(hvla_ctx* ctx, const hvla_weights* w, float* theta, floa
     HIPCHK(ctx, launch_export_theta(w->wh.as<__bf16>(), w->wl.as<__bf16>(), w->vf.as<float>(), ctx->perm.as<int32_t>(),
                                     pl.Gm, pl.Gv, pl.G, w->B, theta, st));
   if (context)
-    HIPCHK(ctx, hipMemcpyAsync(context, w->ctx.p, (size_t)w->B * ctx->g.C * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(ctx, hipMemcpyAsync(context, w->ctx.p, (size_t)w->B * ctx->g.ctx_row() * 4, hipMemcpyDeviceToDevice, st));
   return HVLA_OK;
 }
 
@@ -663,9 +700,9 @@ static ServeCount arena_batch_of(int32_t B) { return {ServeCount::BATCH, false, 
 // rows are written whole, so the arena must have this context's row sizes (an arena of another context with the same geometry is fine)
 static int arena_fits(hvla_ctx* ctx, const hvla_weights* w, const char* what) {
   const PolicyLayout& pl = ctx->lay.pl;
-  if (w->Gm != pl.Gm || w->Gv != pl.Gv || w->C != ctx->g.C)
+  if (w->Gm != pl.Gm || w->Gv != pl.Gv || w->C != ctx->g.ctx_row())
     FAIL(ctx, HVLA_E_SHAPE, "the %s arena belongs to another geometry (rows of %d + %d weights and %d context floats, this context's have %d + %d and %d)",
-         what, w->Gm, w->Gv, w->C, pl.Gm, pl.Gv, ctx->g.C);
+         what, w->Gm, w->Gv, w->C, pl.Gm, pl.Gv, ctx->g.ctx_row());
   return HVLA_OK;
 }
 
@@ -685,7 +722,7 @@ static int import_body(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int
   const PolicyLayout& pl = ctx->lay.pl;
   ++ctx->prof.nlaunch;
   HIPCHK(ctx, launch_import_theta(theta, context, ctx->perm.as<int32_t>(), slots, w->wh.as<__bf16>(), w->wl.as<__bf16>(),
-                                  w->vf.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), pl.Gm, pl.Gv, pl.G, ctx->g.C, K, w->B,
+                                  w->vf.as<float>(), w->ctx.as<float>(), w->slot_count.as<int>(), pl.Gm, pl.Gv, pl.G, ctx->g.ctx_row(), K, w->B,
                                   st));
   return lang_prefix(ctx, w, tok, K, slots, st);
 }

@@ -14,6 +14,8 @@
 //                       straight into the policy kernel's arena layout (layout.h).  HBM-bound:
 //                       reads W_cat once (hi+lo planes), writes the arena once; the ctx tiles reach the
 //                       four waves of a workgroup through LDS (LDS-DMA, one tile ahead).
+//   ctx_encoder_kernel_tokens / weightgen_tokens_kernel   share_layer_index=False: NL layer tokens in the sequence, and a
+//                       product whose A row depends on the output position (a sum over the tile's token segments).
 //   export_theta_kernel arena -> reference-order theta[B, G] (parity tests / `base_params` views).
 #include "common.h"
 #include "kernels.h"
@@ -27,7 +29,7 @@ namespace hvla {
 // waves of that one workgroup have to hide each other's latencies
 static_assert(CTX_THREADS == 1024, "ctx_encoder_kernel is written for 16 waves");
 constexpr int CTX_WAVES = CTX_THREADS / 64;
-constexpr int CTX_RG = 20;   // S <= 2 * CTX_RG = 40 rows: three 16-row MFMA tiles at most
+static_assert(CTX_MAX_ROWS == 48, "Acc3 and the attention block hold three 16-row MFMA tiles");
 
 // y[s][n] = sum_k xs[s][k] * W[k][n]   for s in [0,S), n in [0,N); xs in LDS (row stride xs_ld, == 4 mod 64 words so that
 // the 16 rows x 4 k of one A operand fall in 64 different banks), W global [K][N] (flax kernel layout), result handed to
@@ -373,6 +375,197 @@ __global__ __launch_bounds__(CTX_THREADS) void ctx_encoder_kernel(CtxParams p) {
   }
 }
 
+// share_layer_index=False: ctx_encoder_kernel with NL layer tokens behind the image token instead of one.  The same phases
+// on the same device helpers (they work for any S <= 48); what differs: S = T + 1 + NL, rows T + 1 .. S - 1 start as the NL rows of
+// layer_pos_embedding, a layer key is attended by the layer queries alone and token 0 -- the shared image encoder's, layer_token_mask[0]
+// = False (model.py:418-422) -- by nobody (hypernetwork.py:170-178), and all NL rows are normalised, scaled and published: ctx f32
+// [B][NL][C], the bf16 planes token-major [NL][B][C] so that one token's rows of 32 consecutive episodes are contiguous.
+// ctx_encoder_kernel itself is left as it is: its register allocation moves with any change to its text.
+__global__ __launch_bounds__(CTX_THREADS) void ctx_encoder_kernel_tokens(CtxTokensParams q) {
+  const CtxParams& p = q.enc;
+  const int NL = q.NL;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int b = blockIdx.x;
+  const int T = p.T, S = p.T + 1 + NL, C = p.C, F = p.F, Hc = p.heads, hc = C / Hc;
+  const int ldx = C + 4, ldq = 3 * C + 4, ldf = F + 4;
+  float* x = reinterpret_cast<float*>(smem);            // [S][ldx] residual stream
+  float* h = x + S * ldx;                                // [S][ldx] LN output / attention output
+  float* big = h + S * ldx;                              // [S][max(ldq, ldf)] qkv or mlp hidden
+  // ---- token projection: x[s] = tok[s] @ Wt + bt + pos_t[s]     (hypernetwork.py:112-115)
+  {
+    const float* tok = p.tok + (size_t)b * T * p.lang_dim;
+    // the token rows go through `big` in K-chunks (row stride == 4 mod 64 words); every wave keeps its tile's sums over the chunks
+    const int kc = T * 388 <= p.big_elems ? 384 : 128, ldt = kc + 4;
+    const int wave = threadIdx.x >> 6, ntc = C >> 4;
+    const bool split = ntc * 2 <= CTX_WAVES && (p.lang_dim & 7) == 0;
+    const int tc = wave % ntc, kh = split ? (wave < 2 * ntc ? wave / ntc : -1) : (wave < ntc ? 0 : -1);
+    Acc3 acc;
+    acc3_zero(acc);
+    for (int k0 = 0; k0 < p.lang_dim; k0 += kc) {
+      const int kw = min(kc, p.lang_dim - k0);
+      __syncthreads();
+      for (int i = threadIdx.x; i < T * (kw >> 2); i += CTX_THREADS) {
+        const int s = i / (kw >> 2), k = (i % (kw >> 2)) * 4;
+        *reinterpret_cast<f32x4*>(big + s * ldt + k) = *reinterpret_cast<const f32x4*>(tok + (size_t)s * p.lang_dim + k0 + k);
+      }
+      __syncthreads();
+      const int klen = split ? kw >> 1 : kw;
+      if (kh >= 0) mfma_cols(big, ldt, T, kh * klen, p.w_tok + (size_t)(k0 + kh * klen) * C, C, tc, klen, acc);
+    }
+    auto put = [&](int row, int n, float v) { x[row * ldx + n] = v + p.b_tok[n] + p.pos_tok[row * C + n]; };
+    if (split) acc3_combine(acc, T, tc, kh, h, ldx, put);
+    else if (kh == 0) acc3_rows(acc, T, tc, put);
+    __syncthreads();
+    // ---- initial-image CLS projection (hypernetwork.py:118-128) and layer token (:144-145): the E products of a column are
+    // summed in CTX_THREADS / C parts, then the parts in order
+    const float* cls = p.cls + (size_t)b * p.E;
+    float* parts = big + p.E;
+    for (int i = threadIdx.x; i < p.E; i += CTX_THREADS) big[i] = cls[i];
+    __syncthreads();
+    {
+      const int np = CTX_THREADS / C, kper = (p.E + np - 1) / np;
+      const int c = threadIdx.x % C, pi = threadIdx.x / C;
+      const int kb = pi * kper, ke = min(p.E, kb + kper);
+      float a = 0.f;
+#pragma unroll 8
+      for (int k = kb; k < ke; ++k) a = fmaf(big[k], p.w_img[(size_t)k * C + c], a);
+      parts[pi * C + c] = a;
+      __syncthreads();
+      if (threadIdx.x < C) {
+        float t = 0.f;
+        for (int i = 0; i < np; ++i) t += parts[i * C + c];
+        x[T * ldx + c] = t + p.b_img[c] + p.pos_img[c];
+        for (int j = 0; j < NL; ++j) x[(T + 1 + j) * ldx + c] = p.pos_layer[j * C + c];
+      }
+    }
+    __syncthreads();
+  }
+  int* kmask = reinterpret_cast<int*>(big + p.big_elems);          // [T] language-token mask (read in the first layer after several barriers)
+  for (int k = threadIdx.x; k < T; k += CTX_THREADS) kmask[k] = p.attn_mask[(size_t)b * T + k] != 0;
+  // ---- context Transformer (transformer.py:127-262)
+  for (int l = 0; l < p.layers; ++l) {
+    const CtxLayer& w = p.layer[l];
+    ln_rows(x, h, ldx, S, C, w.ln0_s, w.ln0_b);
+    __syncthreads();
+    // q | k | v = h @ W{q,k,v} + b    (flax DenseGeneral kernel [C, H, hd] == [C, C] row-major)
+    for (int task = threadIdx.x >> 6; task < 3 * (C >> 4); task += CTX_WAVES) {     // 24 column tiles over 16 waves: 6 per SIMD
+      const int which = task / (C >> 4), tc = task % (C >> 4);
+      const float* W = which == 0 ? w.wq : which == 1 ? w.wk : w.wv;
+      const float* B = which == 0 ? w.bq : which == 1 ? w.bk : w.bv;
+      const float sc = which == 0 ? rsqrtf((float)hc) : 1.f;     // query pre-scaling
+      Acc3 acc;
+      acc3_zero(acc);
+      const float bn = B[tc * 16 + (lane_here() & 15)];
+      mfma_cols(h, ldx, S, 0, W, C, tc, C, acc);
+      acc3_rows(acc, S, tc, [&](int s, int n, float v) { big[s * ldq + which * C + n] = (v + bn) * sc; });
+    }
+    __syncthreads();
+    // attention on the matrix cores, transposed: one wave per (head, 16-query tile).  S^T = K Q^T leaves lane (query = l & 15,
+    // kq = l >> 4) with the logits of keys 16 kt + 4 kq + r of its query -- exactly the B operand P^T[key slot][query] that
+    // O^T = V^T P^T wants when MFMA k slot kq of step (kt, r) is read as key 16 kt + 4 kq + r, so the probabilities never leave
+    // their registers; the softmax reduces in-lane and over the four lanes of a query (xor 16, 32).
+    {
+      const int nqt = (S + 15) >> 4;
+      for (int task = threadIdx.x >> 6; task < Hc * nqt; task += CTX_WAVES) {
+        const int hh = task / nqt, qt = task % nqt;
+        const int lane = lane_here(), j = lane & 15, kq = lane >> 4;
+        const int q = qt * 16 + j, qr = q < S ? q : S - 1;
+        const float* qp = big + qr * ldq + hh * hc + kq;
+        f32x4 sc[3];
+#pragma unroll
+        for (int kt = 0; kt < 3; ++kt) {
+          sc[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (kt < nqt) {
+            const int kr = kt * 16 + j < S ? kt * 16 + j : S - 1;
+            const float* kp = big + kr * ldq + C + hh * hc + kq;
+            for (int d = 0; d < hc; d += 4) sc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(kp[d], qp[d], sc[kt], 0, 0, 0);
+          }
+        }
+        float mx = -3.4028234663852886e38f;        // finfo(float32).min stands in for a masked logit (transformer.py)
+#pragma unroll
+        for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = kt * 16 + 4 * kq + r;
+            const bool layer_key = q > T && key != T + 1;      // (a clamped query row past S is never stored)
+            const bool keep = key < S && (key < T ? kmask[key] != 0 : (key == T ? true : layer_key));
+            sc[kt][r] = keep ? sc[kt][r] : -3.4028234663852886e38f;
+            mx = fmaxf(mx, sc[kt][r]);
+          }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float den = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int key = kt * 16 + 4 * kq + r;
+            const float e = key < S ? __expf(sc[kt][r] - mx) : 0.f;     // a masked key of the sequence gives exp(min - mx) = 0
+            sc[kt][r] = e;
+            den += e;
+          }
+        den += __shfl_xor(den, 16, 64);
+        den += __shfl_xor(den, 32, 64);
+        const float inv = 1.f / den;
+        for (int dt = 0; dt * 16 < hc; ++dt) {
+          const int dd = dt * 16 + j < hc ? dt * 16 + j : hc - 1;
+          const float* vp = big + 2 * C + hh * hc + dd;
+          f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (kt * 16 + r < S) {                 // uniform: the step's smallest key (kq = 0)
+                const int key = kt * 16 + 4 * kq + r < S ? kt * 16 + 4 * kq + r : S - 1;     // past the end: probability 0 times a real row
+                o = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[key * ldq], sc[kt][r], o, 0, 0, 0);
+              }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int d = dt * 16 + 4 * kq + r;
+            if (d < hc && q < S) h[q * ldx + hh * hc + d] = o[r] * inv;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // out projection + residual   (kernel [H, hd, C] == [C, C] row-major)
+    dense_mfma(h, ldx, S, C, w.wo, C, w.bo, big, ldq, [&](int s, int n, float v) { x[s * ldx + n] += v; });     // q|k|v are dead: `big` takes the partial sums
+    __syncthreads();
+    ln_rows(x, h, ldx, S, C, w.ln1_s, w.ln1_b);
+    __syncthreads();
+    dense_mfma(h, ldx, S, C, w.w1, F, w.b1, nullptr, 0, [&](int s, int n, float v) { big[s * ldf + n] = gelu_tanh(v); });
+    __syncthreads();
+    dense_mfma(big, ldf, S, F, w.w2, C, w.b2, h, ldx, [&](int s, int n, float v) { x[s * ldx + n] += v; });      // h (LN output) is dead
+    __syncthreads();
+  }
+  // ---- encoder_norm on the last NL rows, scale, publish (hypernetwork.py:188-192): one wave per row
+  for (int j = threadIdx.x >> 6; j < NL; j += CTX_WAVES) {
+    const int lane = threadIdx.x & 63;
+    const float* xr = x + (T + 1 + j) * ldx;
+    const size_t of = ((size_t)b * NL + j) * C, o16 = ((size_t)j * gridDim.x + b) * C;
+    float sum = 0.f, sq = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      sum += xr[c];
+      sq += xr[c] * xr[c];
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      sum += __shfl_xor(sum, o, 64);
+      sq += __shfl_xor(sq, o, 64);
+    }
+    const float mean = sum / C, var = fmaxf(0.f, sq / C - mean * mean), rstd = rsqrtf(var + 1e-6f);
+    const float post = p.scale_context ? rsqrtf((float)C) : 1.f;
+    for (int c = lane; c < C; c += 64) {
+      const float v = ((xr[c] - mean) * rstd * p.norm_s[c] + p.norm_b[c]) * post;
+      p.ctx[of + c] = v;
+      __bf16 hi, lo;
+      split1(v, hi, lo);
+      p.ctx_hi[o16 + c] = hi;
+      p.ctx_lo[o16 + c] = lo;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // weight generation GEMM
 // ------------------------------------------------------------------------------------------------
@@ -537,6 +730,133 @@ __global__ __launch_bounds__(256, 3) void weightgen_slots_kernel(WeightGenParams
   weightgen_body<KS, true>(p, slot, rows);
 }
 
+// share_layer_index=False: the A row of a position is the context row of its leaf's layer token, so a tile's product is a
+// sum over its SEGMENTS (pack.h TokenSegments): per segment one fragment block of W_cat^T in which the rows of positions of another
+// token are zero, times that token's context rows.  Zero rows add exact zeros: a position's value is the same split-bf16 sum (lo . hi
+// + hi . lo + hi . hi, ascending k-steps, from the bias) it would be if its tile had one token.  A wave owns a tile, as above; the
+// first segment's fragments stay in registers over the episode loop (nearly every tile has one segment), a further segment's are read
+// per episode tile.  The B fragments come per wave from the token-major planes [NL][B][C] (at most NL B C 4 bytes, L2-resident): no
+// staging, so the only LDS is the store stage and its two barriers.  Stores are weightgen_body's, condition for condition.
+template <int KS, bool SLOTS>
+__device__ __forceinline__ void weightgen_tokens_body(WeightGenTokensParams q, const int32_t* __restrict__ slot, int rows) {
+  const WeightGenParams& p = q.gen;
+  constexpr int C = KS * 16;
+  __shared__ __attribute__((aligned(16))) __bf16 stage[2][32][128];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int wg = blockIdx.x;
+  const bool active = wg * 4 + wave < p.ntiles;      // a ragged last workgroup: its spare waves still go to the barriers
+  const int tile = active ? wg * 4 + wave : p.ntiles - 1;
+  const bool via_lds = wg * 4 + 3 < p.ntiles && (wg * 4 + 4) * 32 <= p.Gm;     // workgroup-uniform
+  const int col = lane & 31, half = lane >> 5;
+  const int seg0 = __builtin_amdgcn_readfirstlane(q.tile_segs[2 * tile]), nseg = __builtin_amdgcn_readfirstlane(q.tile_segs[2 * tile + 1]);
+  const bf16x8* Ah = reinterpret_cast<const bf16x8*>(p.wcat_hi) + lane;      // block s at (s KS + ks) 64
+  const bf16x8* Al = reinterpret_cast<const bf16x8*>(p.wcat_lo) + lane;
+  bf16x8 ah[KS], al[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    ah[ks] = nseg > 0 ? __builtin_nontemporal_load(Ah + ((size_t)seg0 * KS + ks) * 64) : bf16x8{};
+    al[ks] = nseg > 0 ? __builtin_nontemporal_load(Al + ((size_t)seg0 * KS + ks) * 64) : bf16x8{};
+  }
+  const int tok0 = nseg > 0 ? __builtin_amdgcn_readfirstlane(q.seg_token[seg0]) : 0;
+  const int pos0 = tile * 32 + half * 16;
+  float bias[16];
+#pragma unroll
+  for (int r = 0; r < 16; r += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(p.bcat + pos0 + r);
+    bias[r] = v[0], bias[r + 1] = v[1], bias[r + 2] = v[2], bias[r + 3] = v[3];
+  }
+  for (int b0 = 0; b0 < p.B; b0 += 32) {
+    const int b = b0 + col;
+    const int br = b < p.B ? b : p.B - 1;            // a ragged tile's spare columns read the last episode and store nothing
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = bias[r];
+    {
+      const size_t o = ((size_t)tok0 * p.B + br) * C + half * 8;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(p.ctx_hi + o + ks * 16), bl = *reinterpret_cast<const bf16x8*>(p.ctx_lo + o + ks * 16);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks], bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bh, acc, 0, 0, 0);
+      }
+    }
+    for (int s = 1; s < nseg; ++s) {
+      const int tok = __builtin_amdgcn_readfirstlane(q.seg_token[seg0 + s]);
+      const size_t o = ((size_t)tok * p.B + br) * C + half * 8;
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const bf16x8 sh = Ah[((size_t)(seg0 + s) * KS + ks) * 64], sl = Al[((size_t)(seg0 + s) * KS + ks) * 64];
+        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(p.ctx_hi + o + ks * 16), bl = *reinterpret_cast<const bf16x8*>(p.ctx_lo + o + ks * 16);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sl, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sh, bh, acc, 0, 0, 0);
+      }
+    }
+    if (via_lds) {
+      bf16x8 h0, h1, l0, l1;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        __bf16 hi, lo;
+        split1(acc[j], hi, lo);
+        h0[j] = hi, l0[j] = lo;
+        split1(acc[8 + j], hi, lo);
+        h1[j] = hi, l1[j] = lo;
+      }
+      __syncthreads();                           // the previous episode tile's rows have been read
+      const int c0 = wave * 4 + half * 2, sx = col & 15;     // (the chunk index XORed with the row on both sides: weightgen_body)
+      *reinterpret_cast<bf16x8*>(&stage[0][col][((c0 + 0) ^ sx) * 8]) = h0;
+      *reinterpret_cast<bf16x8*>(&stage[0][col][((c0 + 1) ^ sx) * 8]) = h1;
+      *reinterpret_cast<bf16x8*>(&stage[1][col][((c0 + 0) ^ sx) * 8]) = l0;
+      *reinterpret_cast<bf16x8*>(&stage[1][col][((c0 + 1) ^ sx) * 8]) = l1;
+      __syncthreads();
+      const size_t gpos = (size_t)wg * 128 + (lane & 15) * 8;          // 16 lanes x 16 B = one episode's 256-byte run
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int row = wave * 8 + u * 4 + (lane >> 4);
+        const int orow = !SLOTS ? b0 + row : b0 + row < p.B ? slot[b0 + row] : -1;     // arena row of this episode
+        if (b0 + row < p.B && (!SLOTS || (orow >= 0 && orow < rows))) {
+          const bf16x8 vh = *reinterpret_cast<const bf16x8*>(&stage[0][row][((lane & 15) ^ (row & 15)) * 8]);
+          const bf16x8 vl = *reinterpret_cast<const bf16x8*>(&stage[1][row][((lane & 15) ^ (row & 15)) * 8]);
+          *reinterpret_cast<bf16x8*>(p.wh + (size_t)orow * p.Gm + gpos) = vh;
+          *reinterpret_cast<bf16x8*>(p.wl + (size_t)orow * p.Gm + gpos) = vl;
+        }
+      }
+    } else {
+      const int ob = !SLOTS ? b : b < p.B ? slot[b] : -1;      // arena row of this lane's episode
+      if (active && b < p.B && (!SLOTS || (ob >= 0 && ob < rows))) {
+        if (pos0 < p.Gm) {
+          bf16x8 h0, h1, l0, l1;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            __bf16 hi, lo;
+            split1(acc[j], hi, lo);
+            h0[j] = hi, l0[j] = lo;
+            split1(acc[8 + j], hi, lo);
+            h1[j] = hi, l1[j] = lo;
+          }
+          bf16x8* dh = reinterpret_cast<bf16x8*>(p.wh + (size_t)ob * p.Gm + pos0);
+          bf16x8* dl = reinterpret_cast<bf16x8*>(p.wl + (size_t)ob * p.Gm + pos0);
+          dh[0] = h0, dh[1] = h1, dl[0] = l0, dl[1] = l1;
+        } else {
+          f32x4* dv = reinterpret_cast<f32x4*>(p.vf + (size_t)ob * p.Gv + (pos0 - p.Gm));
+#pragma unroll
+          for (int r = 0; r < 16; r += 4) dv[r >> 2] = f32x4{acc[r], acc[r + 1], acc[r + 2], acc[r + 3]};
+        }
+      }
+    }
+  }
+}
+
+template <int KS>
+__global__ __launch_bounds__(256, 2) void weightgen_tokens_kernel(WeightGenTokensParams q) {
+  weightgen_tokens_body<KS, false>(q, nullptr, 0);
+}
+template <int KS>
+__global__ __launch_bounds__(256, 2) void weightgen_tokens_slots_kernel(WeightGenTokensParams q, const int32_t* __restrict__ slot, int rows) {
+  weightgen_tokens_body<KS, true>(q, slot, rows);
+}
+
 // episode pool: the f32 context rows of K new tasks (workspace rows 0 .. K-1) into arena rows slot[k], and those rows' temporal-
 // ensemble counters to zero.  One thread per (task, column); entries outside [0, rows) touch nothing.
 __global__ void pool_assign_kernel(const float* __restrict__ src, float* __restrict__ ctx, int* __restrict__ count,
@@ -572,10 +892,12 @@ hipError_t debug_ctx_stamps(unsigned long long* out) { return hipMemcpyFromSymbo
 // ---- launchers -----------------------------------------------------------------------------------
 // (the LDS the context encoder needs for a geometry: ctx_big_elems / ctx_encoder_lds_bytes of accept.h, by which hvla_create refuses
 // a configuration that does not fit instead of letting the first hvla_generate fail with a bare HIP error)
-hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st) {
+hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st, int NL) {
   CtxParams q = p;
-  q.big_elems = (int)ctx_big_elems(p.T, p.C, p.F, p.E);
-  const size_t smem = ctx_encoder_lds_bytes(p.T, p.C, p.F, p.E);      // x, h, big and the key mask
+  const bool tokens = NL > 0;                                  // share_layer_index=False: ctx_encoder_kernel_tokens, T + 1 + NL rows
+  if (tokens && p.T + 1 + NL > CTX_MAX_ROWS) return hipErrorInvalidValue;
+  q.big_elems = (int)ctx_big_elems(p.T, p.C, p.F, p.E, tokens ? NL - 1 : 0);
+  const size_t smem = ctx_encoder_lds_bytes(p.T, p.C, p.F, p.E, tokens ? NL - 1 : 0);      // x, h, big and the key mask
   static bool attr_done[64] = {};                              // per device: the attribute belongs to the device's code object
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
@@ -584,10 +906,13 @@ hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st) {
   if (!attr_done[dev]) {
     e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctx_encoder_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctx_encoder_kernel_tokens), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
     attr_done[dev] = true;
   }
   if (smem > LDS_LIMIT) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ctx_encoder_kernel, dim3(B), dim3(CTX_THREADS), smem, st, q);
+  if (tokens) hipLaunchKernelGGL(ctx_encoder_kernel_tokens, dim3(B), dim3(CTX_THREADS), smem, st, CtxTokensParams{q, NL});
+  else hipLaunchKernelGGL(ctx_encoder_kernel, dim3(B), dim3(CTX_THREADS), smem, st, q);
   return hipGetLastError();
 }
 
@@ -605,6 +930,22 @@ hipError_t launch_weightgen(const WeightGenParams& p, int C, hipStream_t st, con
     hipLaunchKernelGGL(pooled[k], dim3(blocks), dim3(256), 0, st, p, slot, rows);
   else
     hipLaunchKernelGGL(plain[k], dim3(blocks), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
+
+// share_layer_index=False: weightgen_tokens_kernel / its _slots form over q.gen.ntiles tiles; q.gen.ctx_hi / ctx_lo are the token-major
+// planes [NL][q.gen.B][C] the context kernel of the same batch wrote, q.gen.wcat_hi / wcat_lo the segments' fragment blocks
+hipError_t launch_weightgen_tokens(const WeightGenTokensParams& q, int C, hipStream_t st, const int32_t* slot, int rows) {
+  static void (*const plain[3])(WeightGenTokensParams) = {weightgen_tokens_kernel<8>, weightgen_tokens_kernel<4>, weightgen_tokens_kernel<2>};
+  static void (*const pooled[3])(WeightGenTokensParams, const int32_t*, int) = {
+      weightgen_tokens_slots_kernel<8>, weightgen_tokens_slots_kernel<4>, weightgen_tokens_slots_kernel<2>};
+  const int k = C == 128 ? 0 : C == 64 ? 1 : C == 32 ? 2 : -1;
+  if (k < 0) return hipErrorInvalidValue;
+  const int blocks = (q.gen.ntiles + 3) / 4;
+  if (slot)
+    hipLaunchKernelGGL(pooled[k], dim3(blocks), dim3(256), 0, st, q, slot, rows);
+  else
+    hipLaunchKernelGGL(plain[k], dim3(blocks), dim3(256), 0, st, q);
   return hipGetLastError();
 }
 

@@ -26,6 +26,12 @@ struct CtxParams {
   float* ctx;                // [B, C]
   __bf16 *ctx_hi, *ctx_lo;   // [B, C]
 };
+// share_layer_index=False (ctx_encoder_kernel_tokens): NL layer tokens, T + 1 + NL <= CTX_MAX_ROWS rows; of `enc`, pos_layer is then
+// [NL, C], ctx [B, NL, C] and ctx_hi / ctx_lo token-major [NL, B, C].  (A struct of its own: ctx_encoder_kernel's arguments stay as they are.)
+struct CtxTokensParams {
+  CtxParams enc;
+  int NL;
+};
 struct WeightGenParams {
   const __bf16 *wcat_hi, *wcat_lo;   // [ntiles][KS][64 lanes][8]
   const float* bcat;                 // [Gm + Gv]
@@ -34,7 +40,15 @@ struct WeightGenParams {
   float* vf;                         // [B, Gv]
   int B, Gm, Gv, ntiles;
 };
-hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st);
+// share_layer_index=False (pack.h TokenSegments): gen.wcat_hi / wcat_lo are the segments' fragment blocks [nseg][KS][64 lanes][8],
+// gen.ctx_hi / ctx_lo the token-major planes [NL][B][C]
+struct WeightGenTokensParams {
+  WeightGenParams gen;
+  const int32_t* seg_token;          // [nseg] the layer token of a segment
+  const int32_t* tile_segs;          // [ntiles][2] first segment, count
+};
+hipError_t launch_ctx_encoder(const CtxParams& p, int B, hipStream_t st, int NL = 0);     // NL > 0: ctx_encoder_kernel_tokens
+hipError_t launch_weightgen_tokens(const WeightGenTokensParams& q, int C, hipStream_t st, const int32_t* slot = nullptr, int rows = 0);
 // (ctx_encoder_lds_bytes, the dynamic LDS of ctx_encoder_kernel for a geometry -- <= 160 KiB or refused at create -- is accept.h's)
 // episode pool, `slot` not null: weightgen_kernel's output row of input episode r is arena row slot[r] of an arena of
 // `rows`; launch_pool_assign puts the K new context rows (f32 workspace rows 0 .. K-1) at arena rows slot[k] and zeroes those rows'

@@ -2,7 +2,8 @@
 // the map back to the reference's pytree order (hypervla/model.py:370-515).
 //
 // The hypernetwork's 73 output heads are one GEMM  theta[B, G] = ctx[B, C] @ W_cat[C, G] + b_cat
-// (share_layer_index=True => every head reads context token 0, hypernetwork.py:205-217).  Because
+// (share_layer_index=True => every head reads context token 0, hypernetwork.py:205-217; with share_layer_index=False the A row of
+// a position is the context row of its leaf's layer token, pack.h's segment list).  Because
 // the columns of W_cat can be permuted freely at load time, the GEMM writes each parameter straight
 // to the place the policy kernel reads it from:
 //
@@ -41,6 +42,14 @@ struct Geom {
   int differential = 0;      // vit_kwargs.use_differential_transformer (transformer.py:166-171, differential_transformer.py:99-252): the blocks'
                              // attention is DifferentialAttention_0 -- two softmaxes over the halves of each head's q / k, A1 - lambda A2,
                              // an RMSNorm per head; no q / k / v / out bias.  Not with either flag above
+  int layer_tokens = 0;      // hypernet_kwargs.share_layer_index=False (model.py:400-436): NL() layer tokens in the context encoder, every generated
+                             // leaf reads the token of its module (layer_token_of, below).  Served, not fine-tuned
+  int shared_block_heads = 0;   // hypernet_kwargs.share_TF_output_head (hypernetwork.py:221-225): one output head per leaf name for all policy
+                             // blocks; only with layer_tokens
+  // rows of layer_pos_embedding and of the context embedding: the shared image encoder, encoder_norm, L blocks, the image projection,
+  // (the language projection,) the position table and the action head -- or the one token every head reads
+  int NL() const { return layer_tokens ? L + 5 + (lang_in_policy ? 1 : 0) : 1; }
+  int ctx_row() const { return NL() * C; }     // floats of one episode's context wherever it is carried
   const char* attention_name() const {
     return differential ? "DifferentialAttention_0_" : (mask_as_bias ? "CustomMultiHeadDotProductAttention_0_" : "MultiHeadDotProductAttention_0_");
   }
@@ -122,6 +131,41 @@ inline std::vector<LeafInfo> generated_leaves(const Geom& g) {
   }
   add("encoder_pos_embedding", {1, g.pos_rows(), D});
   return v;
+}
+
+// share_layer_index=False: the layer token a generated leaf reads (model.py:418-436, restated in hypervla.config.layer_token_modules,
+// which tests/test_layer_tokens_host.py holds this function to).  Token 0 is the shared image encoder (never returned); then the
+// modules of encoder/Transformer_0 in the key-sorted order jax.tree_map rebuilds a dict in -- "encoder_norm", then "encoderblock_<l>"
+// as STRINGS, so encoderblock_10 precedes encoderblock_2 --, then image_embedding_projection, (language_token_projection,)
+// pos_embedding, and action_head last.  -1: no leaf of this geometry.
+inline int layer_token_of(const Geom& g, const std::string& flat) {
+  auto starts = [&](const std::string& p) { return flat.compare(0, p.size(), p) == 0; };
+  const std::string T = "encoder_Transformer_0_";
+  if (starts("action_head_")) return g.NL() - 1;
+  if (starts(T + "encoder_norm_")) return 1;
+  if (starts(T + "encoderblock_")) {
+    const size_t a = T.size() + 13, e = flat.find('_', a);
+    if (e == std::string::npos) return -1;
+    const std::string own = flat.substr(a, e - a);
+    int rank = 0, found = 0;
+    for (int l = 0; l < g.L; ++l) {
+      const std::string other = std::to_string(l);
+      if (other == own) found = 1;
+      else if (other < own) ++rank;
+    }
+    return found ? 2 + rank : -1;
+  }
+  if (starts("encoder_image_embedding_projection_")) return 2 + g.L;
+  if (g.lang_in_policy && starts("encoder_language_token_projection_")) return 3 + g.L;
+  if (starts("encoder_pos_embedding")) return 3 + g.L + (g.lang_in_policy ? 1 : 0);
+  return -1;
+}
+// share_TF_output_head: the output head of a leaf, "encoderblock_<l>" -> "encoderblock" (hypernetwork.py:221-225)
+inline std::string output_head_of(const Geom& g, const std::string& flat) {
+  const std::string B = "encoder_Transformer_0_encoderblock_";
+  if (!g.shared_block_heads || flat.compare(0, B.size(), B) != 0) return "output_head_" + flat;
+  const size_t e = flat.find('_', B.size());
+  return "output_head_" + B.substr(0, B.size() - 1) + (e == std::string::npos ? "" : flat.substr(e));
 }
 
 // Offsets the policy kernel uses (all in elements; frag offsets are multiples of 512).

@@ -148,6 +148,62 @@ inline void pack_wcat(const PackedLayout& lay, const std::vector<LeafInfo>& leav
     }
 }
 
+// share_layer_index=False: the A row of a packed position is the context row of its leaf's layer token (layout.h layer_token_of).
+// The arena order is the policy kernel's, so a 32-position tile may hold positions of several tokens -- the vector region packs
+// encoder_norm, the per-layer vectors, the head bias and the position table side by side.  A tile is therefore cut into SEGMENTS, one
+// per distinct token among its positions, in order of first appearance; a padding position (perm -1) has no token and a tile of
+// padding alone no segment.  Each segment has its own W_cat^T fragment block (hi and lo, [KS][64 lanes][8] as pack_wcat's) in which
+// the rows of positions of another token, or of padding, are zero: summed over a tile's segments, every position meets its own
+// column exactly once and exact zeros otherwise (hypernet.hip weightgen_tokens_body).
+struct TokenSegments {
+  std::vector<int32_t> token;         // [nseg] the layer token of segment s
+  std::vector<int32_t> tile;          // [nseg] its tile
+  std::vector<int32_t> tile_segs;     // [ntiles][2]: first segment, count
+  std::vector<int32_t> pos_token;     // [Gm + Gv] the token of every position, -1 for padding
+};
+inline TokenSegments build_segments(const Geom& g, const PackedLayout& lay, const std::vector<LeafInfo>& leaves) {
+  const PolicyLayout& pl = lay.pl;
+  const int Gtot = pl.Gm + pl.Gv, ntiles = Gtot / 32;
+  std::vector<int32_t> tok_of_ref(pl.G, -1);
+  for (const LeafInfo& l : leaves) {
+    const int t = layer_token_of(g, l.flat);
+    for (int64_t j = 0; j < l.size; ++j) tok_of_ref[l.offset + j] = t;
+  }
+  TokenSegments s;
+  s.pos_token.assign(Gtot, -1);
+  s.tile_segs.assign((size_t)ntiles * 2, 0);
+  for (int pos = 0; pos < Gtot; ++pos)
+    if (lay.perm[pos] >= 0) s.pos_token[pos] = tok_of_ref[lay.perm[pos]];
+  for (int pt = 0; pt < ntiles; ++pt) {
+    const int first = (int)s.token.size();
+    for (int i = 0; i < 32; ++i) {
+      const int t = s.pos_token[pt * 32 + i];
+      bool seen = t < 0;
+      for (int q = first; q < (int)s.token.size() && !seen; ++q) seen = s.token[q] == t;
+      if (!seen) { s.token.push_back(t); s.tile.push_back(pt); }
+    }
+    s.tile_segs[2 * pt] = first;
+    s.tile_segs[2 * pt + 1] = (int)s.token.size() - first;
+  }
+  return s;
+}
+// the segments' fragment blocks from pack_wcat's planes: block s is tile s.tile[s] with the lanes of other tokens' positions zeroed
+inline void pack_segments(const TokenSegments& s, int C, const std::vector<uint16_t>& hi, const std::vector<uint16_t>& lo,
+                          std::vector<uint16_t>& shi, std::vector<uint16_t>& slo) {
+  const int KS = C / 16;
+  shi.assign(s.token.size() * KS * 512, 0);
+  slo.assign(shi.size(), 0);
+  for (size_t q = 0; q < s.token.size(); ++q)
+    for (int lane = 0; lane < 64; ++lane) {
+      if (s.pos_token[s.tile[q] * 32 + tau_of_rho(lane & 31)] != s.token[q]) continue;
+      for (int ks = 0; ks < KS; ++ks) {
+        const size_t src = ((size_t)(s.tile[q] * KS + ks) * 64 + lane) * 8, dst = ((q * KS + ks) * 64 + lane) * 8;
+        memcpy(&shi[dst], &hi[src], 16);
+        memcpy(&slo[dst], &lo[src], 16);
+      }
+    }
+}
+
 // flax [K][N] -> [N][K] 16-bit, and the rounding residues for the per-image compensation of the encoder GEMMs (encoder.hip
 // corr_kernel)
 inline void pack_matrix_t(const float* src, int K, int N, bool bf, uint16_t* w16, uint16_t* d16) {

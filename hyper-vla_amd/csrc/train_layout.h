@@ -38,6 +38,7 @@ struct TrainLayout {
 // The first two answers are the default: hvla_train_differential(ctx, 1) / hvla_train_language_tokens(ctx, 1) lift them for that
 // context (train_entry, api.hip)
 inline const char* train_refusal(const Geom& g) {
+  if (g.layer_tokens) return "the training path does not build hypernet_kwargs.share_layer_index=False (one layer token per policy module): serving is";
   if (g.differential) return "the training path does not build use_differential_transformer (DifferentialAttention): serving is";
   if (g.lang_in_policy) return "the training path does not build use_language_token";
   if (g.ctx_layers > CTX_MAX_LAYERS || g.L > TRAIN_MAX_POLICY_LAYERS || g.enc_layers > ENC_MAX_LAYERS) return "too many layers for the training path";

@@ -28,7 +28,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_create_with", "hvla_create_with_v2", "hvla_create_with_v3", "hvla_train_publish", "hvla_position_interp", "hvla_position_interp_adjoint",
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
-           "hvla_loss_terms", "hvla_train_metrics", "hvla_train_noise_set", "hvla_train_noise_probe", "hvla_train_differential"]
+           "hvla_loss_terms", "hvla_train_metrics", "hvla_train_noise_set", "hvla_train_noise_probe", "hvla_train_differential",
+           "hvla_create_with_v4", "hvla_num_layer_tokens"]
 # hvla_train_metrics (include/hvla.h): select bits, the slots of its output vector, the size of its scratch
 HVLA_METRICS_PRE, HVLA_METRICS_UPDATE = 1, 2
 (HVLA_METRIC_TRAINING_LOSS, HVLA_METRIC_CONTINUOUS_LOSS, HVLA_METRIC_GRIPPER_LOSS, HVLA_METRIC_MSE, HVLA_METRIC_BASE_PARAMS_NORM,
@@ -69,6 +70,12 @@ class hvla_policy_options_v3(C.Structure):
     """hvla_policy_options_v2 with differential_attention, for hvla_create_with_v3 (include/hvla.h): struct_size must be its sizeof."""
     _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32), ("attention_mask_as_bias", C.c_int32),
                 ("differential_attention", C.c_int32)]
+
+
+class hvla_policy_options_v4(C.Structure):
+    """hvla_policy_options_v3 with layer_tokens and shared_block_heads, for hvla_create_with_v4 (include/hvla.h): struct_size must be its sizeof."""
+    _fields_ = [("struct_size", C.c_uint32), ("use_language_token", C.c_int32), ("attention_mask_as_bias", C.c_int32),
+                ("differential_attention", C.c_int32), ("layer_tokens", C.c_int32), ("shared_block_heads", C.c_int32)]
 
 
 class hvla_tensor_desc(C.Structure):
@@ -142,6 +149,10 @@ def load_library():
     lib.hvla_create_with_v2.restype = C.c_int
     lib.hvla_create_with_v3.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options_v3), C.c_int, C.POINTER(vp)]
     lib.hvla_create_with_v3.restype = C.c_int
+    lib.hvla_create_with_v4.argtypes = [C.POINTER(hvla_config), C.POINTER(hvla_policy_options_v4), C.c_int, C.POINTER(vp)]
+    lib.hvla_create_with_v4.restype = C.c_int
+    lib.hvla_num_layer_tokens.argtypes = [vp]
+    lib.hvla_num_layer_tokens.restype = i32
     lib.hvla_destroy.argtypes = [vp]
     lib.hvla_destroy.restype = None
     lib.hvla_last_error.argtypes = [vp]
@@ -284,7 +295,12 @@ class Context:
         self.geometry, self.device, self.max_batch, self.enc_dtype = g, device, max_batch, enc_dtype
         h = C.c_void_p()
         lang, mab = bool(getattr(g, "lang_in_policy", False)), bool(getattr(g, "mask_as_bias", False))
-        if bool(getattr(g, "differential", False)):   # use_differential_transformer: the newest options struct and its entry
+        diff = bool(getattr(g, "differential", False))
+        if bool(getattr(g, "layer_tokens", False)):   # share_layer_index=False: the newest options struct and its entry
+            self.options = hvla_policy_options_v4(C.sizeof(hvla_policy_options_v4), int(lang), int(mab), int(diff), 1,
+                                                  int(bool(getattr(g, "shared_block_heads", False))))
+            rc = self.lib.hvla_create_with_v4(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
+        elif diff:            # use_differential_transformer: the newest options struct and its entry
             self.options = hvla_policy_options_v3(C.sizeof(hvla_policy_options_v3), int(lang), int(mab), 1)
             rc = self.lib.hvla_create_with_v3(C.byref(self.cfg), C.byref(self.options), device, C.byref(h))
         elif mab:             # return_attention_map: the larger options struct has an entry of its own (both sizes are ABI)
@@ -321,6 +337,10 @@ class Context:
     @property
     def num_generated(self) -> int:
         return int(self.lib.hvla_num_generated(self.h))
+
+    @property
+    def num_layer_tokens(self) -> int:
+        return int(self.lib.hvla_num_layer_tokens(self.h))
 
     def load_weights(self, params: Dict[str, np.ndarray]):
         keep = []

@@ -12,6 +12,7 @@ the synthetic generators.
 from __future__ import annotations
 
 import copy
+import re
 from dataclasses import dataclass, field
 from typing import Dict, List, Tuple
 
@@ -59,8 +60,17 @@ class Geometry:
     # (differential_transformer.py:99-252): per head two softmaxes over the halves of q / k with the mask added to the unscaled scores,
     # (A1 - lambda A2) V, an RMSNorm over the head's values; bias-free projections.  Served, not fine-tuned
     differential: bool = False
+    # hypernet_kwargs.share_layer_index=False (model.py:400-436): the context encoder carries one layer token per module of the
+    # policy and every generated leaf reads the token of its module.  Served, not fine-tuned
+    layer_tokens: bool = False
+    # hypernet_kwargs.share_TF_output_head (hypernetwork.py:221-225): one set of output heads serves every policy block, the
+    # blocks differ through their tokens alone -- so only with layer_tokens
+    shared_block_heads: bool = False
 
     def __post_init__(self):
+        if self.shared_block_heads and not self.layer_tokens:
+            raise ValueError("Geometry(shared_block_heads=True, layer_tokens=False): with share_TF_output_head and one shared layer "
+                             "token every policy block would receive the same weights")
         if self.differential and self.lang_in_policy:
             raise ValueError("use_differential_transformer together with use_language_token is not built: DifferentialAttention adds "
                              "the mask as a bias, so language queries attend to patch keys and the language prefix is no per-episode "
@@ -95,8 +105,12 @@ class Geometry:
         return self.seq + (self.lang_tokens if self.lang_in_policy else 0)
 
     @property
-    def ctx_seq(self) -> int:      # language tokens + initial-image CLS + 1 layer token
-        return self.lang_tokens + 2
+    def num_layer_tokens(self) -> int:   # NL: rows of layer_pos_embedding, and of the context embedding [B, NL, C]
+        return len(layer_token_modules(self)) if self.layer_tokens else 1
+
+    @property
+    def ctx_seq(self) -> int:      # language tokens + initial-image CLS + NL layer tokens
+        return self.lang_tokens + 1 + self.num_layer_tokens
 
     @property
     def head_dim(self) -> int:
@@ -181,6 +195,35 @@ class Leaf:
     @property
     def head_name(self) -> str:     # flax auto-name of the per-leaf Dense: hypernetwork.py:65-67
         return "output_head_" + self.flat_name
+
+    @property
+    def shared_head_name(self) -> str:   # share_TF_output_head: the head of this leaf's name in any block (hypernetwork.py:221-225)
+        return re.sub(r"encoderblock_\d+", "encoderblock", self.head_name)
+
+
+def layer_token_modules(g: "Geometry") -> List[Tuple[str, ...]]:
+    """THE layer-token table of ``share_layer_index=False`` with ``encoder_type="DINOv2"`` (model.py:418-436): the module each
+    token index stands for, as a path prefix of its leaves.  Index 0 is the shared image encoder, which is not generated
+    (``layer_token_mask[0] = False``); then the modules of ``encoder/Transformer_0``, the remaining ``encoder`` modules, and
+    ``action_head``.  The reference walks dicts that ``jax.tree_map`` rebuilt, whose keys are SORTED AS STRINGS -- the assumption
+    `generated_leaves` already rests on -- so ``encoderblock_10`` comes before ``encoderblock_2``.  The table does
+    not depend on `g.layer_tokens`: it is what the flag switches on."""
+    T = ("encoder", "Transformer_0")
+    mods = [("encoder", "image_encoder")]
+    mods += [T + (m,) for m in sorted(["encoder_norm"] + [f"encoderblock_{l}" for l in range(g.layers)])]
+    mods += [("encoder", m) for m in sorted(["image_embedding_projection", "pos_embedding"] +
+                                            (["language_token_projection"] if g.lang_in_policy else []))]
+    return mods + [("action_head",)]
+
+
+def token_of(g: "Geometry", leaf) -> int:
+    """The layer-token index a generated leaf (a `Leaf` or its path) reads under ``layer_tokens``: that of the module its path
+    begins with.  Never 0."""
+    path = tuple(leaf.path if isinstance(leaf, Leaf) else leaf)
+    for i, m in enumerate(layer_token_modules(g)):
+        if path[:len(m)] == m:
+            return i
+    raise ValueError(f"leaf {'/'.join(path)} belongs to no module of the layer-token table")
 
 
 def generated_leaves(g: Geometry) -> List[Leaf]:
@@ -334,8 +377,8 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
             scale_context_embedding=g.scale_context, output_head_bias=True,
             generation_strategy="block", shared_modules=("image_encoder",),
             include_goal_image=False, use_initial_image=True, use_all_image_tokens=False,
-            share_TF_output_head=False, init_strategy=0, share_all_params=False,
-            share_layer_index=True, image_dropout=0.0),
+            share_TF_output_head=bool(g.shared_block_heads), init_strategy=0, share_all_params=False,
+            share_layer_index=not g.layer_tokens, image_dropout=0.0),
         base_net_kwargs=dict(
             model_type="vit", action_head_type="mix", action_horizon=g.horizon,
             action_dim=g.action_dim,
@@ -350,7 +393,7 @@ def default_config(g: Geometry = FULL, dataset_name: str = "bridge_dataset") -> 
                                     max_action=g.max_action, hidden_dims=())),
         geometry=dict(image_size=g.image_size, patch=g.patch, enc_dim=g.enc_dim,
                       enc_layers=g.enc_layers, enc_heads=g.enc_heads, enc_mlp=g.enc_mlp,
-                      lang_tokens=g.lang_tokens, lang_dim=g.lang_dim),
+                      lang_tokens=g.lang_tokens, lang_dim=g.lang_dim, layer_tokens=bool(g.layer_tokens)),
     )
     return copy.deepcopy(cfg)
 
@@ -368,7 +411,17 @@ def geometry_from_config(cfg: Dict) -> Geometry:
         raise ValueError("only model_type=vit / encoder_type=DINOv2 / action_head_type=mix is built "
                          "(README.md:45-56); got %r/%r/%r" % (b["model_type"], v["encoder_type"],
                                                               b["action_head_type"]))
-    for key, want in (("generation_strategy", "block"), ("share_layer_index", True),
+    # share_layer_index: `geometry.layer_tokens`, which default_config and convert_checkpoint write, must say the same; a raw
+    # reference config has no such key and share_layer_index decides alone
+    layer_tokens = not bool(h.get("share_layer_index", False))
+    if "layer_tokens" in ge and bool(ge["layer_tokens"]) != layer_tokens:
+        raise ValueError(f"hypernet_kwargs.share_layer_index={h.get('share_layer_index')!r} contradicts geometry.layer_tokens="
+                         f"{ge['layer_tokens']!r}: geometry.layer_tokens must equal not share_layer_index")
+    shared_block_heads = bool(h.get("share_TF_output_head", False))
+    if shared_block_heads and not layer_tokens:
+        raise ValueError("hypernet_kwargs.share_TF_output_head=True with share_layer_index=True: every policy block would receive "
+                         "the same weights")
+    for key, want in (("generation_strategy", "block"),
                       ("use_initial_image", True), ("use_all_image_tokens", False),
                       ("attend_to_padding", False), ("task_attend_to_layer", False)):
         if h.get(key) != want:
@@ -411,7 +464,7 @@ def geometry_from_config(cfg: Dict) -> Geometry:
         ctx_heads=ce["num_attention_heads"], ctx_mlp=ce["mlp_dim"],
         lang_tokens=ge.get("lang_tokens", 32), lang_dim=ge.get("lang_dim", 768),
         scale_context=bool(h.get("scale_context_embedding", False)), lang_in_policy=lang_in_policy, mask_as_bias=mask_as_bias,
-        differential=differential)
+        differential=differential, layer_tokens=layer_tokens, shared_block_heads=shared_block_heads)
 
 
 # --------------------------------------------------------------------------------------
@@ -458,7 +511,7 @@ def hypernet_param_shapes(g: Geometry) -> Dict[str, Tuple[int, ...]]:
         "initial_image_projection/kernel": (g.enc_dim, C), "initial_image_projection/bias": (C,),
         "task_pos_embedding": (1, g.lang_tokens, C),
         "initial_image_pos_embedding": (1, 1, C),
-        "layer_pos_embedding": (1, 1, C),
+        "layer_pos_embedding": (1, g.num_layer_tokens, C),
     }
     for l in range(g.ctx_layers):
         b = f"Transformer_0/encoderblock_{l}/"
@@ -477,9 +530,10 @@ def hypernet_param_shapes(g: Geometry) -> Dict[str, Tuple[int, ...]]:
         s[b + "MlpBlock_0/Dense_1/bias"] = (C,)
     s["Transformer_0/encoder_norm/scale"] = (C,)
     s["Transformer_0/encoder_norm/bias"] = (C,)
-    for lf in generated_leaves(g):
-        s[lf.head_name + "/kernel"] = (C, lf.size)
-        s[lf.head_name + "/bias"] = (lf.size,)
+    for lf in generated_leaves(g):       # shared_block_heads: the blocks' leaves of one name collapse onto one head
+        head = lf.shared_head_name if g.shared_block_heads else lf.head_name
+        s[head + "/kernel"] = (C, lf.size)
+        s[head + "/bias"] = (lf.size,)
     for path, shape in encoder_leaves(g):
         s[shared_name(path)] = (int(np.prod(shape)),)
     return s

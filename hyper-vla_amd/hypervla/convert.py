@@ -416,6 +416,8 @@ def convert_checkpoint(src_dir: str, dst_dir: str, step: int, ema: Optional[floa
     if rows != g.patches:
         n = int(round(np.sqrt(rows)))
         config["position_embeddings_baked_from"] = [n, n]
+    # share_layer_index as the geometry key `geometry_from_config` checks it against (hypervla.config.default_config writes it too)
+    config.setdefault("geometry", {})["layer_tokens"] = bool(g.layer_tokens)
     with open(os.path.join(dst_dir, "config.json"), "w") as f:
         json.dump(config, f)
     return out

@@ -59,12 +59,13 @@ class GeneratedWeights:
             pass
 
     def export(self):
-        """(theta [B, G] in reference leaf order, context embedding [B, C]) as torch CUDA tensors."""
+        """(theta [B, G] in reference leaf order, context embedding [B, C]) as torch CUDA tensors; with share_layer_index=False
+        (`Geometry.layer_tokens`) the context embedding is [B, NL, C], one row per layer token."""
         torch = _torch()
         m = self._model
         dev = m.device
         theta = torch.empty(self.batch, m._ctx.num_generated, dtype=torch.float32, device=dev)
-        ctx = torch.empty(self.batch, m.geometry.ctx_dim, dtype=torch.float32, device=dev)
+        ctx = torch.empty((self.batch,) + m._context_shape(), dtype=torch.float32, device=dev)
         m._ctx.weights_export(self._h, theta.data_ptr(), ctx.data_ptr(), m._stream())
         return theta, ctx
 
@@ -74,7 +75,7 @@ class GeneratedWeights:
         return pytree_from_theta(self._model.geometry, self.export()[0].cpu().numpy(), squeeze)
 
     def save(self, path: str) -> None:
-        """Write the handle's policies to `path` as an npz: ``theta`` [B, G] and ``context`` [B, C] as `export` returns them and the
+        """Write the handle's policies to `path` as an npz: ``theta`` [B, G] and ``context`` [B, C] ([B, NL, C] with layer tokens) as `export` returns them and the
         geometry's ``G``; with use_language_token also the ``token_embedding`` [B, T, lang_dim] the rows were built from.
         `HyperVLA.load_tasks` reads it back (through `import_tasks`: the same theta and context bit for bit)."""
         m = self._model
@@ -290,6 +291,11 @@ class HyperVLA:
         return other
 
     # ------------------------------------------------------------------ helpers
+    def _context_shape(self):
+        """The shape of one episode's context embedding: (C,), or (NL, C) with share_layer_index=False."""
+        g = self.geometry
+        return (g.num_layer_tokens, g.ctx_dim) if g.layer_tokens else (g.ctx_dim,)
+
     def _stream(self) -> int:
         return int(_torch().cuda.current_stream(self.device).cuda_stream)
 
@@ -450,8 +456,8 @@ class HyperVLA:
         ctx = None
         if context is not None:
             ctx = self._dev(context, torch.float32)
-            if tuple(ctx.shape) != (B, g.ctx_dim):
-                raise ValueError(f"context must be [{B}, {g.ctx_dim}], got {tuple(ctx.shape)}")
+            if tuple(ctx.shape) != (B,) + self._context_shape():
+                raise ValueError(f"context must be {[B, *self._context_shape()]}, got {tuple(ctx.shape)}")
         tok = None
         if g.lang_in_policy:                      # the only thing instruction_dict is read for
             if instruction_dict is None:
@@ -520,13 +526,17 @@ class HyperVLA:
         torch.cuda.current_stream(self.device).synchronize()      # the maps are temporaries
 
     def load_tasks(self, path: str) -> GeneratedWeights:
-        """The handle `GeneratedWeights.save(path)` wrote, through `import_tasks`; a file of another geometry's G is refused."""
+        """The handle `GeneratedWeights.save(path)` wrote, through `import_tasks`; a file of another geometry's G, or whose context
+        rows are not this model's ([C], or [NL, C] with layer tokens), is refused."""
         with np.load(path) as z:
             G = int(z["G"])
             if G != self._ctx.num_generated:
                 raise ValueError(f"{path} holds policies of G={G} generated parameters, this model's geometry has "
                                  f"G={self._ctx.num_generated}")
             theta, context = z["theta"], z["context"]
+            if tuple(context.shape[1:]) != self._context_shape():
+                raise ValueError(f"{path} holds context rows of shape {tuple(context.shape[1:])}, this model's are "
+                                 f"{self._context_shape()}")
             tok = z["token_embedding"] if "token_embedding" in z.files else None
         ins = None
         if self.geometry.lang_in_policy:

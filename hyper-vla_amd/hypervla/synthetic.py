@@ -96,9 +96,15 @@ def synthetic_params(g: Geometry = FULL, seed: int = SEED_WEIGHTS) -> Dict[str, 
     for lf in generated_leaves(plain):
         std, mean = _leaf_natural(lf.path, lf.shape, g)
         head = lf.head_name.replace(plain.attention_name, g.attention_name)
-        p[head + "/bias"] = normal((lf.size,), std, mean)
+        bias = normal((lf.size,), std, mean)
         # ctx = LN(.)/sqrt(C) has |ctx|~1 => delta ~ 0.5*std of the leaf's own scale
-        p[head + "/kernel"] = normal((C, lf.size), k_scale * std * np.sqrt(C))
+        kernel = normal((C, lf.size), k_scale * std * np.sqrt(C))
+        if g.shared_block_heads:                # one head per leaf name for all blocks: block 0's draw (the others are drawn and dropped,
+            shared = lf.shared_head_name.replace(plain.attention_name, g.attention_name)      # so the rest of the stream does not move)
+            if shared + "/bias" in p:
+                continue
+            head = shared
+        p[head + "/bias"], p[head + "/kernel"] = bias, kernel
 
     # shared DINOv2 leaves (flat vectors)
     for path, shape in encoder_leaves(g):

@@ -469,6 +469,9 @@ class FineTuner:
                           context_dropout=float(embedding_dropout_rate), image_dropout=float(image_dropout))
         self.noise_on = any(v != 0.0 for v in self.noise.values())
         self.noise_seed, self.noise_draw = int(noise_seed), 0
+        if getattr(model.geometry, "layer_tokens", False):
+            raise ValueError("fine-tuning a model with hypernet_kwargs.share_layer_index=False is not built; serving is "
+                             "(the training kernels run one layer token and one GEMM over the output heads, DESIGN.md §24)")
         if getattr(model.geometry, "differential", False) and not self.differential:
             raise ValueError("fine-tuning a model with vit_kwargs.use_differential_transformer is not built; serving is "
                              "(without differential=True the training kernels run no DifferentialAttention, DESIGN.md §23)")

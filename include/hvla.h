@@ -62,7 +62,8 @@ typedef struct hvla_config {
   float tanh_scale, max_action;              /* 5, 5 (action_heads.py:469-470)                  */
   int32_t ctx_dim, ctx_layers, ctx_heads, ctx_mlp; /* hypernet: 128, 6, 4, 512.  ctx_dim 128, 64 or 32; ctx_dim / ctx_heads a multiple
                                                 of 4 (the score loop's k-steps); ctx_mlp % 16 == 0 (the f32 MFMA's column
-                                                tiles), and the context encoder's LDS working set -- (lang_tokens + 2) rows of
+                                                tiles), and the context encoder's LDS working set -- (lang_tokens + 2) rows
+                                                (lang_tokens + 1 + NL with layer_tokens, hvla_policy_options_v4) of
                                                 max(3 ctx_dim, ctx_mlp) + 2 ctx_dim floats -- must fit 160 KiB: hvla_create
                                                 returns HVLA_E_SHAPE otherwise                                          */
   int32_t lang_tokens, lang_dim;             /* 32, 768                                         */
@@ -154,11 +155,44 @@ typedef struct hvla_policy_options_v3 {
 /* hvla_create_with_v2 for hvla_policy_options_v3: opts == NULL, or differential_attention 0, is hvla_create_with_v2 of the other
  * two fields (the same ctx, byte for byte).  Refusals as for hvla_create_with_v2.                                          */
 int hvla_create_with_v3(const hvla_config* cfg, const hvla_policy_options_v3* opts, int device, hvla_ctx** out);
+
+/* hvla_policy_options_v3 with two more fields, by the same rule (struct_size must be sizeof(hvla_policy_options_v4)).
+ *   layer_tokens        hypernet_kwargs.share_layer_index=False (hypervla/model.py:400-436, the reference config's default): the
+ *                       context encoder's sequence ends in NL = layers + 5 (+ 1 with use_language_token) learned layer tokens, one
+ *                       per module of the policy in key-sorted order -- 0 the shared image encoder (attended by nobody), then
+ *                       encoder_norm, encoderblock_<l> as strings (encoderblock_10 before encoderblock_2), image_embedding_
+ *                       projection, (language_token_projection,) pos_embedding, action_head -- a layer key is attended by the
+ *                       layer queries alone (hypernetwork.py:149-181), and every generated leaf is the output head of its name
+ *                       applied to the context row of its module's token (hypernetwork.py:199-217).  Shapes that
+ *                       change: "layer_pos_embedding" is (1, NL, ctx_dim) in hvla_load_weights; the context of an episode is
+ *                       [NL, ctx_dim] wherever it is carried (hvla_weights_export / _import / _import_slots, pool slots, copies).
+ *                       Needs lang_tokens + 1 + NL <= 48 and the context encoder's LDS working set with that many rows within
+ *                       160 KiB.  Served only: every hvla_train_* entry returns HVLA_E_SHAPE with a text naming share_layer_index.
+ *   shared_block_heads  hypernet_kwargs.share_TF_output_head (hypernetwork.py:221-225): the leaves of all policy blocks with one
+ *                       name are generated by ONE output head, "output_head_encoder_Transformer_0_encoderblock_<rest>" in
+ *                       hvla_load_weights, and differ through their tokens alone.  Only with layer_tokens: HVLA_E_SHAPE otherwise,
+ *                       hvla_last_error(NULL) says why.                                                                         */
+typedef struct hvla_policy_options_v4 {
+  uint32_t struct_size;                      /* = sizeof(hvla_policy_options_v4)                                        */
+  int32_t use_language_token;                /* 0 (default) or 1                                                        */
+  int32_t attention_mask_as_bias;            /* 0 (default) or 1                                                        */
+  int32_t differential_attention;            /* 0 (default) or 1                                                        */
+  int32_t layer_tokens;                      /* 0 (default) or 1                                                        */
+  int32_t shared_block_heads;                /* 0 (default) or 1                                                        */
+} hvla_policy_options_v4;
+
+/* hvla_create_with_v3 for hvla_policy_options_v4: opts == NULL, or both new fields 0, is hvla_create_with_v3 of the other three
+ * (the same ctx, byte for byte).  Refusals as for hvla_create_with_v2.                                                      */
+int hvla_create_with_v4(const hvla_config* cfg, const hvla_policy_options_v4* opts, int device, hvla_ctx** out);
+/* NL, the layer tokens of the context (1 unless created with layer_tokens): an episode's context is [NL, ctx_dim].  NULL ctx: 0.  */
+int32_t hvla_num_layer_tokens(const hvla_ctx* ctx);
 void hvla_destroy(hvla_ctx* ctx);
 const char* hvla_last_error(const hvla_ctx* ctx);
 
 /* Replaces: orbax restore of HN params + `.replace(params=EMA)` (hypervla/model.py:210-214,
  * data/simpler/evaluate.py:438-444).  Packs every tensor into its device layout.
+ * With layer_tokens "layer_pos_embedding" has NL * ctx_dim elements; with shared_block_heads the policy blocks' output heads are the
+ * shared ones, "output_head_encoder_Transformer_0_encoderblock_<rest>/{kernel,bias}" (hvla_policy_options_v4).
  * Must be given every tensor of the checkpoint in one call; may be called again to swap weights. */
 int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* tensors, int32_t n);
 
@@ -182,7 +216,8 @@ int32_t hvla_weights_batch(const hvla_weights* w);
 
 /* Reference-order views for the caller / parity tests (the reference returns these from
  * create_tasks as `base_params` and the context embedding).  theta f32 [B, G] in pytree leaf
- * order; context f32 [B, ctx_dim].  Either pointer may be NULL.          */
+ * order; context f32 [B, ctx_dim], with layer_tokens [B, NL, ctx_dim]
+ * (NL = hvla_num_layer_tokens).  Either pointer may be NULL.                                    */
 int hvla_weights_export(hvla_ctx* ctx, const hvla_weights* w, float* theta, float* context,
                         void* stream);
 
@@ -249,7 +284,7 @@ int hvla_ensemble(hvla_ctx* ctx, hvla_weights* w, const float* actions, const fl
 int hvla_weights_alloc(hvla_ctx* ctx, int32_t B, hvla_weights** out, void* stream);
 /* hvla_generate for K (1 <= K <= min(B, max_batch)) new tasks into slots[0 .. K-1] of w: inputs as hvla_generate's for K
  * episodes.  Writes only those rows of the weights and the context and zeroes those slots' ensemble counters; the rows are
- * bitwise what hvla_generate gives the same tasks.                                                                          */
+ * bitwise what hvla_generate gives the same tasks.  (With layer_tokens a context row is [NL, ctx_dim], here as everywhere.)           */
 int hvla_generate_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, int32_t K, const float* token_embedding,
                         const int64_t* attention_mask, const float* initial_cls, void* stream);
 /* hvla_step for K frames, frame k with the weights of slot slots[k]: images u8 [K, H, W, 3] -> actions f32 [K, horizon,
@@ -268,7 +303,8 @@ int hvla_ensemble_slots(hvla_ctx* ctx, hvla_weights* w, const int32_t* slots, in
  * returns a plain `base_params` pytree and sample_actions(base_params=...) runs any pytree of that shape (hypervla/model.py:35-137): a
  * policy kept on disk, the mean of two tasks' policies, a perturbed leaf, one the hypernetwork never produced.  hypervla.model
  * import_tasks / assign_base_params / copy_tasks / load_tasks drive these.  theta is a DEVICE f32 [K, G] in reference leaf order
- * (G = hvla_num_generated; what hvla_weights_export writes), context a device f32 [K, ctx_dim] or NULL (zeros: the policy does not read
+ * (G = hvla_num_generated; what hvla_weights_export writes), context a device f32 [K, ctx_dim] -- [K, NL, ctx_dim] for a context
+ * created with layer_tokens, NL = hvla_num_layer_tokens -- or NULL (zeros: the policy does not read
  * it), token_embedding a device f32 [K, lang_tokens, lang_dim], required iff the context was created with use_language_token (the
  * rows' language prefix is then written from it, as hvla_generate does) and refused otherwise.  Matrix elements are split into
  * hi = bf16(x), lo = bf16(x - hi) exactly as the weight generation splits its f32 results; vector elements are stored as given;
