@@ -64,6 +64,8 @@ struct TrainState {               // what the hvla_train_* entries keep per cont
   bool frozen_enc = false;        //   ... namely the one of this train_encoder value
   bool language_tokens = false;   // hvla_train_language_tokens: the entries serve this use_language_token context
   bool differential = false;      // hvla_train_differential: the entries serve this differential_attention context
+  bool layer_tokens = false;      // hvla_train_layer_tokens: the entries serve this layer_tokens context ...
+  DevBuf tiles;                   //   ... with the tile tables of its three grouped products (sel.groups points into them), built with the layout
   bool noise_set = false;         // hvla_train_noise_set holds a setting (sel.noise, by value; all rates 0 is a setting too)
   hipEvent_t ev_bucket[3] = {nullptr, nullptr, nullptr};   // hvla_train_step: gradient buckets final (created on first use)
   bool bucket_recorded[3] = {false, false, false};
@@ -82,6 +84,8 @@ struct hvla_ctx {
   CtxParams ctxp{};
   DevBuf wcat_hi, wcat_lo, bcat, perm;
   DevBuf seg_token, tile_segs;   // layer_tokens: wcat_hi / wcat_lo then hold one fragment block per segment (pack.h TokenSegments)
+  DevBuf seg_tile, pos_token, pos_head;   //   ... and what hvla_train_publish gathers them by: a segment's tile, a position's token and head column
+  int nseg = 0;
   DevBuf enc16, encd16, encf32;  // encoder matrices (16-bit), their rounding residues x 4096 (16-bit) and vectors (f32)
   EncWeights encw{};
   // workspaces (sized for cfg.max_batch)
@@ -311,6 +315,19 @@ int hvla_load_weights(hvla_ctx* ctx, const hvla_tensor_desc* t, int32_t n) {
   if (g.layer_tokens) {
     HIPCHK(ctx, up(ctx->seg_token, segs.token.data(), segs.token.size() * 4));
     HIPCHK(ctx, up(ctx->tile_segs, segs.tile_segs.data(), segs.tile_segs.size() * 4));
+    // publish.hip's maps: the head column of every packed position, through the training layout's run table
+    const TrainLayout L = make_train_layout(g);
+    std::vector<int32_t> pos_head(segs.pos_token.size(), -1);
+    if (L.policy_ok)
+      for (size_t pos = 0; pos < pos_head.size(); ++pos) {
+        const int32_t ref = ctx->lay.perm[pos];
+        for (int r = 0; r < L.nruns && ref >= 0; ++r)
+          if (ref >= L.run[r].tcol && ref < L.run[r].tcol + L.run[r].width) pos_head[pos] = (int32_t)(L.run[r].hcol + (ref - L.run[r].tcol));
+      }
+    HIPCHK(ctx, up(ctx->seg_tile, segs.tile.data(), segs.tile.size() * 4));
+    HIPCHK(ctx, up(ctx->pos_token, segs.pos_token.data(), segs.pos_token.size() * 4));
+    HIPCHK(ctx, up(ctx->pos_head, pos_head.data(), pos_head.size() * 4));
+    ctx->nseg = (int)segs.token.size();
   }
   HIPCHK(ctx, up(ctx->enc16, h.enc16.data(), h.enc16.size() * 2));
   HIPCHK(ctx, up(ctx->encd16, h.encd16.data(), h.encd16.size() * 2));
@@ -863,10 +880,17 @@ static int frozen_fits(hvla_ctx* ctx, bool train_encoder) {
 static int train_entry(hvla_ctx* ctx, bool args = true, int frozen_for = -1) {
   if (!ctx || !args) return HVLA_E_STATE;
   TrainState& t = ctx->train;
-  if (const char* why = train_refusal(ctx->g, t.language_tokens, t.differential)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
+  if (const char* why = train_refusal(ctx->g, t.language_tokens, t.differential, t.layer_tokens)) FAIL(ctx, HVLA_E_SHAPE, "%s", why);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (!t.have_layout) { t.L = make_train_layout(ctx->g); t.have_layout = true; }
   if (!t.L.policy_ok) FAIL(ctx, HVLA_E_STATE, "the generated policy has no leaf of a name the training path reads");
+  if (ctx->g.layer_tokens && !t.tiles.p) {      // once per context: the tables do not depend on the batch
+    std::vector<BGTile> host;
+    (void)token_groups(ctx->g, t.L, nullptr, host);
+    HIPCHK(ctx, t.tiles.alloc(host.size() * sizeof(BGTile)));
+    HIPCHK(ctx, hipMemcpy(t.tiles.p, host.data(), host.size() * sizeof(BGTile), hipMemcpyHostToDevice));
+    t.sel.groups = token_groups(ctx->g, t.L, t.tiles.as<BGTile>(), host);
+  }
   return frozen_for < 0 ? HVLA_OK : frozen_fits(ctx, frozen_for != 0);
 }
 
@@ -876,6 +900,15 @@ int hvla_train_sizes(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t ou
   const TrainLayout& L = ctx->train.L;
   out[0] = train_vector_elems(L, ctx->train.sel.ps, train_encoder != 0); out[1] = L.G;
   out[2] = (int64_t)train_workspace_floats(ctx->g, B, train_encoder != 0, ctx->train.sel.noise); out[3] = L.total;
+  return HVLA_OK;
+}
+
+int hvla_train_context_rows(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[3]) {
+  if (int rc = train_entry(ctx, out != nullptr)) return rc;
+  if (B < 1) FAIL(ctx, HVLA_E_SHAPE, "batch %d", B);
+  long o[3];
+  train_context_rows(ctx->g, B, train_encoder != 0, ctx->train.sel.noise, o);
+  out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
   return HVLA_OK;
 }
 
@@ -964,6 +997,14 @@ int hvla_train_differential(hvla_ctx* ctx, int32_t on) {
   if (on != 1) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_differential(%d): 0 or 1", on);
   if (!ctx->g.differential) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_differential(1) on a context created without differential_attention");
   ctx->train.differential = true;
+  return HVLA_OK;
+}
+
+int hvla_train_layer_tokens(hvla_ctx* ctx, int32_t on) {
+  if (!ctx) return HVLA_E_STATE;
+  if (on == 0) { ctx->train.layer_tokens = false; return HVLA_OK; }
+  if (on != 1) FAIL(ctx, HVLA_E_SHAPE, "hvla_train_layer_tokens(%d): 0 or 1", on);
+  ctx->train.layer_tokens = ctx->g.layer_tokens != 0;      // on a context without layer tokens: HVLA_OK and nothing changes
   return HVLA_OK;
 }
 
@@ -1131,6 +1172,10 @@ int hvla_train_publish(hvla_ctx* ctx, const float* params, int64_t n_params, int
   PublishArgs a{g, params, ctx->hn_f32.as<float>(), ctx->perm.as<int32_t>(), ctx->wcat_hi.as<uint16_t>(), ctx->wcat_lo.as<uint16_t>(),
                 ctx->bcat.as<float>(), Gtot, ctx->enc16.as<uint16_t>(), ctx->encd16.as<uint16_t>(), ctx->encf32.as<float>(),
                 ctx->cfg.enc_dtype == HVLA_ENC_BF16, train_encoder != 0};
+  if (g.layer_tokens) {
+    a.pos_head = ctx->pos_head.as<int32_t>(); a.pos_token = ctx->pos_token.as<int32_t>();
+    a.seg_tile = ctx->seg_tile.as<int32_t>(); a.seg_token = ctx->seg_token.as<int32_t>(); a.nseg = ctx->nseg;
+  }
   ctx->prof.nlaunch += train_encoder ? 6 : 2;
   HIPCHK(ctx, launch_publish(a, reinterpret_cast<hipStream_t>(stream)));
   if (ps.n > 0) {      // the served table is the resize of the vector's SOURCE table, by the kernel the step resizes with

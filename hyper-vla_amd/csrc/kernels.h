@@ -229,6 +229,10 @@ struct PublishArgs {
   uint16_t *enc16, *encd16;
   float* encf32;
   int bf, train_encoder;
+  // layer_tokens: wcat_hi / wcat_lo hold one fragment block per segment (pack.h TokenSegments).  Per packed position its
+  // head column in the training vector's W_h (-1: padding) and its token; per segment its tile and its token (device, from the load)
+  const int32_t *pos_head = nullptr, *pos_token = nullptr, *seg_tile = nullptr, *seg_token = nullptr;
+  int nseg = 0;
 };
 hipError_t launch_publish(const PublishArgs& a, hipStream_t st);
 

@@ -43,7 +43,8 @@ struct Geom {
                              // attention is DifferentialAttention_0 -- two softmaxes over the halves of each head's q / k, A1 - lambda A2,
                              // an RMSNorm per head; no q / k / v / out bias.  Not with either flag above
   int layer_tokens = 0;      // hypernet_kwargs.share_layer_index=False (model.py:400-436): NL() layer tokens in the context encoder, every generated
-                             // leaf reads the token of its module (layer_token_of, below).  Served, not fine-tuned
+                             // leaf reads the token of its module (layer_token_of, below).  Fine-tuned behind
+                             // hvla_train_layer_tokens (train_layout.h's run table)
   int shared_block_heads = 0;   // hypernet_kwargs.share_TF_output_head (hypernetwork.py:221-225): one output head per leaf name for all policy
                              // blocks; only with layer_tokens
   // rows of layer_pos_embedding and of the context embedding: the shared image encoder, encoder_norm, L blocks, the image projection,

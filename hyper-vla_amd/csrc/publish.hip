@@ -147,14 +147,80 @@ __global__ void __launch_bounds__(256) publish_wcat_kernel(const float* __restri
   }
 }
 
+// ---- the same for a layer-token model: one fragment block per SEGMENT (pack.h TokenSegments) ----
+// A workgroup takes WC_RUN consecutive segments.  Column tau of segment q is position 32 tile(q) + tau; it is live iff the position's
+// token is the segment's, and then gathers column pos_head[position] of W_h [C][Gh] -- with shared block heads the L blocks' positions
+// of one leaf read one column.  Positions of another token, or of padding, are zero rows, as pack_segments leaves them; the split is
+// publish_wcat_kernel's.  b_cat in packed order is written by the one segment a position is live in (padding keeps the load's zero).
+__global__ void __launch_bounds__(256) publish_wcat_segments_kernel(const float* __restrict__ wcat, const float* __restrict__ bsrc,
+                                                                    const int32_t* __restrict__ pos_head, const int32_t* __restrict__ pos_token,
+                                                                    const int32_t* __restrict__ seg_tile, const int32_t* __restrict__ seg_token,
+                                                                    uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, float* __restrict__ bc,
+                                                                    int Gh, int nseg, int KS) {
+  __shared__ uint4 stage[2][WC_RUN * 64];          // [plane][segment][lane]: 8 bf16 each
+  const int q0 = blockIdx.x * WC_RUN;
+  const int tid = threadIdx.x;
+  int ref[2], slot[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = tid + 256 * c, sl = col >> 5, tau = col & 31;
+    ref[c] = -1;
+    slot[c] = sl * 64 + rho_of_tau(tau);
+    if (q0 + sl < nseg) {
+      const int pos = seg_tile[q0 + sl] * 32 + tau;
+      if (pos_token[pos] == seg_token[q0 + sl]) {
+        ref[c] = pos_head[pos];
+        bc[pos] = bsrc[ref[c]];
+      }
+    }
+  }
+  for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float w[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) w[r] = ref[c] >= 0 ? wcat[(size_t)(16 * ks + r) * Gh + ref[c]] : 0.f;
+#pragma unroll
+      for (int hk = 0; hk < 2; ++hk) {
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint16_t h0, l0, h1, l1;
+          split_pair(w[8 * hk + 2 * j], h0, l0);
+          split_pair(w[8 * hk + 2 * j + 1], h1, l1);
+          h[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
+          l[j] = (uint32_t)l0 | ((uint32_t)l1 << 16);
+        }
+        stage[0][slot[c] + 32 * hk] = make_uint4(h[0], h[1], h[2], h[3]);
+        stage[1][slot[c] + 32 * hk] = make_uint4(l[0], l[1], l[2], l[3]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = tid; i < WC_RUN * 64; i += 256) {
+      const int q = q0 + (i >> 6);
+      if (q < nseg) {
+        const size_t o = ((size_t)q * KS + ks) * 64 + (i & 63);      // in 16-byte units
+        reinterpret_cast<uint4*>(hi)[o] = stage[0][i];
+        reinterpret_cast<uint4*>(lo)[o] = stage[1][i];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 hipError_t launch_publish(const PublishArgs& a, hipStream_t st) {
   const TrainLayout L = make_train_layout(a.g);
   const CopyTable ct = ctx_table(a.g, L);
   const int ctx_layers = ct.layers > 0 ? ct.layers : 1;
   hipLaunchKernelGGL(publish_copy_kernel, dim3(16, ct.nseg, ctx_layers), dim3(256), 0, st, a.params, a.hn, ct);
   const int Gtot = a.Gtot, ntiles = Gtot / 32;
-  hipLaunchKernelGGL(publish_wcat_kernel, dim3((ntiles + WC_RUN - 1) / WC_RUN), dim3(256), 0, st, a.params + L.wcat, a.params + L.bcat,
-                     a.perm, a.wcat_hi, a.wcat_lo, a.bcat, (int)L.G, ntiles, a.g.C / 16);
+  if (a.g.layer_tokens)
+    hipLaunchKernelGGL(publish_wcat_segments_kernel, dim3((a.nseg + WC_RUN - 1) / WC_RUN), dim3(256), 0, st, a.params + L.wcat, a.params + L.bcat,
+                       a.pos_head, a.pos_token, a.seg_tile, a.seg_token, a.wcat_hi, a.wcat_lo, a.bcat, (int)L.Gh, a.nseg, a.g.C / 16);
+  else
+    hipLaunchKernelGGL(publish_wcat_kernel, dim3((ntiles + WC_RUN - 1) / WC_RUN), dim3(256), 0, st, a.params + L.wcat, a.params + L.bcat,
+                       a.perm, a.wcat_hi, a.wcat_lo, a.bcat, (int)L.G, ntiles, a.g.C / 16);
   if (a.train_encoder) {
     const EncMap m = enc_map(a.g, L);
     const int enc_layers = m.layers > 0 ? m.layers : 1;

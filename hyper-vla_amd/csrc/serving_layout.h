@@ -73,7 +73,7 @@ inline Extent served_ctx(const Geom& g, const TrainLayout& L, Offsets& at, F&& f
   put("task_token_projection/kernel", g.lang_dim * C, L.w_tok, at.w_tok, PAD4); put("task_token_projection/bias", C, L.b_tok, at.b_tok, PAD4);
   put("initial_image_projection/kernel", g.E * C, L.w_img, at.w_img, PAD4); put("initial_image_projection/bias", C, L.b_img, at.b_img, PAD4);
   put("task_pos_embedding", g.T * C, L.pos_tok, at.pos_tok, PAD4); put("initial_image_pos_embedding", C, L.pos_img, at.pos_img, PAD4);
-  put("layer_pos_embedding", g.NL() * C, L.pos_layer, at.pos_layer, PAD4);     // (1, NL, C); NL > 1 is served only: the training vector holds one row
+  put("layer_pos_embedding", g.NL() * C, L.pos_layer, at.pos_layer, PAD4);     // (1, NL, C): the training vector holds the NL rows too
   put("Transformer_0/encoder_norm/scale", C, L.norm_s, at.norm_s, PAD4); put("Transformer_0/encoder_norm/bias", C, L.norm_b, at.norm_b, PAD4);
   for (int l = 0; l < g.ctx_layers; ++l) {
     const BlockLeaves& s = L.layer[l];

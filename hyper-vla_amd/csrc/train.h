@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/hvla.h"
 #include "layout.h"
 #include "noise.h"
@@ -30,6 +32,13 @@ struct BG {
   long sBias1 = 0;            // bias stride of the inner batch index b1
 };
 void bgemm(hipStream_t st, bool ta, bool tb, BG g, int nb0);
+// The grouped form: ONE launch whose workgroup column blockIdx.x takes its operand origins, its column origin and
+// width and its K range from tiles[blockIdx.x] (device memory; train_layout.h group_tiles).  g gives the bases, M, the leading
+// dimensions, alpha, the bias base (nullable) and accumulate (0 store, 1 +=, 2 atomic +=), K for a tile without a K range of its own; g.N, the
+// strides and ksplit are not read.  grid = (ntiles, ceil(M / tile), nz); tile = 64 / 128 square; vec_ok: every origin of the table is a multiple of 4 floats.
+// `flops`: the product's f32-equivalent work for the launch timer.  The same staging, hi / lo split, three-MFMA core and store
+// modes as bgemm()'s kernel, in a kernel of its own.
+void bgemm_groups(hipStream_t st, bool ta, bool tb, BG g, const BGTile* tiles, int ntiles, int tile, int nz, bool vec_ok, double flops);
 void train_gemm_timer(bool on, bool first_use_by_this_context);                  // hvla_train_profile (the current device's timer; counts its users)
 void train_gemm_timer_release();                                                 // hvla_destroy of a context that used it: the events go with the last user
 hipError_t train_gemm_timer_read(float* ms, double* flops, int* launches);      // since the last read
@@ -53,6 +62,8 @@ struct TrainNoise {
   bool on() const { return policy_dropout > 0.f || sigma > 0.f || context_dropout > 0.f || image_dropout > 0.f; }
 };
 size_t train_workspace_floats(const Geom& g, int B, bool train_encoder, const TrainNoise& nz = TrainNoise());
+// hvla_train_context_rows: where a step of this batch size leaves ctx and dctx [B][NL][C] in `work` (offsets in floats), and their length
+void train_context_rows(const Geom& g, int B, bool train_encoder, const TrainNoise& nz, long out[3]);
 // hvla_train_noise_probe: out[i] = the multiplier of element i of a dropout site (rate > 0: 0 or 1 / keep_prob) or, with
 // normal, the i-th normal of the site, for the sample whose global index is key.sample0
 hipError_t train_noise_probe(const NoiseKey& key, float rate, bool normal, long n, float* out, hipStream_t st);
@@ -118,6 +129,31 @@ struct AttnAux {
   float* align = nullptr;             // [B] out, nullable: align_b (written iff w_align > 0)
   bool on() const { return w_ent > 0.f || w_align > 0.f; }
 };
+// hvla_train_layer_tokens: the tile tables of the three grouped weight-generation products in device memory, built
+// once per context from the layout's run table (api.hip; train_layout.h group_tiles).  fwd / dw: 64- and 128-column tiles [0] / [1]
+struct TokenGroups {
+  const BGTile *fwd[2] = {nullptr, nullptr}, *dw[2] = {nullptr, nullptr}, *dctx = nullptr;
+  int ntiles[2] = {0, 0}, ndctx = 0;
+  bool vec_ok = false;
+};
+// the five tables back to back in `host` (what the caller uploads to `base`), and the selection that points into `base`
+inline TokenGroups token_groups(const Geom& g, const TrainLayout& L, const BGTile* base, std::vector<BGTile>& host) {
+  TokenGroups t;
+  host.clear();
+  auto put = [&](int kind, int tile, int& count) {
+    const std::vector<BGTile> v = group_tiles(g, L, kind, tile);
+    const BGTile* at = base + host.size();
+    host.insert(host.end(), v.begin(), v.end());
+    count = (int)v.size();
+    return at;
+  };
+  int n = 0;
+  t.fwd[0] = put(0, 64, t.ntiles[0]); t.fwd[1] = put(0, 128, t.ntiles[1]);
+  t.dw[0] = put(1, 64, n); t.dw[1] = put(1, 128, n);
+  t.dctx = put(2, group_kchunk(L), t.ndctx);
+  t.vec_ok = group_vec_ok(g, L);
+  return t;
+}
 // what the hvla_train_* setters selected, in one struct for the three entries below (default: everything off)
 struct TrainOptions {
   PosSource ps;                       // hvla_train_position_source (trained encoder only)
@@ -125,6 +161,7 @@ struct TrainOptions {
   int frozen_buckets = 0;             //   ... and the buckets train_step leaves out
   AttnAux aux;                        // hvla_train_attention_losses
   TrainNoise noise;                   // hvla_train_noise_set
+  TokenGroups groups;                 // hvla_train_layer_tokens (read under Geom::layer_tokens only)
 };
 // vector length of params / grads / mu / nu: the shared leaves and the position table's source follow the hypernetwork's when
 // the image encoder is trained

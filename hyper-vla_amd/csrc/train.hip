@@ -314,6 +314,20 @@ __global__ void softmax_lang_fwd_kernel(float* __restrict__ p, int nmat, int S, 
   softmax_row(p + (long)row * ld, S, ld, lane, [=](int k) { return q < T ? k < T : (q == S - 1 || k < S - 1); });
 }
 
+// The context encoder's mask with NL layer tokens (hypernetwork.py:149-181) on [nmat][S][S], S = T + 1 + NL: a
+// language key by the episode's mask, the image key always, a layer key for the layer queries only and never token 0's (key T + 1).
+// Every row keeps the image key, so no row is empty.  A kernel of its own, as above.
+__global__ void softmax_tokens_fwd_kernel(float* __restrict__ p, int nmat, int S, int T, const int64_t* __restrict__ am, int heads, int ld) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= nmat * S) return;
+  const int mat = row / S, q = row % S;
+  softmax_row(p + (long)row * ld, S, ld, lane, [=](int k) {
+    if (k < T) return am[(long)(mat / heads) * T + k] != 0;
+    if (k == T) return true;
+    return q > T && k != T + 1;
+  });
+}
+
 // The policy's attention under return_attention_map: CustomMultiHeadDotProductAttention adds the 0 / 1 mask of
 // base_vit.py:209-214 to the scaled scores (multi_head_attetion.py:88-98) and masks nothing.  Per row only differences count: the
 // action row q = S - 1 (every key + 1) is a plain softmax, a patch row sees key S - 1 one logit below the others.  A kernel of its
@@ -875,6 +889,83 @@ __global__ void ctx_final_bwd_kernel(const float* __restrict__ x, long xstride, 
   }
 }
 
+// The same four with NL layer tokens, Sc = T + 1 + NL rows per episode: rows T + 1 .. Sc - 1 start as the rows of
+// pos_layer [NL][C], dpos_layer[j] = sum_b dx[b][T + 1 + j]; the final LayerNorm and scale run over the last NL rows of every episode,
+// row = b NL + j of ctx / xhat / dctx [B][NL][C] and mean / rstd [B NL], one wave per row.  Kernels of their own, as above.
+__global__ void ctx_rows_tokens_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
+                                       const float* __restrict__ pos_layer, int B, int T, int NL, int C) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int Sc = T + 1 + NL;
+  if (i >= (long)B * Sc * C) return;
+  const int c = (int)(i % C), t = (int)((i / C) % Sc);
+  if (t < T) x[i] += pos_tok[(long)t * C + c];
+  else if (t == T) x[i] += pos_img[c];
+  else x[i] = pos_layer[(long)(t - T - 1) * C + c];
+}
+__global__ void ctx_rows_tokens_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
+                                           float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
+                                           int B, int T, int NL, int C) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int Sc = T + 1 + NL;
+  if (i >= (long)B * Sc * C) return;
+  const int c = (int)(i % C), t = (int)((i / C) % Sc);
+  const float v = dx[i];
+  if (t < T) { unsafeAtomicAdd(dpos_tok + (long)t * C + c, v); unsafeAtomicAdd(db_tok + c, v); }
+  else if (t == T) { unsafeAtomicAdd(dpos_img + c, v); unsafeAtomicAdd(db_img + c, v); }
+  else unsafeAtomicAdd(dpos_layer + (long)(t - T - 1) * C + c, v);
+}
+__global__ void ctx_final_tokens_fwd_kernel(const float* __restrict__ x, int Sc, int NL, float* __restrict__ xhat,
+                                            float* __restrict__ mean, float* __restrict__ rstd, const float* __restrict__ scale,
+                                            const float* __restrict__ bias, float* __restrict__ ctx, int rows, int C, float post) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const float* xr = x + ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C;
+  float s = 0.f, q = 0.f;
+  for (int c = lane; c < C; c += 64) { s += xr[c]; q += xr[c] * xr[c]; }
+  for (int o = 32; o; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
+  const float m = s / C, var = fmaxf(0.f, q / C - m * m), r = rsqrtf(var + 1e-6f);
+  for (int c = lane; c < C; c += 64) {
+    const float xh = (xr[c] - m) * r;
+    xhat[(long)row * C + c] = xh;
+    ctx[(long)row * C + c] = (xh * scale[c] + bias[c]) * post;
+  }
+  if (lane == 0) { mean[row] = m; rstd[row] = r; }
+}
+__global__ void ctx_final_tokens_bwd_kernel(const float* __restrict__ x, int Sc, int NL, const float* __restrict__ dctx,
+                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                            const float* __restrict__ scale, float* __restrict__ dx, float* __restrict__ dscale,
+                                            float* __restrict__ dbias, int rows, int C, float post) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const long xo = ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C;
+  const float* xr = x + xo;
+  const float m = mean[row], r = rstd[row];
+  float s1 = 0.f, s2 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float xh = (xr[c] - m) * r, dy = dctx[(long)row * C + c] * post, dxh = dy * scale[c];
+    s1 += dxh; s2 += dxh * xh;
+  }
+  for (int o = 32; o; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+  for (int c = lane; c < C; c += 64) {
+    const float xh = (xr[c] - m) * r, dy = dctx[(long)row * C + c] * post, dxh = dy * scale[c];
+    dx[xo + c] += r * (dxh - s1 / C - xh * s2 / C);
+    unsafeAtomicAdd(dscale + c, dy * xh);
+    unsafeAtomicAdd(dbias + c, dy);
+  }
+}
+// db_h[hcols] += sum_b dtheta[b, run] for every run in one launch (the grouped form of colsum_kernel): a workgroup is one 64-column
+// tile of the forward's table (train_layout.h group_tiles kind 0: c = theta column origin, bias = head column origin), blockIdx.z a
+// chunk of 64 rows, one atomic per (chunk, column) -- with shared heads the L blocks' sums meet in one element
+__global__ void colsum_groups_kernel(const float* __restrict__ x, long ld, float* __restrict__ out, const BGTile* __restrict__ tiles, int rows) {
+  const BGTile t = tiles[blockIdx.x];
+  const int n = t.n0 + threadIdx.x;
+  if (n >= t.N) return;
+  const int r0 = blockIdx.z * 64, r1 = r0 + 64 < rows ? r0 + 64 : rows;
+  float s = 0.f;
+  for (int r = r0; r < r1; ++r) s += x[(long)r * ld + t.c + n];
+  unsafeAtomicAdd(out + t.bias + n, s);
+}
+
 // ---- optimizer ------------------------------------------------------------------------------------
 // Under create_optimizer(frozen_keys=...) (octo/utils/train_utils.py:242-292: multi_transform{trainable: the whole chain, frozen:
 // set_to_zero} by fnmatch over the leaf names; the host resolves the names into `frozen` [n], hvla_train_frozen) the clip sits inside
@@ -1015,7 +1106,8 @@ struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; 
                                                                                                           // drop: vit_kwargs.dropout_rate at the sites of `layer` (the policy only)
                 int differential = 0; DiffLeaves dif{-1, -1, -1, -1, -1};                                 // differential: DifferentialAttention with the block's five vectors at
                 const float* theta = nullptr; float* dtheta = nullptr;                                    // dif in a row of theta / dtheta (row stride ws), depth `layer`
-                float lambda_init() const { return (float)(0.8 - 0.6 * exp(-0.3 * (double)layer)); } };   // differential_transformer.py:75-79
+                float lambda_init() const { return (float)(0.8 - 0.6 * exp(-0.3 * (double)layer)); }      // differential_transformer.py:75-79
+                int layer_rows = 0; };                                                                    // > 0: the context encoder's mask with this many layer tokens (softmax_tokens_fwd_kernel)
 // dP, t2 (a DifferentialAttention policy only, else nullptr): dp = dO V^T [nb][H][S][Sp] and the row sums sum_k dp A2 [nb][H][S];
 // dp is then ds [nb][2 H][S][Sp]
 struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y, *dP, *t2; };
@@ -1097,7 +1189,8 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     // kernels): as A operands they are staged with float4 loads like everything else (S = 257: the all-dword staging these four
     // products per layer were left with cost 3.6 ms per step)
     bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
-    if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
+    if (op.layer_rows > 0) KL(softmax_tokens_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S - 1 - op.layer_rows, op.am, H, Sp);
+    else if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
     else if (op.mask_as_bias) KL(softmax_bias_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, Sp);
     else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
     {
@@ -1300,7 +1393,7 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
     b.pa = diff ? take(nb * h * s * ((s + 3) & ~3L)) : nullptr; b.oraw = diff ? take(nb * s * d) : nullptr;
     return b;
   };
-  const long S = g.pos_rows(), D = g.D, H = g.H, F = g.M, Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;     // S: the policy's rows, T + P + 1 under use_language_token
+  const long S = g.pos_rows(), D = g.D, H = g.H, F = g.M, NL = g.NL(), Sc = g.T + 1 + NL, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;     // S: the policy's rows, T + P + 1 under use_language_token; NL = 1 without layer tokens
   const long Se = g.P() + 1, E = g.E, He = g.enc_heads, Fe = g.enc_mlp;
   pl.cb.resize(g.ctx_layers); pl.pb.resize(g.L); pl.eb.resize(enc ? g.enc_layers : 0);
   for (auto& b : pl.cb) b = take_blk(B, Sc, C, Hc, Fc, false);
@@ -1322,7 +1415,7 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
   const long rg = rf > rd ? rf : rd;
   pl.t.h = take(rd); pl.t.g = take(rg); pl.t.d = take(rg); pl.t.dk = take(rd); pl.t.dq = take(rd); pl.t.dv = take(rd);      /* k, q, v: the order of the leaves (block_bwd batches the three) */ pl.t.dp = take(hss);
   pl.t.y = take(rd);
-  pl.cmean = take(B); pl.crstd = take(B); pl.ctx = take(B * C); pl.dctx = take(B * C); pl.ctxn = take(B * C);
+  pl.cmean = take(B * NL); pl.crstd = take(B * NL); pl.ctx = take(B * NL * C); pl.dctx = take(B * NL * C); pl.ctxn = take(B * NL * C);
   pl.dxrow = take(B * D);
   // the noise copies come last: every offset above is what it is without noise
   pl.ntok = nz.sigma > 0.f && !enc ? take((long)B * g.P() * E) : nullptr;
@@ -1335,6 +1428,10 @@ static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNo
 }
 size_t train_workspace_floats(const Geom& g, int B, bool train_encoder, const TrainNoise& nz) {
   return (size_t)make_plan(g, B, train_encoder, nullptr, nz).used + 64;
+}
+void train_context_rows(const Geom& g, int B, bool train_encoder, const TrainNoise& nz, long out[3]) {
+  const Plan pl = make_plan(g, B, train_encoder, nullptr, nz);
+  out[0] = pl.ctx - static_cast<float*>(nullptr); out[1] = pl.dctx - static_cast<float*>(nullptr); out[2] = (long)B * g.NL() * g.C;
 }
 #ifdef HVLA_TRAIN_TRACE
 // One line `plan <name> <offset> <floats>` per buffer of make_plan (offsets into `work`, the floats the plan asked for), for
@@ -1377,7 +1474,10 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const int frozen_buckets = opt.frozen_buckets;
   const int Tl = g.lang_in_policy ? g.T : 0;       // use_language_token: the policy's rows are [Tl language | P patches | 1 action]
   const int S = g.pos_rows(), P = g.P(), D = g.D, H = g.H, F = g.M, E = g.E;
-  const int Sc = g.T + 2, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;
+  const int NL = g.NL(), Sc = g.T + 1 + NL, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp, T = g.T;      // NL > 1: layer tokens
+  const bool lt = g.layer_tokens != 0;
+  const TokenGroups& tg = opt.groups;
+  const float cpost = g.scale_context ? 1.f / sqrtf((float)C) : 1.f;
   const int Se = P + 1, He = g.enc_heads, Fe = g.enc_mlp, Kp = g.patch * g.patch * 3;
   const bool enc = in.images != nullptr;
   const long G = L.G;
@@ -1396,7 +1496,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
   ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
-  const BlkOpt ctx_opt{1, in.attn_mask, 0}, enc_opt{2, nullptr, 1};      // these two draw nothing
+  BlkOpt ctx_opt{1, in.attn_mask, 0};
+  const BlkOpt enc_opt{2, nullptr, 1};      // these two draw nothing
+  if (lt) ctx_opt.layer_rows = NL;
   const BlkOpt pol_opt{0, nullptr, 0, Tl, g.mask_as_bias, pdrop};
   const auto pol_at = [&](int l) {                                                     // the dropout sites carry their layer
     BlkOpt o = pol_opt;
@@ -1441,14 +1543,22 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // tokens: [B][T][lang] . Wt + bt + pos_t  (rows 0..T-1 of each episode's [Sc][C] block)
   bgemm(st, false, false, BG{in.tok, Pm + L.w_tok, cx0, Pm + L.b_tok, T, C, g.lang_dim, g.lang_dim, C, C, (long)T * g.lang_dim, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
   bgemm(st, false, false, BG{cls, Pm + L.w_img, cx0 + (long)T * C, Pm + L.b_img, 1, C, E, E, C, C, (long)E, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
-  KL(ctx_rows_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, C);
+  if (lt) KL(ctx_rows_tokens_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, NL, C);
+  else KL(ctx_rows_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, C);
   for (int l = 0; l < g.ctx_layers; ++l)
     block_fwd(st, B, Sc, C, Hc, Fc, 0, bind(Pm, L.layer[l]), cb[l], l + 1 < g.ctx_layers ? cb[l + 1].x_in : cx_fin, t, ctx_opt);
   // ctx = LN_f(x[:, -1]) (/ sqrt(C)); rows gathered through a stride: x = cx_fin + (Sc-1)*C, row stride Sc*C
-  KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
-  if (cdrop.on()) dropout_fwd(st, cdrop, NOISE_CONTEXT, 0, ctx, nullptr, ctx, B, C);      // embedding_dropout_rate (hypernetwork.py:193-195)
+  if (lt) KL(ctx_final_tokens_fwd_kernel, dim3((B * NL + 3) / 4), dim3(256), cx_fin, Sc, NL, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B * NL, C, cpost);
+  else KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+  if (cdrop.on()) dropout_fwd(st, cdrop, NOISE_CONTEXT, 0, ctx, nullptr, ctx, B, (long)NL * C);      // embedding_dropout_rate (hypernetwork.py:193-195)
   // =============================== theta = ctx W_cat + b_cat (hypernetwork.py:205-233) ===============================
-  bgemm(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0}, 1);
+  // layer tokens: theta[b, run] = ctx[b, token(run)] W_h[:, hcols(run)] + b_h[hcols(run)], every run in ONE grouped launch; the K order of
+  // an element is C's ascending k steps whatever B and whatever the run's neighbours, so a row stays batch-invariant
+  const long Gh = L.Gh;
+  const int NLC = NL * C, wg = B >= 96 ? 1 : 0, wc = C >= 96 ? 1 : 0;                  // tile tables: [0] 64, [1] 128 columns (bgemm()'s rule on M)
+  if (lt) bgemm_groups(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, NLC, (int)Gh, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0},
+                       tg.fwd[wg], tg.ntiles[wg], wg ? 128 : 64, 1, tg.vec_ok, 2.0 * B * (double)G * C);
+  else bgemm(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0}, 1);
   // =============================== policy forward with per-episode weights ===============================
   const float* TH = tb.theta;
   float* px0 = pb[0].x_in;
@@ -1512,11 +1622,25 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // hvla_train_frozen: a bucket declared frozen is not computed -- its range of `grads` stays the zeros of the memset above, its
   // event is recorded where it always is.  dtheta is complete here whatever is frozen.
   const bool heads_on = !(frozen_buckets & 2), ctx_on = !(frozen_buckets & 4);
-  if (heads_on) {
+  if (heads_on && lt) {
+    // dW_h[:, hcols] += ctx[:, token]^T dtheta[:, run] and db_h[hcols] += sum_b dtheta[b, run], a grouped launch each; with shared heads
+    // the L blocks' runs meet in one head: a real sum, by atomics (the range is the memset's zero)
+    bgemm_groups(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, NLC, (int)G, (int)Gh, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, g.shared_block_heads ? 2 : 1},
+                 tg.dw[wc], tg.ntiles[wc], wc ? 128 : 64, 1, tg.vec_ok, 2.0 * B * (double)G * C);
+    KL(colsum_groups_kernel, dim3(tg.ntiles[0], 1, (B + 63) / 64), dim3(64), tb.dtheta, G, Gm + L.bcat, tg.fwd[0], B);
+  } else if (heads_on) {
     bgemm(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1}, 1);   // dW_cat = ctx^T dtheta
     KL(colsum_kernel, dim3((unsigned)((G + 63) / 64), 1, (B + 63) / 64), dim3(64), tb.dtheta, Gm + L.bcat, 0, B, B, (int)G, 1);                  // db_cat
   }
-  if (ctx_on) {
+  if (ctx_on && lt) {
+    // dctx[b, token] = dtheta[b, run] W_h[:, hcols]^T: split-K over the runs' K chunks in one grouped launch; nothing reads token 0,
+    // whose rows stay the memset's zero
+    ENQ(hipMemsetAsync, dctx, 0, (size_t)B * NLC * 4, st);
+    const int td = B >= 96 && C >= 96 ? 128 : 64;
+    bgemm_groups(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)Gh, NLC, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 2},
+                 tg.dctx, tg.ndctx, td, (C + td - 1) / td, tg.vec_ok, 2.0 * B * (double)G * C);
+    if (cdrop.on()) dropout_bwd(st, cdrop, NOISE_CONTEXT, 0, dctx, dctx, B, (long)NLC);
+  } else if (ctx_on) {
     ENQ(hipMemsetAsync, dctx, 0, (size_t)B * C * 4, st);
     // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
     bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
@@ -1526,11 +1650,13 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // =============================== context encoder backward ===============================
   if (ctx_on) {
     ENQ(hipMemsetAsync, cdx, 0, (size_t)B * Sc * C * 4, st);
-    KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+    if (lt) KL(ctx_final_tokens_bwd_kernel, dim3((B * NL + 3) / 4), dim3(256), cx_fin, Sc, NL, dctx, cmean, crstd, Pm + L.norm_s, cdx, Gm + L.norm_s, Gm + L.norm_b, B * NL, C, cpost);
+    else KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
     for (int l = g.ctx_layers - 1; l >= 0; --l)
       block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, bind(Pm, L.layer[l]), bind(Gm, L.layer[l]), cb[l], cdx, t, ctx_opt);
     // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
-    KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
+    if (lt) KL(ctx_rows_tokens_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, NL, C);
+    else KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
     bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
     bgemm(st, true, false, BG{cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
   }

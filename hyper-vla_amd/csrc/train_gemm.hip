@@ -450,4 +450,154 @@ static void bgemm_launch(hipStream_t st, bool ta, bool tb, BG g, int nb0) {
   else hipLaunchKernelGGL((bgemm_kernel<true, true>), grid, dim3(256), 0, st, g);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The grouped form (train.h bgemm_groups): a layer-token model's weight generation reads another context row per
+// run of theta columns, so each of its three products is a list of sub-products that differ in their operand origins.  A workgroup
+// column takes the origins, the column origin and width and the K range from tiles[blockIdx.x]; everything after that is
+// bgemm3_kernel's text -- the same staging, split, core and stores.  A kernel of its own and not a shared body: the existing
+// instantiations keep their ISA (tests/test_isa_guards.py, tests/test_abi.py).  BM = BN in {64, 128}, four waves.
+// ------------------------------------------------------------------------------------------------
+template <bool TA, bool TB, int BM, int BN, bool VEC>
+__global__ __launch_bounds__(256, 2) void bgemm3_groups_kernel(BG g, const BGTile* __restrict__ tiles) {
+  constexpr int NTH = 256;
+  constexpr int WM = BM / 2, WN = BN / 2, IM = WM / 32, IN = WN / 32;
+  constexpr bool SA = TA, SB = !TB;
+  constexpr int NA = SA ? 32 * (BM + 32) : BM * 32, NB = SB ? 32 * (BN + 32) : BN * 32;
+  constexpr int NST = VEC ? 3 : 2;
+  constexpr int PA = BM * 8 / NTH, PB = BN * 8 / NTH;
+  constexpr int LPS = (PA + PB) * (VEC ? 1 : 4);
+  __shared__ __attribute__((aligned(16))) __bf16 Ah[NA], Al[NA], Bh[NB], Bl[NB];
+  const BGTile t = tiles[blockIdx.x];
+  const int kbeg = t.k0, kend = t.k1 ? t.k1 : g.K, N = t.N;       // k1 == 0: the launch's whole K (the table does not depend on the batch)
+  const float* A = g.A + t.a;
+  const float* B = g.B + t.b;
+  float* C = g.C + t.c;
+  const int m0 = blockIdx.y * BM, n0 = t.n0 + blockIdx.z * BN;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wm = wave >> 1, wn = wave & 1, col = lane & 31, half = lane >> 5;
+  f32x16 acc[IM][IN];
+#pragma unroll
+  for (int a = 0; a < IM; ++a)
+#pragma unroll
+    for (int b = 0; b < IN; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  StageRegs<PA, VEC> ra[NST];
+  StageRegs<PB, VEC> rb[NST];
+#pragma unroll
+  for (int s2 = 0; s2 < NST; ++s2) {
+    stage_load<SA, BM, VEC, NTH>(A, g.lda, m0, g.M, kbeg + 32 * s2, kend, ra[s2]);
+    stage_load<SB, BN, VEC, NTH>(B, g.ldb, n0, N, kbeg + 32 * s2, kend, rb[s2]);
+  }
+  for (int k0 = kbeg; k0 < kend; k0 += 32 * NST) {
+#pragma unroll
+    for (int s2 = 0; s2 < NST; ++s2) {
+      const int kcur = k0 + 32 * s2;
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 1) * LPS) : "memory");
+      tie(ra[s2]);
+      tie(rb[s2]);
+      stage_store<SA, BM, VEC, NTH>(Ah, Al, ra[s2]);
+      stage_store<SB, BN, VEC, NTH>(Bh, Bl, rb[s2]);
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      stage_load<SA, BM, VEC, NTH>(A, g.lda, m0, g.M, kcur + 32 * NST, kend, ra[s2]);
+      stage_load<SB, BN, VEC, NTH>(B, g.ldb, n0, N, kcur + 32 * NST, kend, rb[s2]);
+#pragma unroll
+      for (int kk = 0; kk < 32; kk += 16) {
+        Split8 fa[IM], fb[IN];
+#pragma unroll
+        for (int a = 0; a < IM; ++a) fa[a] = load_frag<SA, BM>(Ah, Al, wm * WM + a * 32, kk, lane);
+#pragma unroll
+        for (int b = 0; b < IN; ++b) fb[b] = load_frag<SB, BN>(Bh, Bl, wn * WN + b * 32, kk, lane);
+#pragma unroll
+        for (int a = 0; a < IM; ++a)
+#pragma unroll
+          for (int b = 0; b < IN; ++b) acc[a][b] = mma32_x3(fa[a], fb[b], acc[a][b]);
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const float* bias = g.bias ? g.bias + t.bias : nullptr;
+  auto store = [&](auto fullc, auto modec) {
+    constexpr bool FULL = decltype(fullc)::value;
+    constexpr int MODE = decltype(modec)::value;    // 0 store, 1 read-modify-write, 2 atomic add
+#pragma unroll
+    for (int b = 0; b < IN; ++b) {
+      const int n = n0 + wn * WN + b * 32 + col;
+      if (!FULL && n >= N) continue;
+      const float bn = bias ? bias[n] : 0.f;
+#pragma unroll
+      for (int a = 0; a < IM; ++a) {
+        float old[16];
+        if constexpr (MODE == 1) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm * WM + a * 32 + crow(r, half);
+            old[r] = (FULL || m < g.M) ? C[(long)m * g.ldc + n] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wm * WM + a * 32 + crow(r, half);
+          if (!FULL && m >= g.M) continue;
+          const float v = g.alpha * acc[a][b][r] + bn;
+          float* c = C + (long)m * g.ldc + n;
+          if constexpr (MODE == 2) unsafeAtomicAdd(c, v);
+          else if constexpr (MODE == 1) *c = old[r] + v;
+          else *c = v;
+        }
+      }
+    }
+  };
+  using Yes = std::integral_constant<bool, true>;
+  using No = std::integral_constant<bool, false>;
+  using M0 = std::integral_constant<int, 0>;
+  using M1 = std::integral_constant<int, 1>;
+  using M2 = std::integral_constant<int, 2>;
+  const bool full = m0 + BM <= g.M && n0 + BN <= N;
+  const int mode = g.accumulate;
+  if (full) {
+    if (mode == 2) store(Yes{}, M2{}); else if (mode == 1) store(Yes{}, M1{}); else store(Yes{}, M0{});
+  } else {
+    if (mode == 2) store(No{}, M2{}); else if (mode == 1) store(No{}, M1{}); else store(No{}, M0{});
+  }
+}
+
+template <bool TA, bool TB>
+static void launch_groups(hipStream_t st, const BG& g, const BGTile* tiles, dim3 grid, int tile, bool vec) {
+  if (tile == 128) {
+    if (vec) hipLaunchKernelGGL((bgemm3_groups_kernel<TA, TB, 128, 128, true>), grid, dim3(256), 0, st, g, tiles);
+    else hipLaunchKernelGGL((bgemm3_groups_kernel<TA, TB, 128, 128, false>), grid, dim3(256), 0, st, g, tiles);
+  } else {
+    if (vec) hipLaunchKernelGGL((bgemm3_groups_kernel<TA, TB, 64, 64, true>), grid, dim3(256), 0, st, g, tiles);
+    else hipLaunchKernelGGL((bgemm3_groups_kernel<TA, TB, 64, 64, false>), grid, dim3(256), 0, st, g, tiles);
+  }
+}
+// the three products of the weight generation: (ta, tb) = (0, 0) forward, (1, 0) dW_h, (0, 1) dctx
+static void bgemm_groups_launch(hipStream_t st, bool ta, bool tb, const BG& g, const BGTile* tiles, int ntiles, int tile, int nz, bool vec_ok) {
+  if (ntiles <= 0 || g.M <= 0) return;
+  const dim3 grid(ntiles, (g.M + tile - 1) / tile, nz);
+  const bool vec = vec_ok && g.lda % 4 == 0 && g.ldb % 4 == 0 && ((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0 && (!ta || g.M % 4 == 0);
+  if (!ta && !tb) launch_groups<false, false>(st, g, tiles, grid, tile, vec);
+  else if (ta && !tb) launch_groups<true, false>(st, g, tiles, grid, tile, vec);
+  else launch_groups<false, true>(st, g, tiles, grid, tile, vec);
+}
+void bgemm_groups(hipStream_t st, bool ta, bool tb, BG g, const BGTile* tiles, int ntiles, int tile, int nz, bool vec_ok, double flops) {
+  GemmTimer* tp = g_gemm_timers_on ? gemm_timer_here() : nullptr;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (!tp || !tp->on || hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) { bgemm_groups_launch(st, ta, tb, g, tiles, ntiles, tile, nz, vec_ok); return; }
+  GemmTimer& t = *tp;
+  if (t.used == t.a.size()) {
+    hipEvent_t x, y;
+    if (hipEventCreate(&x) != hipSuccess) { bgemm_groups_launch(st, ta, tb, g, tiles, ntiles, tile, nz, vec_ok); return; }
+    if (hipEventCreate(&y) != hipSuccess) { (void)hipEventDestroy(x); bgemm_groups_launch(st, ta, tb, g, tiles, ntiles, tile, nz, vec_ok); return; }
+    t.a.push_back(x), t.b.push_back(y);
+  }
+  (void)hipEventRecord(t.a[t.used], st);
+  bgemm_groups_launch(st, ta, tb, g, tiles, ntiles, tile, nz, vec_ok);
+  (void)hipEventRecord(t.b[t.used], st);
+  ++t.used;
+  t.flops += flops;
+}
+
 }  // namespace hvla

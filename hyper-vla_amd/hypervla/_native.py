@@ -29,7 +29,8 @@ EXPORTS = ["hvla_create", "hvla_destroy", "hvla_last_error", "hvla_load_weights"
            "hvla_train_position_source", "hvla_train_frozen", "hvla_train_attention_losses", "hvla_train_language_tokens",
            "hvla_weights_import", "hvla_weights_import_slots", "hvla_weights_copy_slots",
            "hvla_loss_terms", "hvla_train_metrics", "hvla_train_noise_set", "hvla_train_noise_probe", "hvla_train_differential",
-           "hvla_create_with_v4", "hvla_num_layer_tokens"]
+           "hvla_create_with_v4", "hvla_num_layer_tokens", "hvla_train_layer_tokens",
+           "hvla_train_context_rows"]
 # hvla_train_metrics (include/hvla.h): select bits, the slots of its output vector, the size of its scratch
 HVLA_METRICS_PRE, HVLA_METRICS_UPDATE = 1, 2
 (HVLA_METRIC_TRAINING_LOSS, HVLA_METRIC_CONTINUOUS_LOSS, HVLA_METRIC_GRIPPER_LOSS, HVLA_METRIC_MSE, HVLA_METRIC_BASE_PARAMS_NORM,
@@ -223,6 +224,10 @@ def load_library():
     lib.hvla_train_language_tokens.restype = C.c_int
     lib.hvla_train_differential.argtypes = [vp, i32]
     lib.hvla_train_differential.restype = C.c_int
+    lib.hvla_train_layer_tokens.argtypes = [vp, i32]
+    lib.hvla_train_layer_tokens.restype = C.c_int
+    lib.hvla_train_context_rows.argtypes = [vp, i32, i32, C.POINTER(C.c_int64)]
+    lib.hvla_train_context_rows.restype = C.c_int
     lib.hvla_train_noise_set.argtypes = [vp, vp]
     lib.hvla_train_noise_set.restype = C.c_int
     lib.hvla_train_noise_probe.argtypes = [vp, C.c_uint32, i64, i64, vp, vp]
@@ -555,6 +560,16 @@ class Context:
     def train_differential(self, on=False):
         """Fine-tune a differential_attention context: while on, the hvla_train_* entries serve it (off: they refuse it, the default)."""
         self._check(self.lib.hvla_train_differential(self.h, int(on)), "hvla_train_differential")
+
+    def train_layer_tokens(self, on=False):
+        """Fine-tune a layer_tokens context: while on, the hvla_train_* entries serve it (off: they refuse it, the default)."""
+        self._check(self.lib.hvla_train_layer_tokens(self.h, int(on)), "hvla_train_layer_tokens")
+
+    def train_context_rows(self, batch, train_encoder=False):
+        """Test instrumentation: (offset of ctx, offset of d ctx, length) in floats of the step's `work` buffer."""
+        out = (C.c_int64 * 3)()
+        self._check(self.lib.hvla_train_context_rows(self.h, int(batch), int(train_encoder), out), "hvla_train_context_rows")
+        return tuple(int(x) for x in out)
 
     def ensemble_reset(self, w, stream=0):
         self._check(self.lib.hvla_ensemble_reset(self.h, w, C.c_void_p(stream)), "hvla_ensemble_reset")

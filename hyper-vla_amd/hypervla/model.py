@@ -641,6 +641,8 @@ class HyperVLA:
         img = self._dev(images, torch.uint8)
         if img.dim() == 5:
             img = img[:, 0].contiguous()
+        if tuple(img.shape[1:]) != (g.image_size, g.image_size, 3):      # the kernel reads B H W 3 bytes whatever it is given
+            raise ValueError(f"encode_images wants uint8 frames [B, (1,) {g.image_size}, {g.image_size}, 3], got {tuple(img.shape)}")
         B = img.shape[0]
         tokens = torch.empty(B, g.patches, g.enc_dim, dtype=torch.float32, device=self.device)
         self._ctx.encode(img.data_ptr(), tokens.data_ptr(), B, self._stream())

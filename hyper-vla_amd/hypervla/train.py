@@ -15,11 +15,49 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 from . import _native
-from .config import Geometry, encoder_leaves, generated_leaves, shared_name
+from .config import Geometry, encoder_leaves, generated_leaves, shared_name, token_of
 
 
 POSITION_SOURCE = "position_table_source"      # the layout's name of the tail: no checkpoint tensor (model.position_table_source)
 POSITION_LEAF = "encoder_image_encoder_embeddings_position_embeddings"
+
+
+def head_columns(g: Geometry):
+    """[(leaf, head name, head column)] in `generated_leaves` order, and Gh: where a leaf's output head sits in the fused heads
+    "W_cat" [C, Gh] / "b_cat" [Gh] (csrc/train_layout.h, the run table's hcol).  Without ``shared_block_heads`` the head column is the
+    leaf's theta column and Gh = G; with it the L blocks' leaves of one name are ONE head, named `shared_head_name` and placed where
+    the first block's leaf is, so Gh = G - (L - 1) (block floats)."""
+    at, out, hc = {}, [], 0
+    for l in generated_leaves(g):
+        name = l.shared_head_name if g.shared_block_heads else l.head_name
+        if name not in at:
+            at[name] = hc
+            hc += l.size
+        out.append((l, name, at[name]))
+    return out, hc
+
+
+def token_runs(g: Geometry):
+    """[(theta column, width, head column, token)]: the run table of csrc/train_layout.h (``layer_tokens``), one entry per
+    maximal run of theta columns that reads one layer token and one contiguous range of head columns -- one per generated module."""
+    runs = []
+    for l, _, h in head_columns(g)[0]:
+        t = token_of(g, l)
+        if runs and runs[-1][3] == t and runs[-1][0] + runs[-1][1] == l.offset and runs[-1][2] + runs[-1][1] == h:
+            runs[-1] = (runs[-1][0], runs[-1][1] + l.size, runs[-1][2], t)
+        else:
+            runs.append((l.offset, l.size, h, t))
+    return runs
+
+
+def _unique_heads(g: Geometry):
+    """[(leaf, head name, head column)] with every head once (a shared head under its first block's leaf)."""
+    seen, out = set(), []
+    for l, name, h in head_columns(g)[0]:
+        if name not in seen:
+            seen.add(name)
+            out.append((l, name, h))
+    return out
 
 
 def train_param_layout(g: Geometry, train_encoder: bool = False,
@@ -40,7 +78,7 @@ def train_param_layout(g: Geometry, train_encoder: bool = False,
     add("task_token_projection/kernel", (g.lang_dim, C)); add("task_token_projection/bias", (C,))
     add("initial_image_projection/kernel", (g.enc_dim, C)); add("initial_image_projection/bias", (C,))
     add("task_pos_embedding", (1, g.lang_tokens, C)); add("initial_image_pos_embedding", (1, 1, C))
-    add("layer_pos_embedding", (1, 1, C))
+    add("layer_pos_embedding", (1, g.num_layer_tokens, C))      # NL rows with layer_tokens, else the one token
     for l in range(g.ctx_layers):
         b = f"Transformer_0/encoderblock_{l}/"
         a = b + "MultiHeadDotProductAttention_0/"
@@ -53,8 +91,8 @@ def train_param_layout(g: Geometry, train_encoder: bool = False,
         add(b + "MlpBlock_0/Dense_0/kernel", (C, F)); add(b + "MlpBlock_0/Dense_0/bias", (F,))
         add(b + "MlpBlock_0/Dense_1/kernel", (F, C)); add(b + "MlpBlock_0/Dense_1/bias", (C,))
     add("Transformer_0/encoder_norm/scale", (C,)); add("Transformer_0/encoder_norm/bias", (C,))
-    G = generated_leaves(g)[-1].offset + generated_leaves(g)[-1].size
-    add("W_cat", (C, G)); add("b_cat", (G,))
+    Gh = head_columns(g)[1]                                     # == G unless shared_block_heads
+    add("W_cat", (C, Gh)); add("b_cat", (Gh,))
     if train_encoder:
         for path, shape in encoder_leaves(g):
             add(shared_name(path), (int(np.prod(shape)),))
@@ -72,7 +110,7 @@ def gradient_buckets(g: Geometry, train_encoder: bool = False, position_source: 
     layout, total = train_param_layout(g, train_encoder, position_source)
     at = {name: off for name, off, _ in layout}
     wcat = at["W_cat"]
-    n_hyper = at["b_cat"] + generated_leaves(g)[-1].offset + generated_leaves(g)[-1].size
+    n_hyper = at["b_cat"] + head_columns(g)[1]
     out = []
     if train_encoder:
         out.append(("image_encoder", n_hyper, total - n_hyper))
@@ -90,14 +128,14 @@ def pack_params(g: Geometry, params: Dict[str, np.ndarray], train_encoder: bool 
     """`position_source`: the source table itself (float32 [1, 1 + n*n, E]), packed as the tail."""
     layout, total = train_param_layout(g, train_encoder, _source_side(position_source) if train_encoder else 0)
     flat = np.zeros(total, np.float32)
-    leaves = generated_leaves(g)
+    heads = _unique_heads(g)                                   # head columns ascend in this order
     for name, off, shape in layout:
         n = int(np.prod(shape))
         if name == "W_cat":
-            w = np.concatenate([np.asarray(params[l.head_name + "/kernel"], np.float32) for l in leaves], axis=1)
+            w = np.concatenate([np.asarray(params[h + "/kernel"], np.float32) for _, h, _ in heads], axis=1)
             flat[off:off + n] = w.reshape(-1)
         elif name == "b_cat":
-            flat[off:off + n] = np.concatenate([np.asarray(params[l.head_name + "/bias"], np.float32).reshape(-1) for l in leaves])
+            flat[off:off + n] = np.concatenate([np.asarray(params[h + "/bias"], np.float32).reshape(-1) for _, h, _ in heads])
         elif name == POSITION_SOURCE:
             flat[off:off + n] = np.asarray(position_source, np.float32).reshape(-1)
         else:
@@ -109,17 +147,17 @@ def unpack_params(g: Geometry, flat: np.ndarray, train_encoder: bool = False, po
     """flat vector (parameters or gradients) -> reference-named tensors.  With `position_source` = n the result is
     (tensors, source [1, 1 + n*n, E]): the tail is no checkpoint tensor and stays out of the dict."""
     layout, _ = train_param_layout(g, train_encoder, position_source)
-    leaves = generated_leaves(g)
+    heads = _unique_heads(g)
     out: Dict[str, np.ndarray] = {}
     source = None
     for name, off, shape in layout:
         v = np.asarray(flat[off:off + int(np.prod(shape))]).reshape(shape)
         if name == "W_cat":
-            for l in leaves:
-                out[l.head_name + "/kernel"] = v[:, l.offset:l.offset + l.size].copy()
+            for l, h, c in heads:
+                out[h + "/kernel"] = v[:, c:c + l.size].copy()
         elif name == "b_cat":
-            for l in leaves:
-                out[l.head_name + "/bias"] = v[l.offset:l.offset + l.size].copy()
+            for l, h, c in heads:
+                out[h + "/bias"] = v[c:c + l.size].copy()
         elif name == POSITION_SOURCE:
             source = v.copy()
         else:
@@ -157,13 +195,12 @@ def weight_decay_mask(g: Geometry, strategy: str, train_encoder: bool = False, p
     if train_encoder and position_source:          # the tail under the leaf's name, the slot under one that no rule matches
         layout = [(POSITION_LEAF if name == POSITION_SOURCE else "" if name == POSITION_LEAF else name, off, shape)
                   for name, off, shape in layout]
-    leaves = generated_leaves(g)
-    G = leaves[-1].offset + leaves[-1].size
+    heads, Gh = _unique_heads(g), head_columns(g)[1]
     mask = np.zeros(total, np.uint8)
-    cols = np.zeros(G, np.uint8)
-    for l in leaves:
+    cols = np.zeros(Gh, np.uint8)
+    for l, _, c in heads:
         if "kernel" in l.flat_name:
-            cols[l.offset:l.offset + l.size] = 1
+            cols[c:c + l.size] = 1
     for name, off, shape in layout:
         n = int(np.prod(shape))
         if name == "":                            # the baked position table's slot (a derived quantity)
@@ -212,12 +249,11 @@ def frozen_plan(g: Geometry, frozen_keys, train_encoder: bool = False, position_
     keys = (frozen_keys,) if isinstance(frozen_keys, str) else tuple(frozen_keys)
     hit = lambda name: any(fnmatch(name.replace("/", "."), k) for k in keys)
     layout, total = train_param_layout(g, train_encoder, position_source)
-    leaves = generated_leaves(g)
-    G = leaves[-1].offset + leaves[-1].size
-    wcols, bcols = np.zeros(G, np.uint8), np.zeros(G, np.uint8)
-    for l in leaves:
-        wcols[l.offset:l.offset + l.size] = hit(l.head_name + "/kernel")
-        bcols[l.offset:l.offset + l.size] = hit(l.head_name + "/bias")
+    heads, Gh = _unique_heads(g), head_columns(g)[1]           # a shared head is frozen once: it is one range of columns
+    wcols, bcols = np.zeros(Gh, np.uint8), np.zeros(Gh, np.uint8)
+    for l, h, c in heads:
+        wcols[c:c + l.size] = hit(h + "/kernel")
+        bcols[c:c + l.size] = hit(h + "/bias")
     mask = np.zeros(total, np.uint8)
     for name, off, shape in layout:
         n = int(np.prod(shape))
@@ -446,6 +482,10 @@ class FineTuner:
     policy block runs DifferentialAttention forward and backward; the heads of the four lambda vectors and of `subln/weight` train (or
     freeze, `frozen_keys`) like every other head.  Without the keyword such a model is refused; the attention terms and the four noise
     arguments are refused with it.
+    `layer_tokens=True`: fine-tune a model with `hypernet_kwargs.share_layer_index=False` (hvla_train_layer_tokens): the
+    context encoder runs with its NL layer tokens, every generated leaf is made from the context row of its module's token, and with
+    `share_TF_output_head` the blocks' shared heads train (decay, freeze) as ONE tensor each, whose gradient is the sum over the blocks.
+    Combines with `language_tokens` and `differential`.  Without the keyword such a model is refused.
     `dropout_rate`, `image_embedding_noise`, `embedding_dropout_rate`, `image_dropout` (all 0 = off, the default; `train_noise_from_config`
     reads them from a reference-shaped config): the four noise sources the reference's loop switches on with train=True
     (hvla_train_noise_set), drawn from a counter-based generator keyed by `noise_seed` -- equal to jax's noise in
@@ -460,7 +500,7 @@ class FineTuner:
                  accept_baked_position_table: bool = False, frozen_keys=(), attention_entropy: float = 0.0,
                  attention_map_alignment: float = 0.0, num_steps=None, metrics: bool = False, task_names=(), language_tokens: bool = False,
                  dropout_rate: float = 0.0, image_embedding_noise: float = 0.0, embedding_dropout_rate: float = 0.0,
-                 image_dropout: float = 0.0, noise_seed: int = 0, differential: bool = False):
+                 image_dropout: float = 0.0, noise_seed: int = 0, differential: bool = False, layer_tokens: bool = False):
         self.attention_entropy, self.attention_map_alignment, self.num_steps = attention_loss_plan(
             attention_entropy, attention_map_alignment, num_steps)
         self.language_tokens = bool(language_tokens)
@@ -469,9 +509,13 @@ class FineTuner:
                           context_dropout=float(embedding_dropout_rate), image_dropout=float(image_dropout))
         self.noise_on = any(v != 0.0 for v in self.noise.values())
         self.noise_seed, self.noise_draw = int(noise_seed), 0
-        if getattr(model.geometry, "layer_tokens", False):
+        self.layer_tokens = bool(layer_tokens)
+        if getattr(model.geometry, "layer_tokens", False) and not self.layer_tokens:
             raise ValueError("fine-tuning a model with hypernet_kwargs.share_layer_index=False is not built; serving is "
                              "(the training kernels run one layer token and one GEMM over the output heads, DESIGN.md §24)")
+        if self.layer_tokens and not getattr(model.geometry, "layer_tokens", False):
+            raise ValueError("layer_tokens=True needs a model with hypernet_kwargs.share_layer_index=False: this model's context "
+                             "encoder has one layer token")
         if getattr(model.geometry, "differential", False) and not self.differential:
             raise ValueError("fine-tuning a model with vit_kwargs.use_differential_transformer is not built; serving is "
                              "(without differential=True the training kernels run no DifferentialAttention, DESIGN.md §23)")
@@ -617,6 +661,7 @@ class FineTuner:
         and first: the entries below refuse a use_language_token context without it)."""
         self.model._ctx.train_language_tokens(self.language_tokens)
         self.model._ctx.train_differential(self.differential)
+        self.model._ctx.train_layer_tokens(self.layer_tokens)
 
     def _select_source(self):
         """The context is the model's, shared by every FineTuner on it: each call into it first says which position table this

@@ -564,6 +564,23 @@ int hvla_train_language_tokens(hvla_ctx* ctx, int32_t on);
  * with a weight != 0 (the module's map A1 - lambda A2 is signed: no entropy) and hvla_train_noise_set with a rate or sigma != 0.
  * HVLA_E_SHAPE: on == 1 on a context created without differential_attention; any other value.  NULL ctx: HVLA_E_STATE.       */
 int hvla_train_differential(hvla_ctx* ctx, int32_t on);
+/* Fine-tune a layer_tokens context (hvla_create_with_v4; hypernet_kwargs.share_layer_index=False, the default of the reference's
+ * pretraining config, with or without share_TF_output_head).  A host-side setting kept on the context like the two above.
+ * on == 0 (always HVLA_OK) is the state of a new context: every hvla_train_* entry refuses a layer_tokens context with
+ * HVLA_E_SHAPE.  on == 1: they serve it.  The training vector then holds layer_pos_embedding as NL rows and
+ * the output heads as [C][Gh] / [Gh], Gh <= G (with shared_block_heads the blocks' leaves of one name are one tensor); the context
+ * encoder runs forward and backward on T + 1 + NL rows; the weight generation and its two gradients are one grouped launch each,
+ * whose tile tables the context keeps in device memory (allocated by the first entry that follows).  hvla_train_sizes reports the
+ * longer vector and workspace; hvla_train_publish serves the trained vector into the running context (the heads into the
+ * per-token segment blocks).  On a context created without layer_tokens on == 1 is HVLA_OK and changes nothing.
+ * HVLA_E_SHAPE: any other value of `on`.  NULL ctx: HVLA_E_STATE.                                                                 */
+int hvla_train_layer_tokens(hvla_ctx* ctx, int32_t on);
+/* Test instrumentation, like hvla_train_noise_probe: where hvla_train_step at this batch size and train_encoder value (under the
+ * current noise setting) leaves the context embedding and its gradient in buffers.work.  out[0], out[1]: the offsets in floats of
+ * ctx and d loss / d ctx, each [B][NL][ctx_dim] (NL = hvla_num_layer_tokens); out[2]: their length B NL ctx_dim.  d ctx is what the
+ * weight-generation backward wrote (rows of a token no leaf reads are zero); with the context encoder's bucket frozen it is not
+ * written.  Errors as hvla_train_sizes.                                                                                           */
+int hvla_train_context_rows(hvla_ctx* ctx, int32_t B, int32_t train_encoder, int64_t out[3]);
 /* Replaces: the four noise sources the reference's training loop switches on by running the model with train=True --
  * vit_kwargs.dropout_rate (base_vit.py:205; transformer.py:67,74,192), vit_kwargs.image_embedding_noise (base_vit.py:123-127),
  * hypernet_kwargs.embedding_dropout_rate (hypernetwork.py:193-195) and hypernet_kwargs.image_dropout (hypernetwork.py:119-122).

@@ -7,7 +7,7 @@
 // aligned like device allocations, so that the alignment and ordering tests of the sequencing see what they see in production.
 constexpr const char* TRACE_BUFFERS[] = {"params", "grads", "mu", "nu", "ema", "theta", "dtheta", "work", "loss", "actions", "logits",
                                          "sqsum", "wd_mask", "params0", "tok", "attn_mask", "cls", "tokens", "images", "target", "tmask",
-                                         "amask", "acc", "frozen", "pos_w", "aux_ref", "aux_ent", "aux_align", "event", "st"};
+                                         "amask", "acc", "frozen", "pos_w", "aux_ref", "aux_ent", "aux_align", "event", "st", "tiles"};
 constexpr int TRACE_NBUF = sizeof(TRACE_BUFFERS) / sizeof(TRACE_BUFFERS[0]);
 void* train_trace_buffer(const char* name) {
   for (int i = 0; i < TRACE_NBUF; ++i)
@@ -69,3 +69,7 @@ static void trace_arg(const NoiseKey& k) {
 #define ENQ(fn, ...) (printf("%s ", #fn), trace_list(__VA_ARGS__), (void)printf("\n"))
 // train.h's bgemm(): these builds do not compile csrc/train_gemm.hip
 void bgemm(hipStream_t, bool ta, bool tb, BG g, int nb0) { printf("bgemm "), trace_list(ta, tb, nb0, g), (void)printf("\n"); }
+// ... and its grouped form (layer tokens): the table prints as tiles+<entries>, its grid as ntiles, tile and nz
+void bgemm_groups(hipStream_t, bool ta, bool tb, BG g, const BGTile* tiles, int ntiles, int tile, int nz, bool vec_ok, double) {
+  printf("bgemm_groups "), trace_list(ta, tb, g, tiles, ntiles, tile, nz, vec_ok), (void)printf("\n");
+}

@@ -2,6 +2,7 @@
 // tools/train_extent_trace.hip): the fake buffers, the two base geometries, one traced point and the recorded sweep.
 #pragma once
 #include <cstdio>
+#include <vector>
 
 #include "train.h"
 
@@ -62,13 +63,16 @@ static int run(const Point& p, bool plan = false) {
   hipEvent_t ev[3];
   for (int i = 0; i < 3; ++i) ev[i] = reinterpret_cast<hipEvent_t>(buf<char>("event") + i);
   hipStream_t st = reinterpret_cast<hipStream_t>(buf<char>("st"));
-  if (train_refusal(g, true, true)) { printf("refused: %s\n", train_refusal(g, true, true)); return 1; }     // (a use_language_token or differential point is one that asked)
+  if (train_refusal(g, true, true, true)) { printf("refused: %s\n", train_refusal(g, true, true, true)); return 1; }     // (a use_language_token, differential or layer_tokens point is one that asked)
   const TrainLayout L = make_train_layout(g);
   if (!L.policy_ok) { printf("a policy leaf was not found\n"); return 1; }
+  std::vector<BGTile> tiles;
+  if (g.layer_tokens) opt.groups = token_groups(g, L, buf<BGTile>("tiles"), tiles);
   if (plan) {
     const long n = train_vector_elems(L, opt.ps, enc);
     printf("size params %ld\nsize grads %ld\nsize theta %ld\nsize dtheta %ld\n", n, n, (long)p.B * L.G, (long)p.B * L.G);
     printf("size tok %ld\nsize cls %ld\nsize tokens %ld\n", (long)p.B * g.T * g.lang_dim, (long)p.B * g.E, enc ? 0L : (long)p.B * g.P() * g.E);
+    if (g.layer_tokens) printf("size tiles %zu\n", tiles.size());
     train_trace_plan(g, p.B, enc, opt.noise);
   }
   printf("step\n");
