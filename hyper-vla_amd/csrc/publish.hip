@@ -97,27 +97,18 @@ __global__ void __launch_bounds__(256) publish_transpose_kernel(const float* __r
 // 1 KiB per plane, each a contiguous run of the output (element ((pt KS + ks) 64 + lane) 8 + j), written 16 bytes per thread.
 // perm < 0 (padding): zeros, as the host packer leaves them.
 constexpr int WC_RUN = 16;
-__global__ void __launch_bounds__(256) publish_wcat_kernel(const float* __restrict__ wcat, const float* __restrict__ bsrc,
-                                                           const int32_t* __restrict__ perm, uint16_t* __restrict__ hi,
-                                                           uint16_t* __restrict__ lo, float* __restrict__ bc, int G, int ntiles, int KS) {
-  __shared__ uint4 stage[2][WC_RUN * 64];          // [plane][tile][lane]: 8 bf16 each
-  const int pt0 = blockIdx.x * WC_RUN;
+// The k-step loop of both W_cat kernels: this thread's two columns gather column ref[c] of wcat [16 KS][ld] (ref < 0: zeros) into LDS
+// slot[c]; the staged k-step goes out as fragment blocks blk0 .. blk0 + WC_RUN - 1, those below nblk.
+__device__ __forceinline__ void wcat_ksteps(const float* __restrict__ wcat, int ld, const int (&ref)[2], const int (&slot)[2], int blk0,
+                                            int nblk, int KS, uint16_t* __restrict__ hi, uint16_t* __restrict__ lo) {
+  __shared__ uint4 stage[2][WC_RUN * 64];          // [plane][block][lane]: 8 bf16 each
   const int tid = threadIdx.x;
-  int ref[2], slot[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int col = tid + 256 * c, tl = col >> 5, tau = col & 31;
-    const bool live = pt0 + tl < ntiles;
-    ref[c] = live ? perm[(size_t)pt0 * 32 + col] : -1;
-    slot[c] = tl * 64 + rho_of_tau(tau);
-    if (live) bc[(size_t)pt0 * 32 + col] = ref[c] >= 0 ? bsrc[ref[c]] : 0.f;
-  }
   for (int ks = 0; ks < KS; ++ks) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       float w[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) w[r] = ref[c] >= 0 ? wcat[(size_t)(16 * ks + r) * G + ref[c]] : 0.f;
+      for (int r = 0; r < 16; ++r) w[r] = ref[c] >= 0 ? wcat[(size_t)(16 * ks + r) * ld + ref[c]] : 0.f;
 #pragma unroll
       for (int hk = 0; hk < 2; ++hk) {
         uint32_t h[4], l[4];
@@ -136,15 +127,32 @@ __global__ void __launch_bounds__(256) publish_wcat_kernel(const float* __restri
     __syncthreads();
 #pragma unroll
     for (int i = tid; i < WC_RUN * 64; i += 256) {
-      const int tl = i >> 6, pt = pt0 + tl;
-      if (pt < ntiles) {
-        const size_t o = ((size_t)pt * KS + ks) * 64 + (i & 63);      // in 16-byte units
+      const int blk = blk0 + (i >> 6);
+      if (blk < nblk) {
+        const size_t o = ((size_t)blk * KS + ks) * 64 + (i & 63);      // in 16-byte units
         reinterpret_cast<uint4*>(hi)[o] = stage[0][i];
         reinterpret_cast<uint4*>(lo)[o] = stage[1][i];
       }
     }
     __syncthreads();
   }
+}
+
+__global__ void __launch_bounds__(256) publish_wcat_kernel(const float* __restrict__ wcat, const float* __restrict__ bsrc,
+                                                           const int32_t* __restrict__ perm, uint16_t* __restrict__ hi,
+                                                           uint16_t* __restrict__ lo, float* __restrict__ bc, int G, int ntiles, int KS) {
+  const int pt0 = blockIdx.x * WC_RUN;
+  const int tid = threadIdx.x;
+  int ref[2], slot[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = tid + 256 * c, tl = col >> 5, tau = col & 31;
+    const bool live = pt0 + tl < ntiles;
+    ref[c] = live ? perm[(size_t)pt0 * 32 + col] : -1;
+    slot[c] = tl * 64 + rho_of_tau(tau);
+    if (live) bc[(size_t)pt0 * 32 + col] = ref[c] >= 0 ? bsrc[ref[c]] : 0.f;
+  }
+  wcat_ksteps(wcat, G, ref, slot, pt0, ntiles, KS, hi, lo);
 }
 
 // ---- the same for a layer-token model: one fragment block per SEGMENT (pack.h TokenSegments) ----
@@ -157,7 +165,6 @@ __global__ void __launch_bounds__(256) publish_wcat_segments_kernel(const float*
                                                                     const int32_t* __restrict__ seg_tile, const int32_t* __restrict__ seg_token,
                                                                     uint16_t* __restrict__ hi, uint16_t* __restrict__ lo, float* __restrict__ bc,
                                                                     int Gh, int nseg, int KS) {
-  __shared__ uint4 stage[2][WC_RUN * 64];          // [plane][segment][lane]: 8 bf16 each
   const int q0 = blockIdx.x * WC_RUN;
   const int tid = threadIdx.x;
   int ref[2], slot[2];
@@ -174,39 +181,7 @@ __global__ void __launch_bounds__(256) publish_wcat_segments_kernel(const float*
       }
     }
   }
-  for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      float w[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) w[r] = ref[c] >= 0 ? wcat[(size_t)(16 * ks + r) * Gh + ref[c]] : 0.f;
-#pragma unroll
-      for (int hk = 0; hk < 2; ++hk) {
-        uint32_t h[4], l[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          uint16_t h0, l0, h1, l1;
-          split_pair(w[8 * hk + 2 * j], h0, l0);
-          split_pair(w[8 * hk + 2 * j + 1], h1, l1);
-          h[j] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-          l[j] = (uint32_t)l0 | ((uint32_t)l1 << 16);
-        }
-        stage[0][slot[c] + 32 * hk] = make_uint4(h[0], h[1], h[2], h[3]);
-        stage[1][slot[c] + 32 * hk] = make_uint4(l[0], l[1], l[2], l[3]);
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = tid; i < WC_RUN * 64; i += 256) {
-      const int q = q0 + (i >> 6);
-      if (q < nseg) {
-        const size_t o = ((size_t)q * KS + ks) * 64 + (i & 63);      // in 16-byte units
-        reinterpret_cast<uint4*>(hi)[o] = stage[0][i];
-        reinterpret_cast<uint4*>(lo)[o] = stage[1][i];
-      }
-    }
-    __syncthreads();
-  }
+  wcat_ksteps(wcat, Gh, ref, slot, q0, nseg, KS, hi, lo);
 }
 
 hipError_t launch_publish(const PublishArgs& a, hipStream_t st) {

@@ -826,74 +826,10 @@ __global__ __launch_bounds__(256) void attention_aux_kernel(AuxP a) {
   }
 }
 
-// context-token assembly: rows t < T += pos_tok[t]; row T += pos_img; row T+1 = pos_layer (hypernetwork.py:112-145)
-__global__ void ctx_rows_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
-                                const float* __restrict__ pos_layer, int B, int T, int C) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int Sc = T + 2;
-  if (i >= (long)B * Sc * C) return;
-  const int c = (int)(i % C), t = (int)((i / C) % Sc);
-  if (t < T) x[i] += pos_tok[(long)t * C + c];
-  else if (t == T) x[i] += pos_img[c];
-  else x[i] = pos_layer[c];
-}
-__global__ void ctx_rows_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
-                                    float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
-                                    int B, int T, int C) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const int Sc = T + 2;
-  if (i >= (long)B * Sc * C) return;
-  const int c = (int)(i % C), t = (int)((i / C) % Sc);
-  const float v = dx[i];
-  if (t < T) { unsafeAtomicAdd(dpos_tok + (long)t * C + c, v); unsafeAtomicAdd(db_tok + c, v); }
-  else if (t == T) { unsafeAtomicAdd(dpos_img + c, v); unsafeAtomicAdd(db_img + c, v); }
-  else unsafeAtomicAdd(dpos_layer + c, v);
-}
-// ctx[b] = (LN(x_b) * scale + bias) * post   (encoder_norm on the layer-token row, hypernetwork.py:188-192)
-__global__ void ctx_final_fwd_kernel(const float* __restrict__ x, long xstride, float* __restrict__ xhat,
-                                     float* __restrict__ mean, float* __restrict__ rstd, const float* __restrict__ scale,
-                                     const float* __restrict__ bias, float* __restrict__ ctx, int B, int C, float post) {
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (b >= B) return;
-  const float* xr = x + (long)b * xstride;
-  float s = 0.f, q = 0.f;
-  for (int c = lane; c < C; c += 64) { s += xr[c]; q += xr[c] * xr[c]; }
-  for (int o = 32; o; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
-  const float m = s / C, var = fmaxf(0.f, q / C - m * m), r = rsqrtf(var + 1e-6f);
-  for (int c = lane; c < C; c += 64) {
-    const float xh = (xr[c] - m) * r;
-    xhat[(long)b * C + c] = xh;
-    ctx[(long)b * C + c] = (xh * scale[c] + bias[c]) * post;
-  }
-  if (lane == 0) { mean[b] = m; rstd[b] = r; }
-}
-__global__ void ctx_final_bwd_kernel(const float* __restrict__ x, long xstride, const float* __restrict__ dctx,
-                                     const float* __restrict__ mean, const float* __restrict__ rstd,
-                                     const float* __restrict__ scale, float* __restrict__ dx, float* __restrict__ dscale,
-                                     float* __restrict__ dbias, int B, int C, float post) {
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (b >= B) return;
-  const float* xr = x + (long)b * xstride;
-  const float m = mean[b], r = rstd[b];
-  float s1 = 0.f, s2 = 0.f;
-  for (int c = lane; c < C; c += 64) {
-    const float xh = (xr[c] - m) * r, dy = dctx[(long)b * C + c] * post, dxh = dy * scale[c];
-    s1 += dxh; s2 += dxh * xh;
-  }
-  for (int o = 32; o; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
-  for (int c = lane; c < C; c += 64) {
-    const float xh = (xr[c] - m) * r, dy = dctx[(long)b * C + c] * post, dxh = dy * scale[c];
-    dx[(long)b * xstride + c] += r * (dxh - s1 / C - xh * s2 / C);
-    unsafeAtomicAdd(dscale + c, dy * xh);
-    unsafeAtomicAdd(dbias + c, dy);
-  }
-}
-
-// The same four with NL layer tokens, Sc = T + 1 + NL rows per episode: rows T + 1 .. Sc - 1 start as the rows of
-// pos_layer [NL][C], dpos_layer[j] = sum_b dx[b][T + 1 + j]; the final LayerNorm and scale run over the last NL rows of every episode,
-// row = b NL + j of ctx / xhat / dctx [B][NL][C] and mean / rstd [B NL], one wave per row.  Kernels of their own, as above.
-__global__ void ctx_rows_tokens_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
-                                       const float* __restrict__ pos_layer, int B, int T, int NL, int C) {
+// context-token assembly with NL layer tokens, Sc = T + 1 + NL rows per episode: rows t < T += pos_tok[t]; row T += pos_img; rows
+// T + 1 + j = pos_layer[j] (hypernetwork.py:112-145).  share_layer_index=True is NL = 1; the _tokens kernels take NL.
+__device__ __forceinline__ void ctx_rows_fwd(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
+                                             const float* __restrict__ pos_layer, int B, int T, int NL, int C) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int Sc = T + 1 + NL;
   if (i >= (long)B * Sc * C) return;
@@ -902,9 +838,10 @@ __global__ void ctx_rows_tokens_kernel(float* __restrict__ x, const float* __res
   else if (t == T) x[i] += pos_img[c];
   else x[i] = pos_layer[(long)(t - T - 1) * C + c];
 }
-__global__ void ctx_rows_tokens_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
-                                           float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
-                                           int B, int T, int NL, int C) {
+// dpos_layer[j] = sum_b dx[b][T + 1 + j]
+__device__ __forceinline__ void ctx_rows_bwd(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
+                                             float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
+                                             int B, int T, int NL, int C) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int Sc = T + 1 + NL;
   if (i >= (long)B * Sc * C) return;
@@ -914,12 +851,12 @@ __global__ void ctx_rows_tokens_bwd_kernel(const float* __restrict__ dx, float* 
   else if (t == T) { unsafeAtomicAdd(dpos_img + c, v); unsafeAtomicAdd(db_img + c, v); }
   else unsafeAtomicAdd(dpos_layer + (long)(t - T - 1) * C + c, v);
 }
-__global__ void ctx_final_tokens_fwd_kernel(const float* __restrict__ x, int Sc, int NL, float* __restrict__ xhat,
-                                            float* __restrict__ mean, float* __restrict__ rstd, const float* __restrict__ scale,
-                                            const float* __restrict__ bias, float* __restrict__ ctx, int rows, int C, float post) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float* xr = x + ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C;
+// ctx[row] = (LN(xr) * scale + bias) * post   (encoder_norm on a layer-token row, hypernetwork.py:188-192); one wave per row of
+// ctx / xhat [rows][C] and mean / rstd [rows], xr the row's place in the context stream
+__device__ __forceinline__ void ctx_final_fwd_row(const float* __restrict__ xr, int row, float* __restrict__ xhat, float* __restrict__ mean,
+                                                  float* __restrict__ rstd, const float* __restrict__ scale, const float* __restrict__ bias,
+                                                  float* __restrict__ ctx, int C, float post) {
+  const int lane = threadIdx.x & 63;
   float s = 0.f, q = 0.f;
   for (int c = lane; c < C; c += 64) { s += xr[c]; q += xr[c] * xr[c]; }
   for (int o = 32; o; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
@@ -931,14 +868,11 @@ __global__ void ctx_final_tokens_fwd_kernel(const float* __restrict__ x, int Sc,
   }
   if (lane == 0) { mean[row] = m; rstd[row] = r; }
 }
-__global__ void ctx_final_tokens_bwd_kernel(const float* __restrict__ x, int Sc, int NL, const float* __restrict__ dctx,
-                                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                                            const float* __restrict__ scale, float* __restrict__ dx, float* __restrict__ dscale,
-                                            float* __restrict__ dbias, int rows, int C, float post) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const long xo = ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C;
-  const float* xr = x + xo;
+__device__ __forceinline__ void ctx_final_bwd_row(const float* __restrict__ xr, float* __restrict__ dxr, int row, const float* __restrict__ dctx,
+                                                  const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                  const float* __restrict__ scale, float* __restrict__ dscale, float* __restrict__ dbias,
+                                                  int C, float post) {
+  const int lane = threadIdx.x & 63;
   const float m = mean[row], r = rstd[row];
   float s1 = 0.f, s2 = 0.f;
   for (int c = lane; c < C; c += 64) {
@@ -948,10 +882,63 @@ __global__ void ctx_final_tokens_bwd_kernel(const float* __restrict__ x, int Sc,
   for (int o = 32; o; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
   for (int c = lane; c < C; c += 64) {
     const float xh = (xr[c] - m) * r, dy = dctx[(long)row * C + c] * post, dxh = dy * scale[c];
-    dx[xo + c] += r * (dxh - s1 / C - xh * s2 / C);
+    dxr[c] += r * (dxh - s1 / C - xh * s2 / C);
     unsafeAtomicAdd(dscale + c, dy * xh);
     unsafeAtomicAdd(dbias + c, dy);
   }
+}
+
+__global__ void ctx_rows_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
+                                const float* __restrict__ pos_layer, int B, int T, int C) {
+  ctx_rows_fwd(x, pos_tok, pos_img, pos_layer, B, T, 1, C);
+}
+__global__ void ctx_rows_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
+                                    float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
+                                    int B, int T, int C) {
+  ctx_rows_bwd(dx, dpos_tok, dpos_img, dpos_layer, db_tok, db_img, B, T, 1, C);
+}
+// one layer token: x / dx point at episode 0's last row, xstride from one episode's to the next's
+__global__ void ctx_final_fwd_kernel(const float* __restrict__ x, long xstride, float* __restrict__ xhat,
+                                     float* __restrict__ mean, float* __restrict__ rstd, const float* __restrict__ scale,
+                                     const float* __restrict__ bias, float* __restrict__ ctx, int B, int C, float post) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  ctx_final_fwd_row(x + (long)b * xstride, b, xhat, mean, rstd, scale, bias, ctx, C, post);
+}
+__global__ void ctx_final_bwd_kernel(const float* __restrict__ x, long xstride, const float* __restrict__ dctx,
+                                     const float* __restrict__ mean, const float* __restrict__ rstd,
+                                     const float* __restrict__ scale, float* __restrict__ dx, float* __restrict__ dscale,
+                                     float* __restrict__ dbias, int B, int C, float post) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  ctx_final_bwd_row(x + (long)b * xstride, dx + (long)b * xstride, b, dctx, mean, rstd, scale, dscale, dbias, C, post);
+}
+
+// NL layer tokens: x / dx are the whole stream [B][Sc][C], row = b NL + j of ctx / xhat / dctx [B][NL][C] is stream row T + 1 + j of episode b
+__global__ void ctx_rows_tokens_kernel(float* __restrict__ x, const float* __restrict__ pos_tok, const float* __restrict__ pos_img,
+                                       const float* __restrict__ pos_layer, int B, int T, int NL, int C) {
+  ctx_rows_fwd(x, pos_tok, pos_img, pos_layer, B, T, NL, C);
+}
+__global__ void ctx_rows_tokens_bwd_kernel(const float* __restrict__ dx, float* __restrict__ dpos_tok, float* __restrict__ dpos_img,
+                                           float* __restrict__ dpos_layer, float* __restrict__ db_tok, float* __restrict__ db_img,
+                                           int B, int T, int NL, int C) {
+  ctx_rows_bwd(dx, dpos_tok, dpos_img, dpos_layer, db_tok, db_img, B, T, NL, C);
+}
+__global__ void ctx_final_tokens_fwd_kernel(const float* __restrict__ x, int Sc, int NL, float* __restrict__ xhat,
+                                            float* __restrict__ mean, float* __restrict__ rstd, const float* __restrict__ scale,
+                                            const float* __restrict__ bias, float* __restrict__ ctx, int rows, int C, float post) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  ctx_final_fwd_row(x + ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C, row, xhat, mean, rstd, scale, bias, ctx, C, post);
+}
+__global__ void ctx_final_tokens_bwd_kernel(const float* __restrict__ x, int Sc, int NL, const float* __restrict__ dctx,
+                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                            const float* __restrict__ scale, float* __restrict__ dx, float* __restrict__ dscale,
+                                            float* __restrict__ dbias, int rows, int C, float post) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long xo = ((long)(row / NL) * Sc + (Sc - NL) + row % NL) * C;
+  ctx_final_bwd_row(x + xo, dx + xo, row, dctx, mean, rstd, scale, dscale, dbias, C, post);
 }
 // db_h[hcols] += sum_b dtheta[b, run] for every run in one launch (the grouped form of colsum_kernel): a workgroup is one 64-column
 // tile of the forward's table (train_layout.h group_tiles kind 0: c = theta column origin, bias = head column origin), blockIdx.z a
@@ -1549,7 +1536,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     block_fwd(st, B, Sc, C, Hc, Fc, 0, bind(Pm, L.layer[l]), cb[l], l + 1 < g.ctx_layers ? cb[l + 1].x_in : cx_fin, t, ctx_opt);
   // ctx = LN_f(x[:, -1]) (/ sqrt(C)); rows gathered through a stride: x = cx_fin + (Sc-1)*C, row stride Sc*C
   if (lt) KL(ctx_final_tokens_fwd_kernel, dim3((B * NL + 3) / 4), dim3(256), cx_fin, Sc, NL, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B * NL, C, cpost);
-  else KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+  else KL(ctx_final_fwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, ctxn, cmean, crstd, Pm + L.norm_s, Pm + L.norm_b, ctx, B, C, cpost);
   if (cdrop.on()) dropout_fwd(st, cdrop, NOISE_CONTEXT, 0, ctx, nullptr, ctx, B, (long)NL * C);      // embedding_dropout_rate (hypernetwork.py:193-195)
   // =============================== theta = ctx W_cat + b_cat (hypernetwork.py:205-233) ===============================
   // layer tokens: theta[b, run] = ctx[b, token(run)] W_h[:, hcols(run)] + b_h[hcols(run)], every run in ONE grouped launch; the K order of
@@ -1651,7 +1638,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   if (ctx_on) {
     ENQ(hipMemsetAsync, cdx, 0, (size_t)B * Sc * C * 4, st);
     if (lt) KL(ctx_final_tokens_bwd_kernel, dim3((B * NL + 3) / 4), dim3(256), cx_fin, Sc, NL, dctx, cmean, crstd, Pm + L.norm_s, cdx, Gm + L.norm_s, Gm + L.norm_b, B * NL, C, cpost);
-    else KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, g.scale_context ? 1.f / sqrtf((float)C) : 1.f);
+    else KL(ctx_final_bwd_kernel, dim3((B + 3) / 4), dim3(256), cx_fin + (long)(Sc - 1) * C, (long)Sc * C, dctx, cmean, crstd, Pm + L.norm_s, cdx + (long)(Sc - 1) * C, Gm + L.norm_s, Gm + L.norm_b, B, C, cpost);
     for (int l = g.ctx_layers - 1; l >= 0; --l)
       block_bwd(st, B, Sc, C, Hc, Fc, 0, 0, bind(Pm, L.layer[l]), bind(Gm, L.layer[l]), cb[l], cdx, t, ctx_opt);
     // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer

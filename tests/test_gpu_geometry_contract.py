@@ -137,6 +137,7 @@ CONTEXT_EDGES = {
     "2 tokens (S = 4)": (dict(lang_tokens=2), 5),
     "38 tokens of 20 (third key tile ragged, one short K chunk)": (dict(lang_tokens=38, lang_dim=20), 5),
     "38 tokens of 20, two episode tiles": (dict(lang_tokens=38, lang_dim=20), 37),
+    "14 tokens (S = 16, the last row of the first tile)": (dict(lang_tokens=14), 3),
     "15 tokens, ctx_mlp 48": (dict(lang_tokens=15, ctx_mlp=48), 5),
     "head width 4 (32 / 8), ctx_mlp 16": (dict(ctx_dim=32, ctx_heads=8, ctx_mlp=16), 5),
     "one head of 128": (dict(ctx_dim=128, ctx_heads=1), 5),

@@ -65,6 +65,8 @@ def _parity(g, B, what):
 
 CASES = {
     "mid_two_row_tiles": (dict(), 3),                                            # S = 20
+    "last_row_of_the_second_tile": (dict(lang_tokens=24), 3),                    # S = 32
+    "first_row_of_the_third_tile": (dict(lang_tokens=25), 3),                    # S = 33
     "three_row_tiles": (dict(lang_tokens=26), 1),                                # S = 34
     "last_row_of_the_last_tile": (dict(layers=4, lang_tokens=38), 2),            # S = 48
     "ks2": (dict(ctx_dim=32, ctx_heads=2), 3),
