@@ -39,6 +39,54 @@ void bgemm(hipStream_t st, bool ta, bool tb, BG g, int nb0);
 // `flops`: the product's f32-equivalent work for the launch timer.  The same staging, hi / lo split, three-MFMA core and store
 // modes as bgemm()'s kernel, in a kernel of its own.
 void bgemm_groups(hipStream_t st, bool ta, bool tb, BG g, const BGTile* tiles, int ntiles, int tile, int nz, bool vec_ok, double flops);
+// One operand of a product: its base, leading dimension and the strides of the outer (b0) and inner (b1) batch index.  T = float
+// converts to T = const float and not back: only an Out names a C.
+template <class T> struct Operand {
+  T* p; int ld; long s0, s1;
+  Operand(T* p_, int ld_, long s0_ = 0, long s1_ = 0) : p(p_), ld(ld_), s0(s0_), s1(s1_) {}
+  template <class U> Operand(const Operand<U>& o) : p(o.p), ld(o.ld), s0(o.s0), s1(o.s1) {}
+};
+using In = Operand<const float>;
+using Out = Operand<float>;
+// the shapes the step's operands have, by name:
+// one matrix for every batch -- shared weights, or [nb][S][ld] activations with the batch folded into M
+template <class T> Operand<T> mat(T* p, int ld) { return {p, ld}; }
+// [nb][n][ld]: n rows a sample (a product may use fewer: the first T of a context block's Sc rows)
+template <class T> Operand<T> per_sample(T* p, int n, int ld) { return {p, ld, (long)n * ld}; }
+// a matrix per episode at any stride (a generated leaf in its row of theta: stride G)
+template <class T> Operand<T> per_episode(T* p, int ld, long stride) { return {p, ld, stride}; }
+// matrices `step` apart as the inner batch b1 (q, k, v in one product), the same for every b0
+template <class T> Operand<T> inner_batch(T* p, int ld, long step) { return {p, ld, 0, step}; }
+// head b1 of an activation [nb][S][D]: columns [b1 w, b1 w + w), w = hd (w = hd / 2: the 2 H sub-heads of DifferentialAttention)
+template <class T> Operand<T> head_slice(T* x, int S, int D, int w) { return {x, D, (long)S * D, w}; }
+// The S x S attention matrices have row stride Sp = S rounded up to 4 floats, zeros behind every row (written by the softmax kernels):
+// as A operands (a_padded) they are staged with float4 loads like everything else (S = 257: the all-dword staging these four
+// products per layer were left with cost 3.6 ms per step).  A block keeps Hn = H tables a sample, 2 H under DifferentialAttention.
+inline int score_stride(int S) { return (S + 3) & ~3; }
+inline long score_floats(long H, long S, bool differential = false) { return (differential ? 2 * H : H) * S * score_stride((int)S); }
+// the score tables [nb][Hn][S][Sp], table b1 of sample b0
+template <class T> Operand<T> score_table(T* p, int Hn, int S) { return {p, score_stride(S), score_floats(Hn, S), (long)S * score_stride(S)}; }
+// what a product does with C
+enum class Store {
+  Set,          // C = ...
+  Add,          // C += ..., one writer per element
+  Atomic,       // atomic C += ...: batches share C
+  AddSplitK,    // C += ..., and the launcher may cut K into chunks reduced with atomics (BG::allow_split)
+};
+// C[b0, b1] = / += alpha op(A)[b0, b1] op(B)[b0, b1], op(A) M x K and op(B) K x N, nb1 inner batches; bgemm()'s nb0 gives the outer count
+inline BG product(In A, In B, Out C, int M, int N, int K, Store store = Store::Set, float alpha = 1.f, int nb1 = 1) {
+  BG g{A.p, B.p, C.p, nullptr};
+  g.M = M; g.N = N; g.K = K; g.lda = A.ld; g.ldb = B.ld; g.ldc = C.ld;
+  g.sA0 = A.s0; g.sA1 = A.s1; g.sB0 = B.s0; g.sB1 = B.s1; g.sC0 = C.s0; g.sC1 = C.s1; g.sBias0 = 0;
+  g.nb1 = nb1; g.alpha = alpha;
+  g.accumulate = store == Store::Set ? 0 : store == Store::Atomic ? 2 : 1;
+  g.allow_split = store == Store::AddSplitK;
+  return g;
+}
+// ... + bias[b0, b1][n] (nullable)
+inline BG with_bias(BG g, const float* bias, long s0 = 0, long s1 = 0) { g.bias = bias; g.sBias0 = s0; g.sBias1 = s1; return g; }
+// ... whose A is score tables: zeros up to a multiple of 4 floats behind every row
+inline BG a_padded(BG g) { g.a_padded = 1; return g; }
 void train_gemm_timer(bool on, bool first_use_by_this_context);                  // hvla_train_profile (the current device's timer; counts its users)
 void train_gemm_timer_release();                                                 // hvla_destroy of a context that used it: the events go with the last user
 hipError_t train_gemm_timer_read(float* ms, double* flops, int* launches);      // since the last read

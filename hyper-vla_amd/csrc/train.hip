@@ -1078,8 +1078,6 @@ template <class T> static Blk<T> bind(T* base, const BlockLeaves& y) {
   return Blk<T>{at(y.ln0_s), at(y.ln0_b), at(y.wq), at(y.bq), at(y.wk), at(y.bk), at(y.wv), at(y.bv), at(y.wo), at(y.bo),
                 at(y.ln1_s), at(y.ln1_b), at(y.w1), at(y.b1), at(y.w2), at(y.b2), at(y.ls1), at(y.ls2)};
 }
-// block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
-// HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention)
 // one dropout rate with its key (noise.h): thr == 0 is off, and nothing is launched
 struct Drop {
   uint32_t thr = 0; float keep_prob = 1.f; NoiseKey key;
@@ -1088,31 +1086,82 @@ struct Drop {
   bool on() const { return thr > 0; }
   NoiseKey at(uint32_t kind, int layer = 0) const { NoiseKey k = key; k.site = kind | (uint32_t)layer << 8; return k; }
 };
-struct BlkOpt { int mask_mode; const int64_t* am; int gelu_erf; int lang_T = 0; int mask_as_bias = 0;     // lang_T > 0: the policy's mask with T language rows in front;
-                Drop drop; int layer = 0;                                                                 // mask_as_bias: the policy's mask added to the scores (softmax_bias_fwd_kernel);
-                                                                                                          // drop: vit_kwargs.dropout_rate at the sites of `layer` (the policy only)
-                int differential = 0; DiffLeaves dif{-1, -1, -1, -1, -1};                                 // differential: DifferentialAttention with the block's five vectors at
-                const float* theta = nullptr; float* dtheta = nullptr;                                    // dif in a row of theta / dtheta (row stride ws), depth `layer`
-                float lambda_init() const { return (float)(0.8 - 0.6 * exp(-0.3 * (double)layer)); }      // differential_transformer.py:75-79
-                int layer_rows = 0; };                                                                    // > 0: the context encoder's mask with this many layer tokens (softmax_tokens_fwd_kernel)
+// block flavour: the flax Encoder1DBlock of the context encoder / generated policy (tanh GELU, masked attention) or the
+// HF Dinov2Layer (erf GELU, LayerScale on both residual branches, dense attention).  Its attention, one value per case that exists:
+enum class Attn {
+  Dense,            // DINOv2: no mask
+  Context,          // the context encoder's mask from am (hypernetwork.py:149-181)
+  ContextTokens,    // ... with NL layer tokens behind the image row (softmax_tokens_fwd_kernel)
+  Policy,           // the policy's mask (base_vit.py:209-214)
+  PolicyLang,       // ... with T language rows in front (softmax_lang_fwd_kernel)
+  Bias,             // the policy's mask added to the scores (softmax_bias_fwd_kernel)
+  Differential,     // DifferentialAttention
+};
+struct BlkOpt {
+  Attn attn = Attn::Dense;
+  // erf GELU (the HF Dinov2Layer), else tanh
+  int gelu_erf = 0;
+  // Context, ContextTokens: attn_mask [B][T]
+  const int64_t* am = nullptr;
+  // PolicyLang: the language rows.  ContextTokens: the layer tokens
+  int T = 0, NL = 0;
+  // the policy only: vit_kwargs.dropout_rate at the sites of `layer`, the block's depth
+  Drop drop;
+  int layer = 0;
+  // Differential: the block's five vectors at dif in a row of theta / dtheta (row stride ws)
+  DiffLeaves dif{-1, -1, -1, -1, -1};
+  const float* theta = nullptr;
+  float* dtheta = nullptr;
+  float lambda_init() const { return (float)(0.8 - 0.6 * exp(-0.3 * (double)layer)); }      // differential_transformer.py:75-79
+  bool differential() const { return attn == Attn::Differential; }
+  // The key bias adds q . bk / sqrt(hd) to every kept score of a query's row, and a softmax row ignores a constant: its gradient is
+  // zero under any mask (sum_k ds[q][k] = 0).  What the column sum of dk gives instead is the operand rounding of ds in dk = ds^T q,
+  // and a language query's few keys carry ds entries of the size of dp: with the language rows the leaf is left at the zero it is
+  // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.  With the mask added as a
+  // bias every query has every key, the constant is still one per row, and the leaf is left at zero in the same way:
+  // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.  Under the policy's
+  // dropout (hvla_train_noise) the kept activations are 1 / keep_prob larger and the same rounding came to 1.5e-3 at MID: left at zero too.
+  bool key_bias_grad_is_rounding() const { return attn == Attn::PolicyLang || attn == Attn::Bias || drop.on(); }
+};
 // dP, t2 (a DifferentialAttention policy only, else nullptr): dp = dO V^T [nb][H][S][Sp] and the row sums sum_k dp A2 [nb][H][S];
 // dp is then ds [nb][2 H][S][Sp]
 struct BlkTmp { float *h, *g, *d, *dq, *dk, *dv, *dp, *y, *dP, *t2; };
 
 // Y[nb][S][N] (+)= X[nb][S][K] W + bias with W per episode (ws = G) or shared (ws = 0: the batch folds into M, so
 // S = 257 does not pay a mostly empty 64-row tile per sample)
-static void linear(hipStream_t st, int nb, int S, long ws, const float* X, const float* W, const float* bias, float* Y, int K, int N, int acc) {
-  if (ws == 0) bgemm(st, false, false, BG{X, W, Y, bias, nb * S, N, K, K, N, N, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, acc}, 1);
-  else bgemm(st, false, false, BG{X, W, Y, bias, S, N, K, K, N, N, (long)S * K, 0, ws, 0, (long)S * N, 0, ws, 1, 1.f, acc}, nb);
+static void linear(hipStream_t st, int nb, int S, long ws, const float* X, const float* W, const float* bias, float* Y, int K, int N, Store store = Store::Set) {
+  if (ws == 0) bgemm(st, false, false, with_bias(product(mat(X, K), mat(W, N), mat(Y, N), nb * S, N, K, store), bias), 1);
+  else bgemm(st, false, false, with_bias(product(per_sample(X, S, K), per_episode(W, N, ws), per_sample(Y, S, N), S, N, K, store), bias, ws), nb);
 }
 // dX[nb][S][K] (+)= dY[nb][S][N] W^T
-static void linear_dx(hipStream_t st, int nb, int S, long ws, const float* dY, const float* W, float* dX, int K, int N, int acc) {
-  if (ws == 0) bgemm(st, false, true, BG{dY, W, dX, nullptr, nb * S, K, N, N, N, K, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, acc}, 1);
-  else bgemm(st, false, true, BG{dY, W, dX, nullptr, S, K, N, N, N, K, (long)S * N, 0, ws, 0, (long)S * K, 0, 0, 1, 1.f, acc}, nb);
+static void linear_dx(hipStream_t st, int nb, int S, long ws, const float* dY, const float* W, float* dX, int K, int N, Store store = Store::Set) {
+  if (ws == 0) bgemm(st, false, true, product(mat(dY, N), mat(W, N), mat(dX, K), nb * S, K, N, store), 1);
+  else bgemm(st, false, true, product(per_sample(dY, S, N), per_episode(W, N, ws), per_sample(dX, S, K), S, K, N, store), nb);
+}
+// the attention products over Hn heads of width w: p_h = alpha q_h k_h^T into the score tables, and y_h = alpha p_h x_h (ta: p_h^T x_h)
+static void scores(hipStream_t st, int nb, int S, int D, const float* q, const float* k, float* p, int Hn, int w, float alpha = 1.f) {
+  bgemm(st, false, true, product(head_slice(q, S, D, w), head_slice(k, S, D, w), score_table(p, Hn, S), S, S, w, Store::Set, alpha, Hn), nb);
+}
+static void apply_scores(hipStream_t st, bool ta, int nb, int S, int D, const float* p, const float* x, float* y, int Hn, int w, float alpha = 1.f) {
+  bgemm(st, ta, false, a_padded(product(score_table(p, Hn, S), head_slice(x, S, D, w), head_slice(y, S, D, w), S, w, S, Store::Set, alpha, Hn)), nb);
+}
+// every pointer on a 16-byte boundary (the float4 forms)
+template <class... T> static bool aligned16(const T*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+// q, k, v (0, 1, 2) in the memory order of p[] -- or in `order`, when given -- and whether the three are equally spaced, `step` apart
+struct Spacing { int ord[3]; long step; bool even; };
+template <class T> static Spacing spacing(T* const* p, const int* order = nullptr) {
+  Spacing s{{0, 1, 2}, 0, false};
+  for (int i = 0; i < 2 && !order; ++i)
+    for (int j = 0; j < 2 - i; ++j)
+      if (p[s.ord[j]] > p[s.ord[j + 1]]) { const int tsw = s.ord[j]; s.ord[j] = s.ord[j + 1]; s.ord[j + 1] = tsw; }
+  for (int i = 0; i < 3 && order; ++i) s.ord[i] = order[i];
+  s.step = p[s.ord[1]] - p[s.ord[0]];
+  s.even = p[s.ord[2]] - p[s.ord[1]] == s.step;
+  return s;
 }
 
 static void scale_add(hipStream_t st, float* out, const float* res, const float* y, const float* ls, long n, int D) {
-  const bool v4 = D % 4 == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(ls)) & 15) == 0;
+  const bool v4 = D % 4 == 0 && aligned16(out, res, y, ls);
   if (v4) KL(scale_add4_kernel, g1(n / 4), dim3(256), reinterpret_cast<f32x4*>(out), reinterpret_cast<const f32x4*>(res), reinterpret_cast<const f32x4*>(y), reinterpret_cast<const f32x4*>(ls), n / 4, D / 4);
   else KL(scale_add_kernel, g1(n), dim3(256), out, res, y, ls, n, D);
 }
@@ -1133,82 +1182,71 @@ static void block_fwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   float* const h2 = a.h2 ? a.h2 : t.h;
   float* const gg = a.g ? a.g : t.g;
   KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_in, h, a.mean0, a.rstd0, w.l0s, w.l0b, ws, rows, S, D);
-  const int Sp = (S + 3) & ~3;
-  if (op.differential) {
+  const int Sp = score_stride(S);
+  if (op.differential()) {
     // DifferentialAttention: bias-free q, k, v; 2 H sub-heads of width hd / 2 with stride hd / 2 in q and k, unscaled
     // scores; softmax_bias_fwd_kernel per sub-head row (the mask is added, as in §20); A = A1 - lambda A2; O = A V; subln into a.o
     const int hp = hd / 2, H2 = 2 * H;
     const DiffLeaves& df = op.dif;
-    linear(st, nb, S, ws, h, w.wq, nullptr, a.q, D, D, 0);
-    linear(st, nb, S, ws, h, w.wk, nullptr, a.k, D, D, 0);
-    linear(st, nb, S, ws, h, w.wv, nullptr, a.v, D, D, 0);
-    bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hp, D, D, Sp, (long)S * D, hp, (long)S * D, hp, (long)H2 * S * Sp, (long)S * Sp, 0, H2, 1.f, 0}, nb);
+    linear(st, nb, S, ws, h, w.wq, nullptr, a.q, D, D);
+    linear(st, nb, S, ws, h, w.wk, nullptr, a.k, D, D);
+    linear(st, nb, S, ws, h, w.wv, nullptr, a.v, D, D);
+    scores(st, nb, S, D, a.q, a.k, a.p, H2, hp);
     KL(softmax_bias_fwd_kernel, dim3((nb * H2 * S + 3) / 4), dim3(256), a.p, nb * H2, S, Sp);
     KL(diff_combine_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, a.pa, op.theta, ws, df.lq1, df.lk1, df.lq2, df.lk2, op.lambda_init(), nb, H, S, Sp);
-    BG pv{a.pa, a.v, a.oraw, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
-    pv.a_padded = 1;
-    bgemm(st, false, false, pv, nb);
+    apply_scores(st, false, nb, S, D, a.pa, a.v, a.oraw, H, hd);
     KL(diff_subln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.oraw, a.o, op.theta, ws, df.sw, 1.f - op.lambda_init(), rows, S);
   } else {
-    {
-      // q, k, v = h Wq, h Wk, h Wv as ONE batched product when weights, biases and outputs are equally spaced in memory order
-      // (shared weights): 3 x 390 tiles in one launch instead of three launches of 198 double tiles that fill 77 % of the chip
-      const float* Wm[3] = {w.wq, w.wk, w.wv};
-      const float* Bm[3] = {w.bq, w.bk, w.bv};
-      float* Ym[3] = {a.q, a.k, a.v};
-      int ord[3] = {0, 1, 2};
-      for (int i = 0; i < 2; ++i)
-        for (int j = 0; j < 2 - i; ++j)
-          if (Wm[ord[j]] > Wm[ord[j + 1]]) { const int tsw = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = tsw; }
-      const long wsd = Wm[ord[1]] - Wm[ord[0]], bsd = Bm[ord[1]] - Bm[ord[0]], ysd = Ym[ord[1]] - Ym[ord[0]];
-      const bool one = ws == 0 && Wm[ord[2]] - Wm[ord[1]] == wsd && Bm[ord[2]] - Bm[ord[1]] == bsd && Ym[ord[2]] - Ym[ord[1]] == ysd &&
-                       wsd % 4 == 0 && ysd % 4 == 0;
-      if (one) {
-        BG g{h, Wm[ord[0]], Ym[ord[0]], Bm[ord[0]], nb * S, D, D, D, D, D, 0, 0, 0, wsd, 0, ysd, 0, 3, 1.f, 0};
-        g.sBias1 = bsd;
-        bgemm(st, false, false, g, 1);
-      } else {
-        for (int i = 0; i < 3; ++i) linear(st, nb, S, ws, h, Wm[i], Bm[i], Ym[i], D, D, 0);
-      }
+    // q, k, v = h Wq, h Wk, h Wv as ONE batched product when weights, biases and outputs are equally spaced in memory order
+    // (shared weights): 3 x 390 tiles in one launch instead of three launches of 198 double tiles that fill 77 % of the chip
+    const float* Wm[3] = {w.wq, w.wk, w.wv};
+    const float* Bm[3] = {w.bq, w.bk, w.bv};
+    float* Ym[3] = {a.q, a.k, a.v};
+    const Spacing sw = spacing(Wm), sb = spacing(Bm, sw.ord), sy = spacing(Ym, sw.ord);
+    const int first = sw.ord[0];
+    if (ws == 0 && sw.even && sb.even && sy.even && sw.step % 4 == 0 && sy.step % 4 == 0)
+      bgemm(st, false, false, with_bias(product(mat(h, D), inner_batch(Wm[first], D, sw.step), inner_batch(Ym[first], D, sy.step), nb * S, D, D, Store::Set, 1.f, 3),
+                                        Bm[first], 0, sb.step), 1);
+    else
+      for (int i = 0; i < 3; ++i) linear(st, nb, S, ws, h, Wm[i], Bm[i], Ym[i], D, D);
+    scores(st, nb, S, D, a.q, a.k, a.p, H, hd, 1.f / sqrtf((float)hd));      // scores[b][h] = q_h k_h^T / sqrt(hd)
+    const dim3 sgrid((nb * H * S + 3) / 4);
+    // mode (softmax_fwd_kernel): 0 the policy's mask, 1 the context mask from am, 2 none
+    auto softmax = [&](int mode) { KL(softmax_fwd_kernel, sgrid, dim3(256), a.p, nb * H, S, S, mode, op.am, H, Sp); };
+    switch (op.attn) {
+      case Attn::Dense: softmax(2); break;
+      case Attn::Context: softmax(1); break;
+      case Attn::Policy: softmax(0); break;
+      case Attn::ContextTokens: KL(softmax_tokens_fwd_kernel, sgrid, dim3(256), a.p, nb * H, S, S - 1 - op.NL, op.am, H, Sp); break;
+      case Attn::PolicyLang: KL(softmax_lang_fwd_kernel, sgrid, dim3(256), a.p, nb * H, S, op.T, Sp); break;
+      case Attn::Bias: KL(softmax_bias_fwd_kernel, sgrid, dim3(256), a.p, nb * H, S, Sp); break;
+      case Attn::Differential: break;      // (above)
     }
-    // scores[b][h] = q_h k_h^T / sqrt(hd)
-    // the S x S attention matrices have row stride Sp = S rounded up to 4 floats, zeros behind every row (written by the softmax
-    // kernels): as A operands they are staged with float4 loads like everything else (S = 257: the all-dword staging these four
-    // products per layer were left with cost 3.6 ms per step)
-    bgemm(st, false, true, BG{a.q, a.k, a.p, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, (long)H * S * Sp, (long)S * Sp, 0, H, 1.f / sqrtf((float)hd), 0}, nb);
-    if (op.layer_rows > 0) KL(softmax_tokens_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S - 1 - op.layer_rows, op.am, H, Sp);
-    else if (op.lang_T > 0) KL(softmax_lang_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, op.lang_T, Sp);
-    else if (op.mask_as_bias) KL(softmax_bias_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, Sp);
-    else KL(softmax_fwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, nb * H, S, S, op.mask_mode, op.am, H, Sp);
-    {
-      BG pv{a.p, a.v, a.o, nullptr, S, hd, S, Sp, D, D, (long)H * S * Sp, (long)S * Sp, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0};
-      pv.a_padded = 1;
-      bgemm(st, false, false, pv, nb);
-    }
+    apply_scores(st, false, nb, S, D, a.p, a.v, a.o, H, hd);
   }
   if (w.ls1) {
-    linear(st, nb, S, ws, a.o, w.wo, w.bo, a.y1, D, D, 0);
+    linear(st, nb, S, ws, a.o, w.wo, w.bo, a.y1, D, D);
     scale_add(st, a.x_mid, a.x_in, a.y1, w.ls1, (long)rows * D, D);
   } else if (dr.on()) {                                                    // the branch into t.y (free in a block without LayerScale), then x_mid = x_in + drop(y)
-    linear(st, nb, S, ws, a.o, w.wo, w.bo, t.y, D, D, 0);
+    linear(st, nb, S, ws, a.o, w.wo, w.bo, t.y, D, D);
     dropout_fwd(st, dr, NOISE_ATTN_OUT, op.layer, a.x_mid, a.x_in, t.y, nb, (long)S * D);
   } else {
     ENQ(hipMemcpyAsync, a.x_mid, a.x_in, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
-    linear(st, nb, S, ws, a.o, w.wo, w.bo, a.x_mid, D, D, 1);
+    linear(st, nb, S, ws, a.o, w.wo, w.bo, a.x_mid, D, D, Store::Add);
   }
   KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_mid, h2, a.mean1, a.rstd1, w.l1s, w.l1b, ws, rows, S, D);
-  linear(st, nb, S, ws, h2, w.w1, w.b1, a.u, D, F, 0);
+  linear(st, nb, S, ws, h2, w.w1, w.b1, a.u, D, F);
   KL(gelu_fwd_kernel, g1((long)rows * F), dim3(256), a.u, gg, (long)rows * F, op.gelu_erf);
   if (dr.on()) dropout_fwd(st, dr, NOISE_MLP_HIDDEN, op.layer, gg, nullptr, gg, nb, (long)S * F);     // g is kept (or recomputed) dropped
   if (w.ls2) {
-    linear(st, nb, S, ws, gg, w.w2, w.b2, a.y2, F, D, 0);
+    linear(st, nb, S, ws, gg, w.w2, w.b2, a.y2, F, D);
     scale_add(st, x_out, a.x_mid, a.y2, w.ls2, (long)rows * D, D);
   } else if (dr.on()) {
-    linear(st, nb, S, ws, gg, w.w2, w.b2, t.y, F, D, 0);
+    linear(st, nb, S, ws, gg, w.w2, w.b2, t.y, F, D);
     dropout_fwd(st, dr, NOISE_MLP_OUT, op.layer, x_out, a.x_mid, t.y, nb, (long)S * D);
   } else {
     ENQ(hipMemcpyAsync, x_out, a.x_mid, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st);
-    linear(st, nb, S, ws, gg, w.w2, w.b2, x_out, F, D, 1);
+    linear(st, nb, S, ws, gg, w.w2, w.b2, x_out, F, D, Store::Add);
   }
 }
 
@@ -1220,15 +1258,15 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   const int hd = D / H, rows = nb * S;
   const bool shared = gs == 0;
   auto wgrad = [&](const float* X, int K, const float* dY, int N, float* dW) {   // dW[K][N] (+)= X^T dY
-    if (shared) bgemm(st, true, false, BG{X, dY, dW, nullptr, K, N, rows, K, N, N, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
-    else bgemm(st, true, false, BG{X, dY, dW, nullptr, K, N, S, K, N, N, (long)S * K, 0, (long)S * N, 0, gs, 0, 0, 1, 1.f, 1}, nb);
+    if (shared) bgemm(st, true, false, product(mat(X, K), mat(dY, N), mat(dW, N), K, N, rows, Store::AddSplitK), 1);
+    else bgemm(st, true, false, product(per_sample(X, S, K), per_sample(dY, S, N), per_episode(dW, N, gs), K, N, S, Store::Add), nb);
   };
   auto bgrad = [&](const float* dY, int N, float* dB) {
     // the 4-column form wins on the narrow matrices of the policy / hypernetwork; on the encoder's 768- and 3072-wide ones
     // its fewer, fatter waves lose to the one-column form (17 vs 23 us)
-    if (op.differential) { KL(colsum_episode_kernel, dim3((N + 63) / 64, nb), dim3(256), dY, dB, gs, S, S, N); return; }      // no atomics
-    const bool v4 = N % 4 == 0 && N <= 512 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0;
-    if (shared && N % 4 == 0 && N > 512 && rows >= 2048 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0)
+    if (op.differential()) { KL(colsum_episode_kernel, dim3((N + 63) / 64, nb), dim3(256), dY, dB, gs, S, S, N); return; }      // no atomics
+    const bool v4 = N % 4 == 0 && N <= 512 && aligned16(dY);
+    if (shared && N % 4 == 0 && N > 512 && rows >= 2048 && aligned16(dY))
       KL(colsum4b_kernel, dim3((N / 4 + 63) / 64, 1, (rows + CSB_WAVES * 8 * CSB_BATCH - 1) / (CSB_WAVES * 8 * CSB_BATCH)), dim3(CSB_WAVES * 64), dY, dB, rows, N);
     else if (shared && v4) KL(colsum4_kernel, dim3((N / 4 + 63) / 64, 1, (rows + 31) / 32), dim3(64), dY, dB, 0, rows, rows, N, 1);
     else if (shared) KL(colsum_kernel, dim3((N + 63) / 64, 1, (rows + 63) / 64), dim3(64), dY, dB, 0, rows, rows, N, 1);
@@ -1236,12 +1274,12 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     else KL(colsum_kernel, dim3((N + 63) / 64, nb, (S + 63) / 64), dim3(64), dY, dB, gs, S, S, N, nb);
   };
   auto ln_bwd = [&](const float* x, const float* dy, const float* mean, const float* rstd, const float* sc, float* gs_, float* gb_) {
-    if (op.differential) {                                                                                              // no atomics
+    if (op.differential()) {                                                                                            // no atomics
       KL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), x, dy, mean, rstd, sc, dx, (float*)nullptr, (float*)nullptr, gs, rows, S, D, 1);
       KL(ln_pgrad_episode_kernel, dim3((D + 63) / 64, nb), dim3(256), x, dy, mean, rstd, gs_, gb_, gs, S, D);
       return;
     }
-    if (shared && D % 4 == 0 && D <= 1024 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
+    if (shared && D % 4 == 0 && D <= 1024 && aligned16(x, dy, dx)) {
       KL(ln_bwd_shared_kernel, dim3((rows + 63) / 64), dim3(LNB_WAVES * 64), x, dy, mean, rstd, sc, dx, gs_, gb_, rows, D, 1);
     } else if (shared) {
       KL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), x, dy, mean, rstd, sc, dx, (float*)nullptr, (float*)nullptr, 0, rows, S, D, 1);
@@ -1251,7 +1289,7 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
     }
   };
   auto ls_bwd = [&](const float* dxp, const float* y, const float* ls, float* dy, float* dls) {
-    if (D % 4 == 0 && rows >= 1024 && ((reinterpret_cast<uintptr_t>(dxp) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0)
+    if (D % 4 == 0 && rows >= 1024 && aligned16(dxp, y, dy))
       KL(ls_bwd4_kernel, dim3((D / 4 + 63) / 64, (rows + 127) / 128), dim3(512), dxp, y, ls, dy, dls, rows, D);
     else
       KL(ls_bwd_kernel, dim3((D + 63) / 64, (rows + 63) / 64), dim3(64), dxp, y, ls, dy, dls, rows, D);
@@ -1273,12 +1311,12 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   }
   wgrad(gg, F, dy, D, gw.w2);
   bgrad(dy, D, gw.b2);
-  linear_dx(st, nb, S, ws, dy, w.w2, t.d, F, D, 0);                                                                     // dg = dy W2^T
+  linear_dx(st, nb, S, ws, dy, w.w2, t.d, F, D);                                                                        // dg = dy W2^T
   if (dr.on()) dropout_bwd(st, dr, NOISE_MLP_HIDDEN, op.layer, t.d, t.d, nb, (long)S * F);
   KL(gelu_bwd_kernel, g1((long)rows * F), dim3(256), a.u, t.d, (long)rows * F, op.gelu_erf);                           // du
   wgrad(h2, D, t.d, F, gw.w1);
   bgrad(t.d, F, gw.b1);
-  linear_dx(st, nb, S, ws, t.d, w.w1, t.g, D, F, 0);                                                                    // dh2 -> t.g[rows][D]
+  linear_dx(st, nb, S, ws, t.d, w.w1, t.g, D, F);                                                                       // dh2 -> t.g[rows][D]
   ln_bwd(a.x_mid, t.g, a.mean1, a.rstd1, w.l1s, gw.l1s, gw.l1b);
   //   (dx now = gradient wrt x_mid)
   // ---- attention: x_mid = x_in + [ls1 (.)] (o Wo + bo)
@@ -1292,32 +1330,29 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   }
   wgrad(a.o, D, dy, D, gw.wo);
   if (gw.bo) bgrad(dy, D, gw.bo);                                                                                       // (DifferentialAttention's projections have no bias)
-  linear_dx(st, nb, S, ws, dy, w.wo, t.d, D, D, 0);                                                                     // do
+  linear_dx(st, nb, S, ws, dy, w.wo, t.d, D, D);                                                                        // do
   // dp = do_h v_h^T ; dv_h = p^T do_h
-  const int Sp = (S + 3) & ~3;                                                                                          // row stride of p / dp (block_fwd)
-  const long ss0 = (long)H * S * Sp, ss1 = (long)S * Sp;
-  auto padded = [](BG g) { g.a_padded = 1; return g; };
-  if (op.differential) {
+  const int Sp = score_stride(S);                                                                                       // row stride of p / dp (block_fwd)
+  if (op.differential()) {
     // t.d = dN -> dO and dw (subln); dP = dO V^T once per head; dV = A^T dO; both softmax backwards from dP into t.dp = ds [nb][2 H];
     // d lambda from the kept row sums; dq_c = ds_c k_c, dk_c = ds_c^T q_c over the 2 H sub-heads, scale 1
     const int hp = hd / 2, H2 = 2 * H;
     const DiffLeaves& df = op.dif;
-    const long sd0 = (long)H2 * S * Sp;
     KL(diff_subln_bwd_kernel, dim3(nb), dim3(256), a.oraw, t.d, op.theta, op.dtheta, ws, df.sw, 1.f - op.lambda_init(), S);
-    bgemm(st, false, true, BG{t.d, a.v, t.dP, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
-    bgemm(st, true, false, padded(BG{a.pa, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
+    scores(st, nb, S, D, t.d, a.v, t.dP, H, hd);
+    apply_scores(st, true, nb, S, D, a.pa, t.d, t.dv, H, hd);
     KL(diff_softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dP, t.dp, t.t2, op.theta, ws, df.lq1, df.lk1, df.lq2, df.lk2, op.lambda_init(), nb, H, S, Sp);
     KL(diff_lambda_bwd_kernel, dim3(nb), dim3(64), t.t2, op.theta, op.dtheta, ws, df.lq1, df.lk1, df.lq2, df.lk2, H * S);
-    bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hp, S, Sp, D, D, sd0, ss1, (long)S * D, hp, (long)S * D, hp, 0, H2, 1.f, 0}), nb);
-    bgemm(st, true, false, padded(BG{t.dp, a.q, t.dk, nullptr, S, hp, S, Sp, D, D, sd0, ss1, (long)S * D, hp, (long)S * D, hp, 0, H2, 1.f, 0}), nb);
+    apply_scores(st, false, nb, S, D, t.dp, a.k, t.dq, H2, hp);
+    apply_scores(st, true, nb, S, D, t.dp, a.q, t.dk, H2, hp);
   } else {
-    bgemm(st, false, true, BG{t.d, a.v, t.dp, nullptr, S, S, hd, D, D, Sp, (long)S * D, hd, (long)S * D, hd, ss0, ss1, 0, H, 1.f, 0}, nb);
-    bgemm(st, true, false, padded(BG{a.p, t.d, t.dv, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, 1.f, 0}), nb);
+    scores(st, nb, S, D, t.d, a.v, t.dp, H, hd);
+    apply_scores(st, true, nb, S, D, a.p, t.d, t.dv, H, hd);
     if (aux) KL(attention_aux_kernel, dim3(nb), dim3(256), *aux);                                                            // dp row S-1 += d aux / dp
     KL(softmax_bwd_kernel, dim3((nb * H * S + 3) / 4), dim3(256), a.p, t.dp, nb * H * S, S, Sp);                             // ds
     const float sc = 1.f / sqrtf((float)hd);
-    bgemm(st, false, false, padded(BG{t.dp, a.k, t.dq, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);   // dq = ds k / sqrt(hd)
-    bgemm(st, true, false, padded(BG{t.dp, a.q, t.dk, nullptr, S, hd, S, Sp, D, D, ss0, ss1, (long)S * D, hd, (long)S * D, hd, 0, H, sc, 0}), nb);    // dk = ds^T q / sqrt(hd)
+    apply_scores(st, false, nb, S, D, t.dp, a.k, t.dq, H, hd, sc);                                                           // dq = ds k / sqrt(hd)
+    apply_scores(st, true, nb, S, D, t.dp, a.q, t.dk, H, hd, sc);                                                            // dk = ds^T q / sqrt(hd)
   }
   const float* h = a.h ? a.h : t.h;
   if (!a.h) KL(ln_fwd_kernel, dim3((rows + 3) / 4), dim3(256), a.x_in, t.h, a.mean0, a.rstd0, w.l0s, w.l0b, ws, rows, S, D);      // recompute h
@@ -1327,24 +1362,13 @@ static void block_bwd(hipStream_t st, int nb, int S, int D, int H, int F, long w
   const float* Wm[3] = {w.wq, w.wk, w.wv};
   // the three weight gradients h^T dq, h^T dk, h^T dv as ONE batched product when the three dY buffers and the three gradient
   // leaves are equally spaced (shared weights; any order): one launch whose split-K needs a third of the atomic adds per element
-  int ord[3] = {0, 1, 2};                                    // q, k, v in the order of their gradient leaves in memory
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2 - i; ++j)
-      if (gWm[ord[j]] > gWm[ord[j + 1]]) { const int tsw = ord[j]; ord[j] = ord[j + 1]; ord[j + 1] = tsw; }
-  const long dys = dqkv[ord[1]] - dqkv[ord[0]], gws = gWm[ord[1]] - gWm[ord[0]];
-  const bool one = shared && dqkv[ord[2]] - dqkv[ord[1]] == dys && gWm[ord[2]] - gWm[ord[1]] == gws && dys % 4 == 0;
-  if (one) bgemm(st, true, false, BG{h, dqkv[ord[0]], gWm[ord[0]], nullptr, D, D, rows, D, D, D, 0, 0, 0, dys, 0, gws, 0, 3, 1.f, 1, 1, 1}, 1);
+  const Spacing sg = spacing(gWm), sd = spacing(dqkv, sg.ord);      // q, k, v in the order of their gradient leaves in memory
+  const bool one = shared && sd.even && sg.even && sd.step % 4 == 0;
+  if (one) bgemm(st, true, false, product(mat(h, D), inner_batch(dqkv[sg.ord[0]], D, sd.step), inner_batch(gWm[sg.ord[0]], D, sg.step), D, D, rows, Store::AddSplitK, 1.f, 3), 1);
   for (int i = 0; i < 3; ++i) {
     if (!one) wgrad(h, D, dqkv[i], D, gWm[i]);
-    // The key bias adds q . bk / sqrt(hd) to every kept score of a query's row, and a softmax row ignores a constant: its gradient is
-    // zero under any mask (sum_k ds[q][k] = 0).  What the column sum of dk gives instead is the operand rounding of ds in dk = ds^T q,
-    // and a language query's few keys carry ds entries of the size of dp: with the language rows the leaf is left at the zero it is
-    // (dtheta is cleared at the head of the step).  Without them the step launches what it always launched.  With the mask added as a
-    // bias every query has every key, the constant is still one per row, and the leaf is left at zero in the same way:
-    // measured at the README geometry the column sum came to 1.9e-3 of the leaf metric's 2e-3, all of it rounding.  Under the policy's
-    // dropout (hvla_train_noise) the kept activations are 1 / keep_prob larger and the same rounding came to 1.5e-3 at MID: left at zero too.
-    if (gBm[i] && !((op.lang_T > 0 || op.mask_as_bias || dr.on()) && i == 1)) bgrad(dqkv[i], D, gBm[i]);
-    linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0);                                                         // dh
+    if (gBm[i] && !(i == 1 && op.key_bias_grad_is_rounding())) bgrad(dqkv[i], D, gBm[i]);      // (BlkOpt: the key bias's gradient)
+    linear_dx(st, nb, S, ws, dqkv[i], Wm[i], t.g, D, D, i > 0 ? Store::Add : Store::Set);                                // dh
   }
   ln_bwd(a.x_in, t.g, a.mean0, a.rstd0, w.l0s, gw.l0s, gw.l0b);
 }
@@ -1357,59 +1381,73 @@ struct Plan {
   float *cmean, *crstd, *ctx, *dctx, *ctxn, *dxrow, *emean, *erstd;
   float *ntok, *ncls;        // hvla_train_noise: the frozen encoder's tokens + sigma z, the masked CLS rows (null: not taken)
   long used;
+  // the buffer table, in the order of the takes: a -DHVLA_TRAIN_TRACE build records it for train_trace_plan, the libraries build no
+  // string and store nothing
 #ifdef HVLA_TRAIN_TRACE
-  std::vector<std::pair<long, long>> taken;      // (offset, floats asked for) of every take(), in order: train_trace_plan prints them
+  struct Taken { std::string name; long offset, floats; };
+  std::vector<Taken> taken;
+  void note(const char* kind, size_t l, const char* name, long offset, long n) {      // kind: "<kind>[<l>].<name>", a block's buffer
+    taken.push_back({kind ? std::string(kind) + "[" + std::to_string(l) + "]." + name : std::string(name), offset, n});
+  }
+#else
+  void note(const char*, size_t, const char*, long, long) {}
 #endif
 };
 static Plan make_plan(const Geom& g, int B, bool enc, float* base, const TrainNoise& nz) {
   Plan pl;
   float* ws = base;
-#ifdef HVLA_TRAIN_TRACE
-  auto take = [&](long n) { float* p = ws; ws += (n + 3) / 4 * 4; pl.taken.push_back({p - base, n}); return p; };
-#else
-  auto take = [&](long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
-#endif
-  // diff: a DifferentialAttention block -- p holds 2 h tables, and pa and oraw follow the block's other buffers
-  auto take_blk = [&](long nb, long s, long d, long h, long f, bool ls, bool diff = false) {
-    BlkBuf b; b.x_in = take(nb * s * d); b.mean0 = take(nb * s); b.rstd0 = take(nb * s); b.k = take(nb * s * d); b.q = take(nb * s * d);      // k, q, v: the order of the weight leaves (block_fwd batches the three)
-    b.v = take(nb * s * d); b.p = take(nb * (diff ? 2 * h : h) * s * ((s + 3) & ~3L)); b.o = take(nb * s * d); b.x_mid = take(nb * s * d); b.mean1 = take(nb * s);
-    b.rstd1 = take(nb * s); b.u = take(nb * s * f);
-    b.y1 = ls ? take(nb * s * d) : nullptr; b.y2 = ls ? take(nb * s * d) : nullptr;
+  auto take = [&](const char* name, long n, const char* kind = nullptr, size_t l = 0) {
+    float* p = ws;
+    ws += (n + 3) / 4 * 4;
+    pl.note(kind, l, name, p - base, n);
+    return p;
+  };
+  // block l of pl.<kind>.  diff: a DifferentialAttention block -- p holds 2 h tables, and pa and oraw follow the block's other buffers
+  auto take_blk = [&](const char* kind, size_t l, long nb, long s, long d, long h, long f, bool ls, bool diff = false) {
+    auto tk = [&](const char* name, long n) { return take(name, n, kind, l); };
+    const long x = nb * s * d, r = nb * s;
+    BlkBuf b; b.x_in = tk("x_in", x); b.mean0 = tk("mean0", r); b.rstd0 = tk("rstd0", r); b.k = tk("k", x); b.q = tk("q", x);      // k, q, v: the order of the weight leaves (block_fwd batches the three)
+    b.v = tk("v", x); b.p = tk("p", nb * score_floats(h, s, diff)); b.o = tk("o", x); b.x_mid = tk("x_mid", x); b.mean1 = tk("mean1", r);
+    b.rstd1 = tk("rstd1", r); b.u = tk("u", r * f);
+    b.y1 = ls ? tk("y1", x) : nullptr; b.y2 = ls ? tk("y2", x) : nullptr;
     // 288 GB of HBM: the LayerNorm and GELU outputs are kept (B = 32 with the encoder trained: 1.8 GB) instead of recomputed
-    b.h = take(nb * s * d); b.h2 = take(nb * s * d); b.g = take(nb * s * f);
-    b.pa = diff ? take(nb * h * s * ((s + 3) & ~3L)) : nullptr; b.oraw = diff ? take(nb * s * d) : nullptr;
+    b.h = tk("h", x); b.h2 = tk("h2", x); b.g = tk("g", r * f);
+    b.pa = diff ? tk("pa", nb * score_floats(h, s)) : nullptr; b.oraw = diff ? tk("oraw", x) : nullptr;
     return b;
   };
   const long S = g.pos_rows(), D = g.D, H = g.H, F = g.M, NL = g.NL(), Sc = g.T + 1 + NL, C = g.C, Hc = g.ctx_heads, Fc = g.ctx_mlp;     // S: the policy's rows, T + P + 1 under use_language_token; NL = 1 without layer tokens
   const long Se = g.P() + 1, E = g.E, He = g.enc_heads, Fe = g.enc_mlp;
+  const bool diff = g.differential != 0;
   pl.cb.resize(g.ctx_layers); pl.pb.resize(g.L); pl.eb.resize(enc ? g.enc_layers : 0);
-  for (auto& b : pl.cb) b = take_blk(B, Sc, C, Hc, Fc, false);
-  for (auto& b : pl.pb) b = take_blk(B, S, D, H, F, false, g.differential != 0);
-  for (auto& b : pl.eb) b = take_blk(B, Se, E, He, Fe, true);
-  pl.cx_fin = take(B * Sc * C); pl.cdx = take(B * Sc * C);
-  pl.px_fin = take(B * S * D); pl.pdx = take(B * S * D);
+  for (size_t l = 0; l < pl.cb.size(); ++l) pl.cb[l] = take_blk("cb", l, B, Sc, C, Hc, Fc, false);
+  for (size_t l = 0; l < pl.pb.size(); ++l) pl.pb[l] = take_blk("pb", l, B, S, D, H, F, false, diff);
+  for (size_t l = 0; l < pl.eb.size(); ++l) pl.eb[l] = take_blk("eb", l, B, Se, E, He, Fe, true);
+  pl.cx_fin = take("cx_fin", B * Sc * C); pl.cdx = take("cdx", B * Sc * C);
+  pl.px_fin = take("px_fin", B * S * D); pl.pdx = take("pdx", B * S * D);
   pl.ex_fin = pl.edx = pl.eh = pl.patches = pl.emean = pl.erstd = nullptr;
   if (enc) {
-    pl.ex_fin = take(B * Se * E); pl.edx = take(B * Se * E); pl.eh = take(B * Se * E);
-    pl.patches = take((long)B * g.P() * g.patch * g.patch * 3);
-    pl.emean = take(B * Se); pl.erstd = take(B * Se);
+    pl.ex_fin = take("ex_fin", B * Se * E); pl.edx = take("edx", B * Se * E); pl.eh = take("eh", B * Se * E);
+    pl.patches = take("patches", (long)B * g.P() * g.patch * g.patch * 3);
+    pl.emean = take("emean", B * Se); pl.erstd = take("erstd", B * Se);
   }
   // temporaries are used by one transformer at a time: size them for the largest.  t.g and t.d hold rows x F (the GELU output's
   // gradient, du) AND rows x D (dh2 = du W1^T and the three dh products go to t.g, do = dy Wo^T to t.d): the larger of the two,
   // since accept.h admits F < D (policy mlp 32, ctx_mlp 16, enc_mlp 128 under a wider model)
   auto mx = [&](long a, long b, long c) { c = enc ? c : 0; return a > b ? (a > c ? a : c) : (b > c ? b : c); };
-  const long rd = mx(B * S * D, B * Sc * C, B * Se * E), rf = mx(B * S * F, B * Sc * Fc, B * Se * Fe), hss = mx(B * (g.differential ? 2 * H : H) * S * ((S + 3) & ~3L), B * Hc * Sc * ((Sc + 3) & ~3L), B * He * Se * ((Se + 3) & ~3L));
-  const long rg = rf > rd ? rf : rd;
-  pl.t.h = take(rd); pl.t.g = take(rg); pl.t.d = take(rg); pl.t.dk = take(rd); pl.t.dq = take(rd); pl.t.dv = take(rd);      /* k, q, v: the order of the leaves (block_bwd batches the three) */ pl.t.dp = take(hss);
-  pl.t.y = take(rd);
-  pl.cmean = take(B * NL); pl.crstd = take(B * NL); pl.ctx = take(B * NL * C); pl.dctx = take(B * NL * C); pl.ctxn = take(B * NL * C);
-  pl.dxrow = take(B * D);
+  const long rd = mx(B * S * D, B * Sc * C, B * Se * E), rf = mx(B * S * F, B * Sc * Fc, B * Se * Fe);
+  const long hss = mx(B * score_floats(H, S, diff), B * score_floats(Hc, Sc), B * score_floats(He, Se)), rg = rf > rd ? rf : rd;
+  pl.t.h = take("t.h", rd); pl.t.g = take("t.g", rg); pl.t.d = take("t.d", rg);
+  pl.t.dk = take("t.dk", rd); pl.t.dq = take("t.dq", rd); pl.t.dv = take("t.dv", rd);      // k, q, v: the order of the leaves (block_bwd batches the three)
+  pl.t.dp = take("t.dp", hss); pl.t.y = take("t.y", rd);
+  pl.cmean = take("cmean", B * NL); pl.crstd = take("crstd", B * NL);
+  pl.ctx = take("ctx", B * NL * C); pl.dctx = take("dctx", B * NL * C); pl.ctxn = take("ctxn", B * NL * C);
+  pl.dxrow = take("dxrow", B * D);
   // the noise copies come last: every offset above is what it is without noise
-  pl.ntok = nz.sigma > 0.f && !enc ? take((long)B * g.P() * E) : nullptr;
-  pl.ncls = nz.image_dropout > 0.f ? take((long)B * E) : nullptr;
+  pl.ntok = nz.sigma > 0.f && !enc ? take("ntok", (long)B * g.P() * E) : nullptr;
+  pl.ncls = nz.image_dropout > 0.f ? take("ncls", (long)B * E) : nullptr;
   // ... and so do DifferentialAttention's two temporaries (t.dp above holds ds of the 2 H sub-heads)
-  pl.t.dP = g.differential ? take(B * H * S * ((S + 3) & ~3L)) : nullptr;
-  pl.t.t2 = g.differential ? take(B * H * S) : nullptr;
+  pl.t.dP = diff ? take("t.dP", B * score_floats(H, S)) : nullptr;
+  pl.t.t2 = diff ? take("t.t2", B * H * S) : nullptr;
   pl.used = ws - base;
   return pl;
 }
@@ -1422,35 +1460,11 @@ void train_context_rows(const Geom& g, int B, bool train_encoder, const TrainNoi
 }
 #ifdef HVLA_TRAIN_TRACE
 // One line `plan <name> <offset> <floats>` per buffer of make_plan (offsets into `work`, the floats the plan asked for), for
-// tools/train_extent_trace.hip: tests/test_train_workspace_extents.py holds every traced operand to ONE of these buffers.  A buffer
-// make_plan takes without a name below prints as `?`, which that test refuses.
+// tools/train_extent_trace.hip: tests/test_train_workspace_extents.py holds every traced operand to ONE of these buffers.  The names
+// are those make_plan's takes give.
 void train_trace_plan(const Geom& g, int B, bool train_encoder, const TrainNoise& nz) {
-  float* const base = static_cast<float*>(train_trace_buffer("work"));
-  const Plan pl = make_plan(g, B, train_encoder, base, nz);
-  std::vector<std::string> name(pl.taken.size(), "?");
-  auto put = [&](const std::string& n, const float* p) {
-    if (!p) return;
-    for (size_t i = 0; i < pl.taken.size(); ++i)
-      if (pl.taken[i].first == p - base && name[i] == "?") { name[i] = n; return; }
-  };
-  auto put_blk = [&](const char* kind, const std::vector<BlkBuf>& v) {
-    for (size_t l = 0; l < v.size(); ++l) {
-      const BlkBuf& b = v[l];
-      const std::string pre = std::string(kind) + "[" + std::to_string(l) + "].";
-      put(pre + "x_in", b.x_in); put(pre + "mean0", b.mean0); put(pre + "rstd0", b.rstd0); put(pre + "k", b.k); put(pre + "q", b.q);
-      put(pre + "v", b.v); put(pre + "p", b.p); put(pre + "o", b.o); put(pre + "x_mid", b.x_mid); put(pre + "mean1", b.mean1);
-      put(pre + "rstd1", b.rstd1); put(pre + "u", b.u); put(pre + "y1", b.y1); put(pre + "y2", b.y2); put(pre + "h", b.h);
-      put(pre + "h2", b.h2); put(pre + "g", b.g); put(pre + "pa", b.pa); put(pre + "oraw", b.oraw);
-    }
-  };
-  put_blk("cb", pl.cb); put_blk("pb", pl.pb); put_blk("eb", pl.eb);
-  put("cx_fin", pl.cx_fin); put("cdx", pl.cdx); put("px_fin", pl.px_fin); put("pdx", pl.pdx); put("ex_fin", pl.ex_fin); put("edx", pl.edx);
-  put("eh", pl.eh); put("patches", pl.patches); put("emean", pl.emean); put("erstd", pl.erstd);
-  put("t.h", pl.t.h); put("t.g", pl.t.g); put("t.d", pl.t.d); put("t.dk", pl.t.dk); put("t.dq", pl.t.dq); put("t.dv", pl.t.dv);
-  put("t.dp", pl.t.dp); put("t.y", pl.t.y);
-  put("cmean", pl.cmean); put("crstd", pl.crstd); put("ctx", pl.ctx); put("dctx", pl.dctx); put("ctxn", pl.ctxn); put("dxrow", pl.dxrow);
-  put("ntok", pl.ntok); put("ncls", pl.ncls); put("t.dP", pl.t.dP); put("t.t2", pl.t.t2);
-  for (size_t i = 0; i < pl.taken.size(); ++i) printf("plan %s %ld %ld\n", name[i].c_str(), pl.taken[i].first, pl.taken[i].second);
+  const Plan pl = make_plan(g, B, train_encoder, static_cast<float*>(train_trace_buffer("work")), nz);
+  for (const Plan::Taken& t : pl.taken) printf("plan %s %ld %ld\n", t.name.c_str(), t.offset, t.floats);
 }
 #endif
 
@@ -1483,14 +1497,22 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   const bool src_on = enc && ps.n > 0;      // the position table is trained through its interpolation: its source is the vector's tail
   ENQ(hipMemsetAsync, Gm, 0, (size_t)train_vector_elems(L, ps, enc) * 4, st);
   ENQ(hipMemsetAsync, tb.dtheta, 0, (size_t)B * G * 4, st);
-  BlkOpt ctx_opt{1, in.attn_mask, 0};
-  const BlkOpt enc_opt{2, nullptr, 1};      // these two draw nothing
-  if (lt) ctx_opt.layer_rows = NL;
-  const BlkOpt pol_opt{0, nullptr, 0, Tl, g.mask_as_bias, pdrop};
-  const auto pol_at = [&](int l) {                                                     // the dropout sites carry their layer
-    BlkOpt o = pol_opt;
-    o.layer = l;
-    if (g.differential) { o.differential = 1; o.dif = L.dif[l]; o.theta = tb.theta; o.dtheta = tb.dtheta; }
+  BlkOpt ctx_opt, enc_opt;                  // these two draw nothing
+  ctx_opt.attn = lt ? Attn::ContextTokens : Attn::Context;
+  ctx_opt.am = in.attn_mask;
+  ctx_opt.NL = lt ? NL : 0;
+  enc_opt.attn = Attn::Dense;
+  enc_opt.gelu_erf = 1;
+  // hvla_create refuses every pair of use_language_token, attention_mask_as_bias and differential_attention (api.hip; train_refusal
+  // and accept.h add none), so at most one of the three is set; were two, this order is the priority the blocks always had
+  const Attn pol_attn = g.differential ? Attn::Differential : Tl ? Attn::PolicyLang : g.mask_as_bias ? Attn::Bias : Attn::Policy;
+  const auto pol_at = [&](int l) {
+    BlkOpt o;
+    o.attn = pol_attn;
+    o.T = Tl;
+    o.drop = pdrop;
+    o.layer = l;                                                                       // the dropout sites carry their layer
+    if (o.differential()) { o.dif = L.dif[l]; o.theta = tb.theta; o.dtheta = tb.dtheta; }
     return o;
   };
 
@@ -1501,7 +1523,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     float* ex0 = eb.empty() ? pl.ex_fin : eb[0].x_in;
     if (src_on) ENQ(launch_position_interp, Pe + L.enc_total, ps.n, ps.w, tb.params + L.total + L.e_pos, ps.grid, E, st);     // tail -> slot
     KL(im2col_f32_kernel, g1((long)B * P * Kp), dim3(256), in.images, pl.patches, B, g.image_size, g.patch);
-    bgemm(st, false, false, BG{pl.patches, Pe + L.e_pk, ex0 + E, Pe + L.e_pb, P, E, Kp, Kp, E, E, (long)P * Kp, 0, 0, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
+    bgemm(st, false, false, with_bias(product(per_sample(pl.patches, P, Kp), mat(Pe + L.e_pk, E), per_sample(ex0 + E, Se, E), P, E, Kp), Pe + L.e_pb), B);      // rows 1.. of x0
     KL(enc_x0_kernel, g1((long)B * Se * E), dim3(256), ex0, Pe + L.e_cls, Pe + L.e_pos, B, Se, E);
     for (int l = 0; l < g.enc_layers; ++l)
       block_fwd(st, B, Se, E, He, Fe, 0, bind(Pe, L.enc[l]), eb[l], l + 1 < g.enc_layers ? eb[l + 1].x_in : pl.ex_fin, t, enc_opt);
@@ -1528,8 +1550,9 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // =============================== context encoder forward (hypernetwork.py:99-197) ===============================
   float* cx0 = cb.empty() ? cx_fin : cb[0].x_in;
   // tokens: [B][T][lang] . Wt + bt + pos_t  (rows 0..T-1 of each episode's [Sc][C] block)
-  bgemm(st, false, false, BG{in.tok, Pm + L.w_tok, cx0, Pm + L.b_tok, T, C, g.lang_dim, g.lang_dim, C, C, (long)T * g.lang_dim, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
-  bgemm(st, false, false, BG{cls, Pm + L.w_img, cx0 + (long)T * C, Pm + L.b_img, 1, C, E, E, C, C, (long)E, 0, 0, 0, (long)Sc * C, 0, 0, 1, 1.f, 0}, B);
+  const int Kl = g.lang_dim;
+  bgemm(st, false, false, with_bias(product(per_sample(in.tok, T, Kl), mat(Pm + L.w_tok, C), per_sample(cx0, Sc, C), T, C, Kl), Pm + L.b_tok), B);
+  bgemm(st, false, false, with_bias(product(per_sample(cls, 1, E), mat(Pm + L.w_img, C), per_sample(cx0 + (long)T * C, Sc, C), 1, C, E), Pm + L.b_img), B);      // row T
   if (lt) KL(ctx_rows_tokens_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, NL, C);
   else KL(ctx_rows_kernel, g1((long)B * Sc * C), dim3(256), cx0, Pm + L.pos_tok, Pm + L.pos_img, Pm + L.pos_layer, B, T, C);
   for (int l = 0; l < g.ctx_layers; ++l)
@@ -1543,15 +1566,16 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   // an element is C's ascending k steps whatever B and whatever the run's neighbours, so a row stays batch-invariant
   const long Gh = L.Gh;
   const int NLC = NL * C, wg = B >= 96 ? 1 : 0, wc = C >= 96 ? 1 : 0;                  // tile tables: [0] 64, [1] 128 columns (bgemm()'s rule on M)
-  if (lt) bgemm_groups(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, NLC, (int)Gh, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0},
+  const int Gi = (int)G, Ghi = (int)Gh;
+  if (lt) bgemm_groups(st, false, false, with_bias(product(mat(ctx, NLC), mat(Pm + L.wcat, Ghi), mat(tb.theta, Gi), B, Gi, C), Pm + L.bcat),
                        tg.fwd[wg], tg.ntiles[wg], wg ? 128 : 64, 1, tg.vec_ok, 2.0 * B * (double)G * C);
-  else bgemm(st, false, false, BG{ctx, Pm + L.wcat, tb.theta, Pm + L.bcat, B, (int)G, C, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 0}, 1);
+  else bgemm(st, false, false, with_bias(product(mat(ctx, C), mat(Pm + L.wcat, Gi), mat(tb.theta, Gi), B, Gi, C), Pm + L.bcat), 1);
   // =============================== policy forward with per-episode weights ===============================
   const float* TH = tb.theta;
   float* px0 = pb[0].x_in;
   // rows [0, Tl) = token_embedding_b Wl_b + bl_b, every position (base_vit.py:159-166 masks nothing); the patches follow at row Tl
-  if (Tl) bgemm(st, false, false, BG{in.tok, TH + L.wl, px0, TH + L.bl, Tl, D, g.lang_dim, g.lang_dim, D, D, (long)Tl * g.lang_dim, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
-  bgemm(st, false, false, BG{tokens, TH + L.wp, px0 + (long)Tl * D, TH + L.bp, P, D, E, E, D, D, tok_stride, 0, G, 0, (long)S * D, 0, G, 1, 1.f, 0}, B);
+  if (Tl) bgemm(st, false, false, with_bias(product(per_sample(in.tok, Tl, Kl), per_episode(TH + L.wl, D, G), per_sample(px0, S, D), Tl, D, Kl), TH + L.bl, G), B);
+  bgemm(st, false, false, with_bias(product(per_episode(tokens, E, tok_stride), per_episode(TH + L.wp, D, G), per_sample(px0 + (long)Tl * D, S, D), P, D, E), TH + L.bp, G), B);
   KL(x0_finish_kernel, g1((long)B * S * D), dim3(256), px0, TH + L.pos, G, S, D, B);
   if (pdrop.on()) dropout_fwd(st, pdrop, NOISE_POLICY_INPUT, 0, px0, nullptr, px0, B, (long)S * D);      // base_vit.py:205
   for (int l = 0; l < g.L; ++l)
@@ -1562,8 +1586,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
             tb.loss, hp.forward_only ? nullptr : dxrow, tb.actions, tb.logits, B, S, D, g.horizon, g.action_dim, g.tanh_scale, g.max_action, g.clip_target};
   KL(head_loss_kernel, dim3(B), dim3(64), hpp);
   // hvla_train_attention_losses: the last layer's action row, [B][H][S][Sp] like t.dp (block_fwd / block_bwd)
-  const int Sp = (S + 3) & ~3;
-  AuxP auxp{pb[g.L - 1].p, nullptr, (long)H * S * Sp, (long)S * Sp, S, Sp, H, P, aux.w_ent, aux.w_align, aux.w_align > 0.f ? aux.ref : nullptr,
+  const int Sp = score_stride(S);
+  AuxP auxp{pb[g.L - 1].p, nullptr, score_floats(H, S), (long)S * Sp, S, Sp, H, P, aux.w_ent, aux.w_align, aux.w_align > 0.f ? aux.ref : nullptr,
             tb.loss, aux.ent, aux.align, 1.f / (float)B};
   if (aux.on()) KL(attention_aux_kernel, dim3(B), dim3(256), auxp);
   if (hp.forward_only) return hipGetLastError();
@@ -1578,17 +1602,17 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   KL(add_strided_kernel, g1((long)B * S * D), dim3(256), tb.dtheta + L.pos, G, pdx, (long)S * D, B);
   if (g.differential) KL(colsum_episode_kernel, dim3((D + 63) / 64, B), dim3(256), pdx_patch, tb.dtheta + L.bp, G, S, P, D);
   else KL(colsum_kernel, dim3((D + 63) / 64, B, (P + 63) / 64), dim3(64), pdx_patch, tb.dtheta + L.bp, G, S, P, D, B);
-  bgemm(st, true, false, BG{tokens, pdx_patch, tb.dtheta + L.wp, nullptr, E, D, P, E, D, D, tok_stride, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+  bgemm(st, true, false, product(per_episode(tokens, E, tok_stride), per_sample(pdx_patch, S, D), per_episode(tb.dtheta + L.wp, D, G), E, D, P, Store::Add), B);
   if (Tl) {     // dbl = sum of the language rows, dWl = tok^T dx0[:Tl]; nothing flows into token_embedding (T5 is frozen)
     KL(colsum_kernel, dim3((D + 63) / 64, B, (Tl + 63) / 64), dim3(64), pdx, tb.dtheta + L.bl, G, S, Tl, D, B);
-    bgemm(st, true, false, BG{in.tok, pdx, tb.dtheta + L.wl, nullptr, g.lang_dim, D, Tl, g.lang_dim, D, D, (long)Tl * g.lang_dim, 0, (long)S * D, 0, G, 0, 0, 1, 1.f, 1}, B);
+    bgemm(st, true, false, product(per_sample(in.tok, Tl, Kl), per_sample(pdx, S, D), per_episode(tb.dtheta + L.wl, D, G), Kl, D, Tl, Store::Add), B);
   }
   // =============================== DINOv2 backward ===============================
   if (enc) {
     // d tokens_b = (the patch rows of dx0_b) Wp_b^T -> rows 1.. of the final-LayerNorm output gradient (CLS row gets none)
     float* dh = t.y;                                                      // [B][Se][E]; t.y is free between blocks
     ENQ(hipMemsetAsync, dh, 0, (size_t)B * Se * E * 4, st);
-    bgemm(st, false, true, BG{pdx_patch, TH + L.wp, dh + E, nullptr, P, E, D, D, D, E, (long)S * D, 0, G, 0, (long)Se * E, 0, 0, 1, 1.f, 0}, B);
+    bgemm(st, false, true, product(per_sample(pdx_patch, S, D), per_episode(TH + L.wp, D, G), per_sample(dh + E, Se, E), P, E, D), B);
     float* edx = pl.edx;
     KL(ln_bwd_kernel, dim3((B * Se + 3) / 4), dim3(256), pl.ex_fin, dh, pl.emean, pl.erstd, Pe + L.e_lns, edx, (float*)nullptr, (float*)nullptr, 0, B * Se, Se, E, 0);
     KL(ln_pgrad_kernel, dim3((E + 63) / 64, (B * Se + 63) / 64), dim3(64), pl.ex_fin, dh, pl.emean, pl.erstd, Ge + L.e_lns, Ge + L.e_lnb, B * Se, E);
@@ -1598,7 +1622,7 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     KL(colsum_kernel, dim3((Se * E + 63) / 64, 1, (B + 63) / 64), dim3(64), edx, Ge + L.e_pos, 0, B, B, Se * E, 1);       // dpos = sum_b dx0
     ENQ(hipMemcpyAsync, Ge + L.e_cls, Ge + L.e_pos, (size_t)E * 4, hipMemcpyDeviceToDevice, st);                          // dcls = dpos[0]
     KL(colsum_kernel, dim3((E + 63) / 64, 1, (P + 63) / 64), dim3(64), Ge + L.e_pos + E, Ge + L.e_pb, 0, P, P, E, 1);     // dbias = sum_{t>=1} dpos[t]
-    bgemm(st, true, false, BG{pl.patches, edx + E, Ge + L.e_pk, nullptr, Kp, E, P, Kp, E, E, (long)P * Kp, 0, (long)Se * E, 0, 0, 0, 0, 1, 1.f, 2}, B);
+    bgemm(st, true, false, product(per_sample(pl.patches, P, Kp), per_sample(edx + E, Se, E), mat(Ge + L.e_pk, E), Kp, E, P, Store::Atomic), B);
     if (src_on) {                                                        // dsource = A^T dslot; the slot is no parameter: its gradient is zero
       ENQ(launch_position_adjoint, Ge + L.e_pos, ps.n, ps.w, Ge + L.enc_total, ps.grid, E, st);
       ENQ(hipMemsetAsync, Ge + L.e_pos, 0, (size_t)Se * E * 4, st);
@@ -1612,11 +1636,11 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
   if (heads_on && lt) {
     // dW_h[:, hcols] += ctx[:, token]^T dtheta[:, run] and db_h[hcols] += sum_b dtheta[b, run], a grouped launch each; with shared heads
     // the L blocks' runs meet in one head: a real sum, by atomics (the range is the memset's zero)
-    bgemm_groups(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, NLC, (int)G, (int)Gh, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, g.shared_block_heads ? 2 : 1},
+    bgemm_groups(st, true, false, product(mat(ctx, NLC), mat(tb.dtheta, Gi), mat(Gm + L.wcat, Ghi), C, Gi, B, g.shared_block_heads ? Store::Atomic : Store::Add),
                  tg.dw[wc], tg.ntiles[wc], wc ? 128 : 64, 1, tg.vec_ok, 2.0 * B * (double)G * C);
     KL(colsum_groups_kernel, dim3(tg.ntiles[0], 1, (B + 63) / 64), dim3(64), tb.dtheta, G, Gm + L.bcat, tg.fwd[0], B);
   } else if (heads_on) {
-    bgemm(st, true, false, BG{ctx, tb.dtheta, Gm + L.wcat, nullptr, C, (int)G, B, C, (int)G, (int)G, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1}, 1);   // dW_cat = ctx^T dtheta
+    bgemm(st, true, false, product(mat(ctx, C), mat(tb.dtheta, Gi), mat(Gm + L.wcat, Gi), C, Gi, B, Store::Add), 1);                            // dW_cat = ctx^T dtheta
     KL(colsum_kernel, dim3((unsigned)((G + 63) / 64), 1, (B + 63) / 64), dim3(64), tb.dtheta, Gm + L.bcat, 0, B, B, (int)G, 1);                  // db_cat
   }
   if (ctx_on && lt) {
@@ -1624,13 +1648,13 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     // whose rows stay the memset's zero
     ENQ(hipMemsetAsync, dctx, 0, (size_t)B * NLC * 4, st);
     const int td = B >= 96 && C >= 96 ? 128 : 64;
-    bgemm_groups(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)Gh, NLC, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 2},
+    bgemm_groups(st, false, true, product(mat(tb.dtheta, Gi), mat(Pm + L.wcat, Ghi), mat(dctx, NLC), B, C, Gi, Store::Atomic),
                  tg.dctx, tg.ndctx, td, (C + td - 1) / td, tg.vec_ok, 2.0 * B * (double)G * C);
     if (cdrop.on()) dropout_bwd(st, cdrop, NOISE_CONTEXT, 0, dctx, dctx, B, (long)NLC);
   } else if (ctx_on) {
     ENQ(hipMemsetAsync, dctx, 0, (size_t)B * C * 4, st);
     // dctx = dtheta W_cat^T: [B, G] x [G, C], a K = 201 500 product onto a B x C output -> split-K over the whole chip
-    bgemm(st, false, true, BG{tb.dtheta, Pm + L.wcat, dctx, nullptr, B, C, (int)G, (int)G, (int)G, C, 0, 0, 0, 0, 0, 0, 0, 1, 1.f, 1, 1, 1}, 1);
+    bgemm(st, false, true, product(mat(tb.dtheta, Gi), mat(Pm + L.wcat, Gi), mat(dctx, C), B, C, Gi, Store::AddSplitK), 1);
     if (cdrop.on()) dropout_bwd(st, cdrop, NOISE_CONTEXT, 0, dctx, dctx, B, C);
   }
   if (bucket_done) ENQ(hipEventRecord, bucket_done[1], st);             // W_cat, b_cat are final
@@ -1644,8 +1668,8 @@ hipError_t train_step(const Geom& g, const TrainLayout& L, const TrainBuffers& t
     // inputs: tokens rows -> w_tok, b_tok, pos_tok ; image row -> w_img, b_img, pos_img ; layer row -> pos_layer
     if (lt) KL(ctx_rows_tokens_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, NL, C);
     else KL(ctx_rows_bwd_kernel, g1((long)B * Sc * C), dim3(256), cdx, Gm + L.pos_tok, Gm + L.pos_img, Gm + L.pos_layer, Gm + L.b_tok, Gm + L.b_img, B, T, C);
-    bgemm(st, true, false, BG{in.tok, cdx, Gm + L.w_tok, nullptr, g.lang_dim, C, T, g.lang_dim, C, C, (long)T * g.lang_dim, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
-    bgemm(st, true, false, BG{cls, cdx + (long)T * C, Gm + L.w_img, nullptr, E, C, 1, E, C, C, (long)E, 0, (long)Sc * C, 0, 0, 0, 0, 1, 1.f, 2}, B);
+    bgemm(st, true, false, product(per_sample(in.tok, T, Kl), per_sample(cdx, Sc, C), mat(Gm + L.w_tok, C), Kl, C, T, Store::Atomic), B);
+    bgemm(st, true, false, product(per_sample(cls, 1, E), per_sample(cdx + (long)T * C, Sc, C), mat(Gm + L.w_img, C), E, C, 1, Store::Atomic), B);
   }
   if (bucket_done) ENQ(hipEventRecord, bucket_done[2], st);             // the context encoder's leaves: everything is final
   return hipGetLastError();
